@@ -8,12 +8,16 @@ logits + uint8 argmax mask for every tile.  Multi-GPU: one process per GPU, each
 segments its own 32-tile batch (tiles are independent units -> weak scaling, no
 data-path collective); value = pixels all ranks segmented / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the f32 MFMA implicit-GEMM
-convolution; achieved = its algorithmic FLOPs / its HIP-event time inside the timed region)
-and `cpu_baseline` (the torch-CPU oneDNN restatement of the same net on the host cores,
-standing in for the reference's TF-CPU path -- see BASELINE.md section 3).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and reports the
+headline (value, ms_per_step) alone.  --full adds what takes measurements of its own: `roofline`
+(dominant kernel = the f32 MFMA implicit-GEMM convolution; achieved = its algorithmic FLOPs / its
+HIP-event time inside the timed region), `cpu_baseline` (the torch-CPU oneDNN restatement of the
+same net on the host cores, standing in for the reference's TF-CPU path -- see BASELINE.md
+section 3), `parity_o1`, the PCIe-inclusive `end_to_end` rate and the train_bf16 / gan_bf16 lines.
+--dump-outputs DIR writes what the last timed step computed (dump_infer_outputs).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -316,6 +320,23 @@ def iou_per_class(a, b, nclass=2):
         union = np.logical_or(pa, pb).sum()
         out.append(float(np.logical_and(pa, pb).sum()) / float(union) if union else 1.0)
     return out
+
+
+def dump_infer_outputs(out_dir, logits, mask, seed=0, tiles=4, pixels=1 << 20):
+    """--dump-outputs: what predict() handed its caller in the last timed launch -- the f32 logits (N, H, W, C) and the
+    uint8 mask (N, H, W) -- as float32 .npy files, 24 MiB for the 32-tile batch (the whole logits alone are 64 MiB):
+    every pixel of `tiles` seeded tiles (logits_tiles, mask_tiles) and `pixels` seeded pixels drawn from the whole batch
+    (logits_sample (pixels, C), mask_sample (pixels,)).  The inputs are seeded too, so two builds compare file by file."""
+    lg = logits.detach().float().cpu().numpy()
+    mk = mask.cpu().numpy()
+    rng = np.random.default_rng(seed)
+    pick = np.sort(rng.choice(lg.shape[0], min(tiles, lg.shape[0]), replace=False))
+    flat = np.sort(rng.integers(0, mk.size, pixels))
+    arrays = {"logits_tiles": lg[pick], "mask_tiles": mk[pick],
+              "logits_sample": lg.reshape(-1, lg.shape[-1])[flat], "mask_sample": mk.reshape(-1)[flat]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def end_to_end_rate(net, x_dev, iters=5, dist=None, world=1):
@@ -1312,7 +1333,14 @@ def main():
                          "config 4) is sharded over the ranks; weak (default for one GPU): every rank its own "
                          "config-sized batch (32 tiles; train: 16)")
     ap.add_argument("--global-tiles", type=int, default=0, help="global batch of the strong mode (default 256; train 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="infer mode: add the roofline, CPU baseline, O(1)-logit parity, PCIe-inclusive rate and the "
+                         "train_bf16 / gan_bf16 lines to the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="infer mode: write the logits and masks of the last timed step as float32 .npy files to DIR")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "infer":
+        ap.error("--dump-outputs is for --mode infer")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if args.mode not in ("infer", "train", "gan"):
             ap.error("--gpus > 1 is for --mode infer | train | gan")
@@ -1372,28 +1400,35 @@ def main():
         torch.cuda.synchronize()
 
     def step():
+        mask = None
         for c in chunks:
-            net.predict(c)
+            mask = net.predict(c)
+        return mask
 
     for _ in range(args.warmup):
         step()
     barrier()
-    with ConvTimer(ops, expected_groups=(8 * args.steps + 8) * len(chunks)) as ct:
+    # the conv-launch event timing behind `roofline` runs inside the timed region, so only --full pays for it
+    ct = ConvTimer(ops, expected_groups=(8 * args.steps + 8) * len(chunks)) if args.full else None
+    with ct or contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
-        ct.close()
+            mask = step()
+        if ct is not None:
+            ct.close()
         barrier()
         dt = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:                         # before anything else runs the net again
+        dump_infer_outputs(args.dump_outputs, net.logits(), mask)
 
     # PCIe-inclusive rate: EVERY rank streams at the same time (the collective inside is the harness's MAX of the times),
     # so all ranks must take the same branch -- a failure on any rank is agreed on before the line is built
     e2e = None
-    if not args.no_end_to_end and x_all.shape[0] > 0:
+    if args.full and not args.no_end_to_end and x_all.shape[0] > 0:
         try:
             e2e = end_to_end_rate(net, x, dist=dist, world=world)
         except Exception as e:                                  # noqa: BLE001
@@ -1402,8 +1437,6 @@ def main():
             e2e = {"value": None, "what": "failed: %r" % (e,)}
     if rank == 0:
         pix = float(total_tiles) * TILE * TILE * args.steps
-        conv_ms, conv_flops, nlaunch = ct.summary()
-        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
         out = {
             "metric": "segmented Mpixels/sec on 512x512 tiles; IoU vs reference",
             "value": round(pix / dt / 1e6, 3),
@@ -1427,7 +1460,11 @@ def main():
                        "tiles_per_step": int(total_tiles), "tiles_this_rank": int(x_all.shape[0]),
                        "parity": "logits and masks bit-exact vs oracle/sq_oracle.c (tests/test_gpu_unet.py); the oracle is parity "
                                  "UNPINNED against the reference (its U-Net leaf ops are abstract, unet.py:326-343)"},
-            "roofline": {
+        }
+        if args.full:
+            conv_ms, conv_flops, nlaunch = ct.summary()
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            out["roofline"] = {
                 "bound": "mfma",
                 "kernel": "the 3x3 implicit-GEMM family on v_mfma_f32_16x16x4_f32, all 17 launches of a step: "
                           "conv_mfma_f32_v2_kernel (levels 1-4) and conv_l0_kernel (the 16-channel level-0 launches: first block + "
@@ -1449,10 +1486,9 @@ def main():
                 "launches_per_step": nlaunch // max(1, args.steps),
                 "kernel_ms_per_step": round(conv_ms / max(1, args.steps), 4),
                 "flops_per_step": conv_flops / max(1, args.steps),
-            },
-        }
+            }
         # the two side measurements must never cost the driver its line: a failure is reported in place
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(weights, params, gpu_net=net)
             except Exception as e:                              # noqa: BLE001
@@ -1464,7 +1500,7 @@ def main():
                 out["parity_o1"] = {"failed": repr(e)}
         if e2e is not None:
             out["end_to_end"] = e2e
-        if world == 1 and not args.no_side_lines:
+        if args.full and world == 1 and not args.no_side_lines:
             # BASELINE configs[2] and [4] in the driver's ONE command: the bf16 training step and
             # the bf16 GAN iteration, 20 timed steps each after capture, each with its own roofline + cpu_baseline.
             # Same guard as above: a side measurement never costs the headline.

@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 def test_flags_and_work_figures_cpu():
     import bench
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, text=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--dtype"):
+    for flag in ("--gpus", "--steps", "--warmup", "--mode", "--dtype", "--full", "--dump-outputs"):
         assert flag in out, flag
     # 19,285,409,792 FLOP per 512x512 tile for filters 16..256, 2 classes, eltwise bridge
     f, t = bench.FILTERS, bench.TILE
@@ -94,7 +94,7 @@ def test_gpus_2_launches_two_ranks_and_reports_strong_scaling():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SQ_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--global-tiles", "64"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                        "--global-tiles", "64", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -132,7 +132,7 @@ def test_gpus_2_training_line_times_the_allreduce_apart():
 
 @pytest.mark.gpu
 def test_default_line_has_every_contract_field():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -152,3 +152,34 @@ def test_default_line_has_every_contract_field():
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
     assert min(cb["iou_gpu_vs_cpu_per_class"]) >= 0.9999                     # oneDNN sums in another order: near-ties may flip
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_reproducible_outputs(tmp_path):
+    """a plain run times --steps steps and reports the headline alone (the rest is behind --full); --dump-outputs writes
+    the last timed step's logits and masks as float32 files under 64 MB, the same bits from one run to the next."""
+    dumps = []
+    for i, steps in enumerate((3, 2)):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", "1", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == steps and line["unit"] == "Mpixels/s" and line["dtype"] == "f32"
+        assert abs(line["value"] - 32 * 512 * 512 / (line["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * line["value"]
+        for k in ("roofline", "cpu_baseline", "parity_o1", "end_to_end", "train_bf16", "gan_bf16"):
+            assert k not in line, k
+        files = sorted(os.listdir(d))
+        assert files == ["logits_sample.npy", "logits_tiles.npy", "mask_sample.npy", "mask_tiles.npy"], files
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64e6
+        dumps.append({f: np.load(os.path.join(d, f)) for f in files})
+    a, b = dumps
+    for f, x in a.items():
+        assert x.dtype == np.float32 and np.array_equal(x.view(np.uint32), b[f].view(np.uint32)), f
+    lg, mk = a["logits_tiles.npy"], a["mask_tiles.npy"]
+    assert lg.shape == (4, 512, 512, 2) and np.array_equal(mk, (lg[..., 1] > lg[..., 0]).astype(np.float32))

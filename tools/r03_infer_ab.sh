@@ -8,7 +8,7 @@ echo "pytest rc=$rc"; tail -3 $O/pytest.log
 [ $rc -ne 0 ] && exit 1
 for v in "$@"; do
   name=$(echo "$v" | tr ' =' '__')
-  ( export $v; timeout -k 10 200 python bench.py --steps 60 --warmup 20 --no-cpu-baseline --no-end-to-end --no-side-lines > $O/bench_$name.json 2> $O/bench_$name.err ) ; echo "bench[$v] rc=$?"
+  ( export $v; timeout -k 10 200 python bench.py --full --steps 60 --warmup 20 --no-cpu-baseline --no-end-to-end --no-side-lines > $O/bench_$name.json 2> $O/bench_$name.err ) ; echo "bench[$v] rc=$?"
   python -c "
 import json; d=json.load(open('$O/bench_$name.json')); print('$v', d['ms_per_step'], d['value'], d['roofline']['frac'])"
 done

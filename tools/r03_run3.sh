@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 timeout -k 10 1100 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; rc=$?
 echo "pytest rc=$rc"; tail -5 $O/pytest.log
 [ $rc -ne 0 ] && exit 1
-( time timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err ) 2>&1 | tail -3; echo "bench rc=$?"; cut -c1-600 $O/bench.json
+( time timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2>&1 | tail -3; echo "bench rc=$?"; cut -c1-600 $O/bench.json
 python - <<PY
 import json
 d=json.load(open("$O/bench.json"))

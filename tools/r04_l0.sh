@@ -9,7 +9,7 @@ echo "pytest rc=$rc"; tail -5 $O/pytest.log
 echo "--- L0 kernel"; timeout -k 10 200 python tools/r03_op_bench.py level0 2>&1 | tee $O/op_l0.txt
 echo "--- generic kernel (SQ_CONV_L0=0)"; SQ_CONV_L0=0 timeout -k 10 200 python tools/r03_op_bench.py level0 2>&1 | tee $O/op_v2.txt
 for v in SQ_CONV_L0=1 SQ_CONV_L0=0; do
-  ( export $v; timeout -k 10 200 python bench.py --steps 60 --warmup 20 --no-cpu-baseline --no-end-to-end --no-side-lines > $O/bench_$v.json 2> $O/bench_$v.err ); echo "bench[$v] rc=$?"
+  ( export $v; timeout -k 10 200 python bench.py --full --steps 60 --warmup 20 --no-cpu-baseline --no-end-to-end --no-side-lines > $O/bench_$v.json 2> $O/bench_$v.err ); echo "bench[$v] rc=$?"
   python -c "
 import json; d=json.load(open('$O/bench_$v.json')); print('$v', d['ms_per_step'], d['value'], d['roofline']['frac'])"
 done
