@@ -681,6 +681,34 @@ int sq_conv2d_nhwc_dgrad_actgate_bf16(const void *dy, const void *wp_t, const vo
 int sq_conv2d_nhwc_mosaic_bf16(const void *x, const void *wp, const float *bias, const void *gate, void *y, int Nimg, int h,
                                int w, int Cin, int Cout, int act, int R, int Cc, float *workspace, int64_t workspace_bytes,
                                void *stream);
+/* Launch plan of the implicit-GEMM convolutions, computed on the host without a HIP call (the choices the launchers make,
+ * from the same functions, under the same environment switches SQ_CONV_BF16_NARROW, SQ_CONV_STAGE32, SQ_CONV_L0, ...).
+ * family: SQ_PLAN_BF16 (bf16 tensors: sq_conv2d_nhwc_fwd_bf16 and its fused forms, sq_conv2d_nhwc_mosaic_bf16),
+ *         SQ_PLAN_MIXED (f32 tensors, bf16 operands: sq_conv2d_nhwc_fwd_mixed_f32, ..._dgrad_actgate_mixed_f32, ..._mixed_mosaic_f32),
+ *         SQ_PLAN_F32 (the f32 v2 / level-0 kernels behind sq_conv2d_nhwc_fwd_f32, sq_conv2d_concat_nhwc_fwd_f32 with
+ *         Cin = both sources' channels, sq_conv3x3_pool_fwd_f32).
+ * form: SQ_PLAN_PLAIN (also the relu / dropout gates of the plain kernel), _JUNCTION, _POOL (max or average pooled copy;
+ *         f32: sq_conv3x3_pool_fwd_f32), _MASK, _MASKGATE, _ACTGATE, _FIRSTBLOCK, _PIXELNORM, _CONCAT (f32).
+ * act: SQ_ACT_* of the call (the level-0 kernel takes ReLU only); flags: SQ_PLAN_WSCALE when an f32 call has wscale != 1.
+ * mosaic: NULL, or {R, Cc} of a mosaic call, whose (N, H, W) are then (Nimg, h, w); workspace_bytes: its split-K room (0: none).
+ * out[5] = {BN channel-block width, KC input channels per chunk, gy channel blocks, S split-K slices, 1 if the f32 level-0
+ * kernel takes the call (BN, KC, gy then describe that kernel: Cout, 16, 1)}.  Returns SQ_OK, or SQ_EINVAL where no kernel of
+ * the family takes the call. */
+#define SQ_PLAN_BF16 0
+#define SQ_PLAN_MIXED 1
+#define SQ_PLAN_F32 2
+#define SQ_PLAN_PLAIN 0
+#define SQ_PLAN_JUNCTION 1
+#define SQ_PLAN_POOL 2
+#define SQ_PLAN_MASK 3
+#define SQ_PLAN_MASKGATE 4
+#define SQ_PLAN_ACTGATE 5
+#define SQ_PLAN_FIRSTBLOCK 8
+#define SQ_PLAN_PIXELNORM 9
+#define SQ_PLAN_CONCAT 10
+#define SQ_PLAN_WSCALE 1
+int sq_conv_plan(int family, int form, int N, int H, int W, int Cin, int Cout, int K, int act, int flags, const int *mosaic,
+                 int64_t workspace_bytes, int *out);
 int sq_conv2d_nhwc_wgrad_scaled_bf16(const void *x, const void *dy, float *dw, float *db, float *workspace, int N, int H,
                                      int W, int Cin, int Cout, int K, float dw_scale, void *stream);
 int sq_conv2d_nhwc_wgrad_mosaic_bf16(const void *x, const void *dy, float *dw, float *db, float *workspace, int Nimg, int h,

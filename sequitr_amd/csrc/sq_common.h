@@ -19,6 +19,14 @@ void sq_set_error(const char *fmt, ...);
         }                                \
     } while (0)
 
+// launch-plan rules shared by the convolution launchers and sq_conv_plan (sq_conv_plan.hip; host only, no HIP call)
+int sq_plan_bf16_kc(int Cin);
+int sq_plan_bf16_bn(int64_t ntiles, int Cout, bool pn, bool mos);
+int sq_plan_mosaic_splitk(int Nimg, int h, int w, int Cin, int Cout, int R, int Cc, bool have_ws, int64_t workspace_bytes);
+int sq_plan_f32_bn(int64_t ntiles, int Cout);
+bool sq_plan_f32_stage32(int bn, int KS, int KC, int Cin, bool concat);
+bool sq_plan_l0_takes(int mode, int cout, int act, int H, int W, bool concat, int head_c, bool pooled);
+
 #define SQ_ALIGNED16(p) ((((uintptr_t)(p)) & 15u) == 0)
 
 #define SQ_REQUIRE_ALIGNED(p)                                     \

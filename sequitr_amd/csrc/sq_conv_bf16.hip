@@ -959,6 +959,8 @@ int launch(const TIO *x, const __bf16 *wp, const float *bias, TIO *y, int N, int
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     const int ntiles = tiles_x * tiles_y * N;
     const int gy = (Cout + BN - 1) / BN;
+    // FORM_PN normalises over the channels of ONE block: a launch that split them would scale each part by its own sum
+    if constexpr (FORM == FORM_PN) SQ_REQUIRE(gy == 1, "sq_conv2d_nhwc_fwd_pixelnorm_bf16: Cout=%d spans %d channel blocks of %d", Cout, gy, BN);
     // persistent grid: every block slot the CU can hold (these kernels are latency / HBM bound at C <= 32:
     // the tiles in flight, not the MFMA rate, set their speed)
     int want = (256 * occ + gy - 1) / gy;
@@ -976,20 +978,16 @@ int launch(const TIO *x, const __bf16 *wp, const float *bias, TIO *y, int N, int
 template <int KS, int KC, typename TIO>
 int dispatch_bn(const TIO *x, const __bf16 *wp, const float *bias, TIO *y, int N, int H, int W, int Cin,
                 int Cout, int act, hipStream_t st, const __bf16 *gate, const SqDropEpi &drop) {
-    // narrow the channel block until the launch has ~2 blocks per CU (as sq_conv_f32_v2.hip): the GAN's 4x4 .. 32x32
-    // levels are a handful of mosaic tiles x 512 .. 64 channels, and 64-channel blocks leave most of the chip idle
+    // the channel-block width (sq_plan_bf16_bn, shared with sq_conv_plan): narrowed until the launch has ~2 blocks per CU;
+    // FORM_PN keeps every channel of a pixel in one block
     const int64_t ntiles = (int64_t)((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
-    int bn = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16);
-    static const int narrow = [] { const char *e = getenv("SQ_CONV_BF16_NARROW"); return e ? atoi(e) : 1; }();
-    while (narrow && bn > 16 && !drop.pn_y && ntiles * ((Cout + bn - 1) / bn) < 2 * 256) bn >>= 1;   // (FORM_PN: one block per pixel's channels)
-    static const int force_bn = [] { const char *e = getenv("SQ_MOS_BN"); return e ? atoi(e) : 0; }();   // experiment switch: block width of the mosaic launches
-    if (drop.mos_h && !drop.pn_y && (force_bn == 16 || force_bn == 32 || force_bn == 64) && force_bn <= ((Cout + 15) / 16) * 16) bn = force_bn;
+    const int bn = sq_plan_bf16_bn(ntiles, Cout, drop.pn_y != nullptr, drop.mos_h != 0);
     if (bn == 64) return launch<64, KS, KC, TIO>(x, wp, bias, y, N, H, W, Cin, Cout, act, st, gate, drop);
     if (bn == 32) return launch<32, KS, KC, TIO>(x, wp, bias, y, N, H, W, Cin, Cout, act, st, gate, drop);
     return launch<16, KS, KC, TIO>(x, wp, bias, y, N, H, W, Cin, Cout, act, st, gate, drop);
 }
 
-inline int kc_for(int Cin) { return Cin % 32 == 0 ? 32 : (Cin % 16 == 0 ? 16 : 8); }
+inline int kc_for(int Cin) { return sq_plan_bf16_kc(Cin); }
 
 // split-K finish: y[p][c] = bf16(act(sum_s ws[s][p][c] + bias[c])), slices added in order; gate != NULL: the result is the gated
 // dgrad instead (no bias / act): t = bf16(sum), y = gate > 0 ? t : bf16(t * slope) -- FORM_GB's two roundings
@@ -1225,16 +1223,10 @@ extern "C" int sq_conv2d_nhwc_mosaic_bf16(const void *x, const void *wp, const f
         d.gate_slope = 1;
         d.gscale = act == SQ_ACT_LEAKY ? 0.2f : 0.0f;
     }
-    // split-K: blocks the unsplit launch would have (16-channel blocks once narrowed) vs the chip
+    // split-K (sq_plan_mosaic_splitk, shared with sq_conv_plan): where the unsplit launch would leave most of the chip idle
     const int nchunk = Cin / kc_for(Cin);
-    const int64_t blocks = (int64_t)((H + TH - 1) / TH) * ((W + TW - 1) / TW) * ((Cout + 15) / 16);
     const int64_t slice = (int64_t)Nimg * h * w * Cout * 4;
-    int S = 1;
-    static const int sk_on = [] { const char *e = getenv("SQ_CONV_SPLITK"); return e ? atoi(e) : 1; }();
-    if (sk_on && workspace && Cout % 4 == 0 && blocks < 256 && nchunk >= 4)
-        while (S < 8 && nchunk % (2 * S) == 0 && nchunk / (2 * S) >= 2 && blocks * S < 512 && slice * 2 * S <= workspace_bytes) S *= 2;
-    static const int force_s = [] { const char *e = getenv("SQ_MOS_S"); return e ? atoi(e) : 0; }();   // experiment switch (tools/r04_mosaic_sweep.py)
-    if (force_s >= 1 && workspace && nchunk % force_s == 0 && slice * force_s <= workspace_bytes) S = force_s;
+    const int S = sq_plan_mosaic_splitk(Nimg, h, w, Cin, Cout, R, Cc, workspace != nullptr, workspace_bytes);
     if (S == 1)
         return conv_fwd_bf16_impl(x, wp, gate ? nullptr : bias, y, 1, H, W, Cin, Cout, 3, gate ? (int)SQ_ACT_NONE : act, stream, gate, d);
     SQ_REQUIRE_ALIGNED(workspace);

@@ -588,11 +588,6 @@ __global__ __launch_bounds__(256, (MODE == M_UP ? SQ_L0_UP_OCC : (NB == 2 ? 2 : 
     }
 }
 
-inline bool l0_enabled() {                                          // SQ_CONV_L0=0: A/B switch back to the generic kernel
-    const char *e = getenv("SQ_CONV_L0");                           // read per launch: the parity tests flip it in-process
-    return !(e && e[0] == '0');
-}
-
 template <int MODE, int EPI, int BRIDGE = 0, int NB = 1>
 int launch_l0(const L0Args &a0, hipStream_t st) {
     static bool attr_set = false;
@@ -623,10 +618,10 @@ int launch_l0(const L0Args &a0, hipStream_t st) {
 
 int sq_conv_l0_launch(int mode, const float *x, const float *w, const float *bias, float *y, int N, int H, int W,
                       int cout, int act, const SqConvEpi &epi, hipStream_t st) {
-    if (cout != 16 && !(cout == 32 && mode == M_PLAIN && !epi.head_w && !epi.pooled)) return SQ_L0_NOT_MINE;
-    if (!l0_enabled() || act != SQ_ACT_RELU || H % 16 != 0 || W % 16 != 0 || epi.x2) return SQ_L0_NOT_MINE;
-    if (epi.head_w && epi.head_c != 2) return SQ_L0_NOT_MINE;
-    if (epi.head_w && epi.pooled) return SQ_L0_NOT_MINE;
+    // which shapes are its own: sq_plan_l0_takes, shared with sq_conv_plan
+    if (!sq_plan_l0_takes(mode, cout, act, H, W, epi.x2 != nullptr, epi.head_w ? epi.head_c : 0,
+                          epi.pooled != nullptr))
+        return SQ_L0_NOT_MINE;
     L0Args a = {};
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.N = N; a.H = H; a.W = W; a.epi = epi;
     const int e = epi.head_w ? EPI_HEAD : (epi.pooled ? EPI_POOL : EPI_STORE);

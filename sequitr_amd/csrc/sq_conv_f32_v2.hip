@@ -714,24 +714,15 @@ int launch_v2(const float *x, const float *w, const float *bias, float *y, int N
     return sq_check_launch("sq_conv2d_nhwc_fwd_f32(v2)");
 }
 
-inline bool stage32() {                                         // SQ_CONV_STAGE32=0: A/B switch back to 16-channel items
-    static const bool v = [] { const char *e = getenv("SQ_CONV_STAGE32"); return !(e && e[0] == '0'); }();
-    return v;
-}
-
 template <int KS, int KC>
 int dispatch_bn(const float *x, const float *w, const float *bias, float *y, int N, int H, int W, int Cin,
                 int Cout, float wscale, int act, const SqConvEpi &epi, hipStream_t st) {
-    // widest channel block the layer fills the chip with: small images (GAN 4x4..32x32 levels, small
-    // batches) have few pixel tiles, so trade operand reuse for blocks until there are ~2 per CU.
-    // BN only changes which block computes an output, never its fmaf chain.
+    // the widest channel block the layer fills the chip with (sq_plan_f32_bn, shared with sq_conv_plan)
     const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
-    int bn = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16);
-    // (32-channel blocks for the wide layers, three blocks per CU: 5.189 vs 5.107 ms per step -- 64 it stays)
-    while (bn > 16 && (int64_t)ntiles * ((Cout + bn - 1) / bn) < 2 * 256) bn >>= 1;
+    const int bn = sq_plan_f32_bn(ntiles, Cout);
     // 32 -> 32 (and wider-input) 3x3 layers on 32-channel blocks: stage 32 input channels per item (same chain)
     if constexpr (KS == 3 && KC == 16) {
-        if (bn == 32 && Cin % 32 == 0 && !epi.x2 && stage32())
+        if (sq_plan_f32_stage32(bn, KS, KC, Cin, epi.x2 != nullptr))
             return launch_v2<32, 3, 32, false>(x, w, bias, y, N, H, W, Cin, Cout, wscale, act, epi, st);
     }
     if (bn == 64) return launch_v2<64, KS, KC, false>(x, w, bias, y, N, H, W, Cin, Cout, wscale, act, epi, st);

@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as TF
 
 from sequitr_amd import ops_bf16 as ob
-from tests.util import tiles, rand_weights
+from tests.util import tiles, rand_weights, bf16_round, check_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -15,21 +15,6 @@ pytestmark = pytest.mark.gpu
 def dev(a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
     return t.to(dtype) if dtype is not None else t
-
-
-def bf16_round(a):
-    return torch.as_tensor(a, dtype=torch.float32).to(torch.bfloat16).to(torch.float64)
-
-
-def check_bf16(got, ref64, what):
-    """got: bf16 tensor; ref64: fp64 reference before the final rounding."""
-    g = got.float().cpu().double()
-    r = ref64.to(torch.bfloat16).double()
-    ulp = torch.clamp(r.abs(), min=1e-30) * 2.0 ** -7
-    bad = (g - ref64).abs() > ulp + 1e-6
-    assert not bad.any(), "%s: %d values off by more than one bf16 ulp" % (what, int(bad.sum()))
-    same = (g == r).double().mean().item()
-    assert same > 0.97, "%s: only %.4f bit-identical" % (what, same)
 
 
 CASES = [(2, 32, 48, 16, 16, 3, "relu"), (1, 32, 32, 16, 32, 3, "relu"), (1, 32, 32, 32, 32, 3, "relu"),

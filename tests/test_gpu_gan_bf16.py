@@ -187,7 +187,8 @@ def test_weighted_conv_bf16_forward_dgrad_gate_and_wgrad(N, H, W, Cin, Cout, K, 
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [(2, 32, 32, 128, 64), (3, 64, 48, 64, 32), (2, 128, 128, 32, 16), (1, 256, 256, 16, 8),
-                                             (2, 16, 16, 8, 8), (1, 40, 24, 16, 24)])
+                                             (2, 16, 16, 8, 8), (1, 40, 24, 16, 24), (2, 32, 32, 64, 40), (1, 48, 40, 32, 48),
+                                             (2, 24, 20, 16, 56)])
 def test_pixel_norm_in_the_conv_epilogue(N, H, W, Cin, Cout):
     """sq_conv2d_nhwc_fwd_pixelnorm_bf16 (SURVEY 8b "pixelnorm epilogue flag"; gan.py:86-97 is conv -> bias -> activation ->
     pixel_norm as ONE op): y is the plain conv's y bit for bit, ynorm is the stand-alone pixel norm of that y up to the f32
@@ -231,6 +232,39 @@ def test_pixel_norm_in_the_conv_epilogue(N, H, W, Cin, Cout):
     finally:
         ops.pixelnorm = orig
     assert torch.equal(gx, hx) and torch.equal(gw, hw) and torch.equal(gb_, hb)     # the backward reads y only
+
+
+@pytest.mark.parametrize("filters", [[48, 48, 48], [64, 48, 56, 40]])
+def test_generator_with_pixel_norm_widths_between_block_widths(filters, monkeypatch):
+    """generator_network under bf16 storage with filter counts (40 / 48 / 56) whose pixel norm spans more than 32 channels: the
+    levels of side >= 16 run conv + pixel norm as one kernel (ops_gan_bf16.USE_CONV_PN), and that kernel must keep every channel
+    of a pixel in one block.  Fused and unfused graphs give the same image and parameter gradients up to the one-ulp difference
+    of the fused norm (its squares are added in another order)."""
+    from sequitr_amd.networks import scope
+    fused_calls = []
+    orig = gb.conv2d_pixelnorm
+    monkeypatch.setattr(gb, "conv2d_pixelnorm", lambda *a, **k: (fused_calls.append(1), orig(*a, **k))[1])
+
+    def run(fused):
+        monkeypatch.setattr(gb, "USE_CONV_PN", fused)
+        with scope.VariableStore("cuda", seed=7) as st, ops.mixed_precision(True, store_bf16=True):
+            z = torch.as_tensor(np.random.default_rng(1).standard_normal((3, 32)), dtype=torch.float32).cuda()
+            _, img = gan.generator_network(z, list(filters))
+            g = torch.as_tensor(np.random.default_rng(2).standard_normal(tuple(img.shape)), dtype=torch.float32).cuda()
+            names = list(st.vars)
+            grads = torch.autograd.grad(img, [st.vars[k] for k in names], g.to(img.dtype), allow_unused=True)
+        return img.detach().float(), {k: v for k, v in zip(names, grads) if v is not None}   # (the unread levels' to_image)
+
+    img0, g0 = run(False)
+    assert not fused_calls
+    img1, g1 = run(True)
+    assert len(fused_calls) == 2 * (len(filters) - 2), "the levels of side >= 16 did not take the fused form"
+    scale = img0.abs().max().item()
+    assert (img1 - img0).abs().max().item() <= 2.0 ** -7 * scale, "generator image, fused vs unfused pixel norm"
+    assert set(g0) == set(g1)
+    for k in g0:
+        e = _rel(g1[k].cpu(), g0[k].cpu())
+        assert e <= GRAD_BOUND, "gradient of %s, fused vs unfused pixel norm: %.3g" % (k, e)
 
 
 def test_minibatch_stdev_on_bf16_features_equals_the_f32_kernels_round_the_casts():
