@@ -737,6 +737,40 @@ typedef struct sq_wgrad_item {
 int64_t sq_conv2d_nhwc_wgrad_group_workspace_bf16(const sq_wgrad_item *items, int n);
 int sq_conv2d_nhwc_wgrad_group_bf16(const sq_wgrad_item *items, int n, float *workspace, void *stream);
 
+/* Launch plan of the weight gradients, computed on the host without a HIP call (the choices the launchers and the workspace
+ * queries make, from the same functions, under the same environment switches SQ_WGRAD_BF16_NARROW, _MAX, _K3,
+ * SQ_WGRAD_INTERLEAVE, SQ_WGRAD_GROUP_SHRINK, SQ_WGRAD_PAIR_MAJOR).
+ * sq_wgrad_plan: family SQ_PLAN_BF16 (sq_conv2d_nhwc_wgrad_bf16 and its scaled / mosaic / transpose-conv forms), SQ_PLAN_MIXED
+ * (sq_conv2d_nhwc_wgrad_mixed_f32 and its forms), SQ_PLAN_F32 (sq_conv2d_nhwc_wgrad_f32; Cin 1..7: the small-Cin kernel, also
+ * that of sq_conv3x3_first_wgrad_bf16).  mosaic: NULL or {R, Cc}, (N, H, W) then (Nimg, h, w); convT_cout > 0: the 1x1 form of
+ * sq_convT2x2s2_wgrad_bf16 with Cout = 4 * convT_cout.  out[SQ_WGP_N]:
+ *   KS; NI, NO (16-channel planes of Cin / Cout per block; f32: KC input channels, BN output channels); kind (SQ_WGP_*);
+ *   PF prefetch depth (tiles in flight; f32: 1); npairs channel-block pairs; gx tile ranges; tpb tiles per block (< 0: block bx
+ *   takes tiles bx, bx + gx, ...); G block groups of the finish; workspace floats.
+ * sq_wgrad_group_plan: out[SQ_WGP_GROUP_N] per item: the launch ("bucket") it runs in, its plan as above after the group's shrink
+ * (workspace: the floats it writes), 1 if the pair-major block mapping applies, and its partials' offset in the workspace
+ * (floats).  Returns the number of buckets, or SQ_EINVAL. */
+#define SQ_WGP_KS 0
+#define SQ_WGP_NI 1
+#define SQ_WGP_NO 2
+#define SQ_WGP_KIND 3
+#define SQ_WGP_PF 4
+#define SQ_WGP_NPAIRS 5
+#define SQ_WGP_GX 6
+#define SQ_WGP_TPB 7
+#define SQ_WGP_G 8
+#define SQ_WGP_WS 9
+#define SQ_WGP_N 10
+#define SQ_WGP_GROUP_N (SQ_WGP_N + 3)
+#define SQ_WGP_PLAIN 0
+#define SQ_WGP_MOSAIC 1
+#define SQ_WGP_RAGGED 2
+#define SQ_WGP_CONVT 3
+#define SQ_WGP_F32 4
+#define SQ_WGP_F32_SMALL 5
+int sq_wgrad_plan(int family, int N, int H, int W, int Cin, int Cout, int K, const int *mosaic, int convT_cout, int64_t *out);
+int sq_wgrad_group_plan(const sq_wgrad_item *items, int n, int64_t *out);
+
 /* ------------------------------------------------------------------------------------------
  * Tile front end: raw single-channel camera frames in HBM (OctopusData .dat memmap,
  * sequitr/dataio/octopus.py:231-245) -> ImageNorm (sequitr/pipeline.py:350-356) -> network tiles, and the

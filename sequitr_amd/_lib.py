@@ -181,6 +181,8 @@ SIGNATURES = {
     "sq_conv2d_nhwc_wgrad_mosaic_bf16": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_float, c_void_p]),
     "sq_conv2d_nhwc_wgrad_group_workspace_bf16": (c_int64, [c_void_p, c_int]),
     "sq_conv2d_nhwc_wgrad_group_bf16": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "sq_wgrad_plan": (c_int, [c_int] * 7 + [c_void_p, c_int, c_void_p]),
+    "sq_wgrad_group_plan": (c_int, [c_void_p, c_int, c_void_p]),
     "sq_act_bwd_bf16": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
     "sq_bridge_fwd_bf16": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
     "sq_bridge_bwd_bf16": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_void_p]),

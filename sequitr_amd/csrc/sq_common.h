@@ -26,6 +26,8 @@ int sq_plan_mosaic_splitk(int Nimg, int h, int w, int Cin, int Cout, int R, int 
 int sq_plan_f32_bn(int64_t ntiles, int Cout);
 bool sq_plan_f32_stage32(int bn, int KS, int KC, int Cin, bool concat);
 bool sq_plan_l0_takes(int mode, int cout, int act, int H, int W, bool concat, int head_c, bool pooled);
+// the plan of sq_conv2d_nhwc_wgrad_f32 (sq_conv_wgrad_f32.hip) as sq_wgrad_plan reports it; SQ_EINVAL: no kernel takes the shape
+int sq_wgrad_f32_plan(int N, int H, int W, int Cin, int Cout, int K, int64_t *out);
 
 #define SQ_ALIGNED16(p) ((((uintptr_t)(p)) & 15u) == 0)
 

@@ -74,10 +74,22 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char *p0, const unsigne
 #ifndef SQ_WGRAD_OCC4_16x16
 #define SQ_WGRAD_OCC4_16x16 0       // ... and the 3x3 16 x 16-channel shape for FOUR (128 VGPRs; the 1x1 32 x 64 shape spills there)
 #endif
-template <int KS, int NI, int NO>
-constexpr int wgrad_occ() {
-    constexpr int blocks = KS * KS * NI * NO;
+constexpr int wg_occ(int KS, int NI, int NO) {
+    const int blocks = KS * KS * NI * NO;
     return blocks > SQ_WGRAD_OCC1_ABOVE ? 1 : ((SQ_WGRAD_OCC4_16x16 && KS == 3 && NI * NO == 1) ? 4 : (blocks <= SQ_WGRAD_OCC3_UPTO ? 3 : 2));
+}
+template <int KS, int NI, int NO>
+constexpr int wgrad_occ() { return wg_occ(KS, NI, NO); }
+
+// prefetch depth PF of a shape: as deep as the accumulators leave registers for (es = 4, f32 tensors: twice the registers per
+// set).  The ragged one-layer launch keeps a depth of its own; the grouped ragged launch uses the rule.
+constexpr int wg_pf(int KS, int NI, int NO, int es, bool rag_single) {
+    if (rag_single) return es == 4 ? 2 : 4;
+    const int hp = (TW + KS - 1) * (TH + KS - 1), xslots = (hp * 2 * NI + 255) / 256, yslots = TH * TW * 2 * NO / 256;
+    const int occ = wg_occ(KS, NI, NO);
+    const int acc_regs = KS * KS * NI * NO * 4, set_regs = (xslots + yslots) * 4 * (es / 2);
+    const int budget = (occ == 1 ? 300 : (occ == 4 ? 100 : (occ == 3 ? 140 : SQ_WGRAD_BUDGET2))) - acc_regs - 40;
+    return budget / set_regs >= 4 ? 4 : (budget / set_regs >= 3 ? 3 : (budget / set_regs >= 2 ? 2 : 1));
 }
 
 __device__ __forceinline__ uint4 f32x8_to_bf16x8(const uint4 &a, const uint4 &b) {
@@ -345,7 +357,9 @@ __global__ __launch_bounds__(256, (wgrad_occ<KS, NI, NO>())) void conv_wgrad_bf1
 // ~10 us of matrix work -- ramp-up (the first tiles' round trips) and the cross-wave reduction at the end run with the chip
 // otherwise idle.  Queued behind each other in one grid, one layer's ramp and tail overlap the next layer's tiles.  Every
 // block finds its layer by its index (blocks of layer e: first[e] .. first[e+1]-1, pair-major) and runs the body above with
-// that layer's arguments: same partials, same finish order, same bits as the one-layer launches.
+// that layer's arguments and the same fixed-order finish.  Cut into the shrunk tile runs of the group plan, each block sums a
+// different run of tiles than in the one-layer launch: a layer's result equals the one-layer launch's to f32 rounding, and is
+// run-to-run identical.
 constexpr int GROUP_MAX = 16;
 struct SqWgradGroup {
     int n, pair_major;
@@ -492,124 +506,6 @@ inline bool wgrad_interleave() {                                // SQ_WGRAD_INTE
     return v;
 }
 
-template <int KS, int NI, int NO>
-void plan(int N, int H, int W, int Cin, int Cout, int *gx, int *tpb, int64_t *ws_floats) {
-    using C = WB<KS, NI, NO>;
-    const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
-    const int npairs = ((Cin + C::CI - 1) / C::CI) * ((Cout + C::CO - 1) / C::CO);
-    // (512: targets that leave a layer with a number of tile ranges that is not a multiple of 8 -- 384, 768 -- put the channel-block
-    // pairs of one range on different XCDs, their shared operands are then fetched once per pair: 2.81 -> 3.2 ms per training step)
-    int want = (512 + npairs - 1) / npairs;
-    if (want < 1) want = 1;
-    int t = (ntiles + want - 1) / want;
-    if (t < 1) t = 1;
-    *tpb = t;
-    *gx = (ntiles + t - 1) / t;
-    *ws_floats = (int64_t)(*gx) * npairs * C::RED_FLOATS;
-}
-
-template <int KS, int NI, int NO>
-int finish(float *ws, float *dw, float *db, int gx, int Cin, int Cout, hipStream_t st) {
-    using C = WB<KS, NI, NO>;
-    const int npairs = ((Cin + C::CI - 1) / C::CI) * ((Cout + C::CO - 1) / C::CO);
-    int G = sq_group_size(gx);
-    if (G > 16) G = 16;                                         // >= 16 consecutive floats (64 B) per load of a group
-    const int64_t total = (int64_t)npairs * C::RED_FLOATS;
-    const int OUT = 256 / G;
-    hipLaunchKernelGGL((conv_wgrad_bf16_finish_kernel<KS, NI, NO>), dim3((unsigned)((total + OUT - 1) / OUT)), dim3(256), 0, st,
-                       ws, dw, db, gx, Cin, Cout, G, t_dw_scale, KS == 1 ? t_convT_cout : 0);
-    return sq_check_launch("sq_conv2d_nhwc_wgrad_bf16(finish)");
-}
-
-// the mosaic form (f32 tensors, 3x3): same plan, same finish; X / dY are the compact small-image tensors
-template <int KS, int NI, int NO, int PF, typename TIO>
-int launch_mos(const TIO *x, const TIO *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin, int Cout,
-               hipStream_t st) {
-    using C = WB<KS, NI, NO>;
-    static bool attr_set = false;
-    auto kern = conv_wgrad_bf16_kernel<KS, NI, NO, PF, TIO, true>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS_BYTES) != hipSuccess) {
-            sq_set_error("conv_wgrad_bf16: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-            return SQ_ELAUNCH;
-        }
-        attr_set = true;
-    }
-    int gx, tpb;
-    int64_t wsf;
-    plan<KS, NI, NO>(N, H, W, Cin, Cout, &gx, &tpb, &wsf);
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int npairs = (Cin / C::CI) * (Cout / C::CO);
-    hipLaunchKernelGGL(kern, dim3(gx, npairs), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout, tiles_x, tiles_y,
-                       tiles_x * tiles_y * N, wgrad_interleave() ? -tpb : tpb, t_mos);
-    int rc = sq_check_launch("sq_conv2d_nhwc_wgrad_mixed_mosaic_f32");
-    if (rc) return rc;
-    return finish<KS, NI, NO>(ws, dw, db, gx, Cin, Cout, st);
-}
-
-template <int KS, int NI, int NO, typename TIO>
-int launch(const TIO *x, const TIO *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin,
-           int Cout, hipStream_t st) {
-    using C = WB<KS, NI, NO>;
-    static bool attr_set = false;
-    // prefetch depth: as deep as the accumulators leave registers for (f32 tensors: twice the registers per set)
-    constexpr int acc_regs = C::NTAP * NI * NO * 4, set_regs = (C::XSLOTS + C::YSLOTS) * 4 * (int)(sizeof(TIO) / 2);
-    constexpr int budget = (wgrad_occ<KS, NI, NO>() == 1 ? 300 : (wgrad_occ<KS, NI, NO>() == 4 ? 100 : (wgrad_occ<KS, NI, NO>() == 3 ? 140 : SQ_WGRAD_BUDGET2))) - acc_regs - 40;
-    constexpr int PF = budget / set_regs >= 4 ? 4 : (budget / set_regs >= 3 ? 3 : (budget / set_regs >= 2 ? 2 : 1));
-    if constexpr (KS == 3) {
-        if (t_mos.h) return launch_mos<KS, NI, NO, PF, TIO>(x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
-    }
-    auto kern = conv_wgrad_bf16_kernel<KS, NI, NO, PF, TIO>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS_BYTES) != hipSuccess) {
-            sq_set_error("conv_wgrad_bf16: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-            return SQ_ELAUNCH;
-        }
-        attr_set = true;
-    }
-    int gx, tpb;
-    int64_t wsf;
-    plan<KS, NI, NO>(N, H, W, Cin, Cout, &gx, &tpb, &wsf);
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int npairs = (Cin / C::CI) * (Cout / C::CO);
-    hipLaunchKernelGGL(kern, dim3(gx, npairs), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout, tiles_x,
-                       tiles_y, tiles_x * tiles_y * N, wgrad_interleave() ? -tpb : tpb, SqMos{});
-    int rc = sq_check_launch("sq_conv2d_nhwc_wgrad_bf16");
-    if (rc) return rc;
-    return finish<KS, NI, NO>(ws, dw, db, gx, Cin, Cout, st);
-}
-
-
-// ragged channel counts (Cin or Cout = 8 mod 16): 16 x 16 channel blocks, the half-empty plane masked in the loader
-template <int KS, typename TIO>
-int launch_rag(const TIO *x, const TIO *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin, int Cout,
-               hipStream_t st) {
-    using C = WB<KS, 1, 1>;
-    static bool attr_set = false;
-    constexpr int PF = sizeof(TIO) == 4 ? 2 : 4;
-    auto kern = conv_wgrad_bf16_kernel<KS, 1, 1, PF, TIO, false, true>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS_BYTES) != hipSuccess) {
-            sq_set_error("conv_wgrad_bf16: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-            return SQ_ELAUNCH;
-        }
-        attr_set = true;
-    }
-    int gx, tpb;
-    int64_t wsf;
-    plan<KS, 1, 1>(N, H, W, Cin, Cout, &gx, &tpb, &wsf);
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int npairs = ((Cin + 15) / 16) * ((Cout + 15) / 16);
-    hipLaunchKernelGGL(kern, dim3(gx, npairs), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout, tiles_x, tiles_y,
-                       tiles_x * tiles_y * N, wgrad_interleave() ? -tpb : tpb, SqMos{});
-    int rc = sq_check_launch("sq_conv2d_nhwc_wgrad_bf16(ragged)");
-    if (rc) return rc;
-    return finish<KS, 1, 1>(ws, dw, db, gx, Cin, Cout, st);
-}
-
 // SQ_WGRAD_BF16_NARROW=1: 16 x 16 channel blocks everywhere (A/B switch for the wider blocks);
 // SQ_WGRAD_BF16_MAX="ni,no": upper bound on the block shape (tuning experiments)
 inline bool narrow_blocks() {
@@ -636,98 +532,31 @@ inline int k3_shape() {
     return v;
 }
 
+// ---- launch plan, host only: the launchers, the workspace queries and sq_wgrad_plan / sq_wgrad_group_plan all take it from here
+enum { WG_PLAIN = SQ_WGP_PLAIN, WG_MOSAIC = SQ_WGP_MOSAIC, WG_RAGGED = SQ_WGP_RAGGED, WG_CONVT = SQ_WGP_CONVT };
+
+// every <KS, NI, NO> instantiated (one kernel each for bf16 and f32 tensors, plain and mosaic)
+#define SQ_WG_SHAPES3(X) X(3, 1, 4) X(3, 2, 2) X(3, 1, 2) X(3, 2, 1) X(3, 1, 1)
+#define SQ_WG_SHAPES(X) SQ_WG_SHAPES3(X) X(1, 2, 4) X(1, 2, 2) X(1, 2, 1) X(1, 1, 2) X(1, 1, 1)
+
 // channel-block shape per layer, from the measured sweep (tools/wgrad_bf16_bench.py under rocprofv3): every
 // launch is bound by the re-read traffic X * Cout/(16 NO) + dY * Cin/(16 NI) at ~4-5 TB/s; 3x3: 16 x 32 channels where Cout
 // allows (with the layers sharing grouped launches: -1.0 % on the training step and -1.2 % on the GAN iteration against
 // 32 x 16, three same-box repeats each; alone the two measured the same), else 32 x 16
 // (32 x 32 needs 36 accumulator blocks = the whole register file at one block per CU, and is slower);
-// 1x1 (transpose-conv backward): 32 x 64
-#define SQ_WGRAD_BF16_DISPATCH(FN, ...)                                                              \
-    do {                                                                                             \
-        const bool wide = !narrow_blocks();                                                          \
-        int mi_, mo_;                                                                                \
-        max_shape(&mi_, &mo_);                                                                       \
-        const bool i2 = wide && mi_ >= 2 && Cin % 32 == 0, o2 = wide && mo_ >= 2 && Cout % 32 == 0,  \
-                   o4 = wide && mo_ >= 4 && Cout % 64 == 0;                                          \
-        if (K == 3) {                                                                                \
-            const int k3_ = k3_shape();                                                              \
-            if (k3_ == 14 && Cout % 64 == 0) return FN<3, 1, 4>(__VA_ARGS__);                        \
-            if (k3_ == 22 && Cin % 32 == 0 && Cout % 32 == 0) return FN<3, 2, 2>(__VA_ARGS__);       \
-            if (k3_ == 12 && Cout % 32 == 0) return FN<3, 1, 2>(__VA_ARGS__);                        \
-            if (o2) return FN<3, 1, 2>(__VA_ARGS__);                                                 \
-            if (i2) return FN<3, 2, 1>(__VA_ARGS__);                                                 \
-            return FN<3, 1, 1>(__VA_ARGS__);                                                         \
-        }                                                                                            \
-        if (i2 && o4) return FN<1, 2, 4>(__VA_ARGS__);                                               \
-        if (i2 && o2) return FN<1, 2, 2>(__VA_ARGS__);                                               \
-        if (i2) return FN<1, 2, 1>(__VA_ARGS__);                                                     \
-        if (o2) return FN<1, 1, 2>(__VA_ARGS__);                                                     \
-        return FN<1, 1, 1>(__VA_ARGS__);                                                             \
-    } while (0)
-
-int64_t plan_floats(int N, int H, int W, int Cin, int Cout, int K) {
-    int gx, tpb;
-    int64_t wsf = 0;
-#define SQ_PLAN_CALL(KS_, NI_, NO_) (plan<KS_, NI_, NO_>(N, H, W, Cin, Cout, &gx, &tpb, &wsf), wsf)
-    if (Cin % 16 || Cout % 16) return K == 3 ? SQ_PLAN_CALL(3, 1, 1) : SQ_PLAN_CALL(1, 1, 1);
-    const bool wide = !narrow_blocks();
-    int mi_, mo_;
-    max_shape(&mi_, &mo_);
-    const bool i2 = wide && mi_ >= 2 && Cin % 32 == 0, o2 = wide && mo_ >= 2 && Cout % 32 == 0,
-               o4 = wide && mo_ >= 4 && Cout % 64 == 0;
-    if (K == 3) {
-        const int k3_ = k3_shape();
-        if (k3_ == 14 && Cout % 64 == 0) return SQ_PLAN_CALL(3, 1, 4);
-        if (k3_ == 22 && Cin % 32 == 0 && Cout % 32 == 0) return SQ_PLAN_CALL(3, 2, 2);
-        if (k3_ == 12 && Cout % 32 == 0) return SQ_PLAN_CALL(3, 1, 2);
-        if (o2) return SQ_PLAN_CALL(3, 1, 2);
-        if (i2) return SQ_PLAN_CALL(3, 2, 1);
-        return SQ_PLAN_CALL(3, 1, 1);
-    }
-    if (i2 && o4) return SQ_PLAN_CALL(1, 2, 4);
-    if (i2 && o2) return SQ_PLAN_CALL(1, 2, 2);
-    if (i2) return SQ_PLAN_CALL(1, 2, 1);
-    if (o2) return SQ_PLAN_CALL(1, 1, 2);
-    return SQ_PLAN_CALL(1, 1, 1);
-#undef SQ_PLAN_CALL
-}
-
-template <int KS, int NI, int NO>
-int launch_b(const __bf16 *x, const __bf16 *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin, int Cout,
-             hipStream_t st) {
-    return launch<KS, NI, NO, __bf16>(x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
-}
-template <int KS, int NI, int NO>
-int launch_f(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin, int Cout,
-             hipStream_t st) {
-    return launch<KS, NI, NO, float>(x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
-}
-
-int launch_any(const __bf16 *x, const __bf16 *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin,
-               int Cout, int K, hipStream_t st) {
-    if (Cin % 16 || Cout % 16)
-        return K == 3 ? launch_rag<3, __bf16>(x, dy, dw, db, ws, N, H, W, Cin, Cout, st)
-                      : launch_rag<1, __bf16>(x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
-    SQ_WGRAD_BF16_DISPATCH(launch_b, x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
-}
-int launch_any_mixed(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin,
-                     int Cout, int K, hipStream_t st) {
-    SQ_WGRAD_BF16_DISPATCH(launch_f, x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
-}
-
-// block shape (ni, no) of a layer: the choice SQ_WGRAD_BF16_DISPATCH makes
-inline void shape_for(int K, int Cin, int Cout, int *ni, int *no) {
-    const bool wide = !narrow_blocks();
-    int mi_, mo_;
-    max_shape(&mi_, &mo_);
-    const bool i2 = wide && mi_ >= 2 && Cin % 32 == 0, o2 = wide && mo_ >= 2 && Cout % 32 == 0,
-               o4 = wide && mo_ >= 4 && Cout % 64 == 0;
+// 1x1 (transpose-conv backward): 32 x 64.  Ragged channel counts (8 mod 16): 16 x 16.
+void wg_shape(int K, int Cin, int Cout, int *ni, int *no) {
     *ni = 1, *no = 1;
+    if (Cin % 16 || Cout % 16) return;
+    const bool wide = !narrow_blocks();
+    int mi, mo;
+    max_shape(&mi, &mo);
+    const bool i2 = wide && mi >= 2 && Cin % 32 == 0, o2 = wide && mo >= 2 && Cout % 32 == 0, o4 = wide && mo >= 4 && Cout % 64 == 0;
     if (K == 3) {
-        const int k3_ = k3_shape();
-        if (k3_ == 14 && Cout % 64 == 0) { *no = 4; return; }
-        if (k3_ == 22 && Cin % 32 == 0 && Cout % 32 == 0) { *ni = 2, *no = 2; return; }
-        if (k3_ == 12 && Cout % 32 == 0) { *no = 2; return; }
+        const int k3 = k3_shape();
+        if (k3 == 14 && Cout % 64 == 0) { *no = 4; return; }
+        if (k3 == 22 && Cin % 32 == 0 && Cout % 32 == 0) { *ni = 2, *no = 2; return; }
+        if (k3 == 12 && Cout % 32 == 0) { *no = 2; return; }
         if (o2) { *no = 2; return; }
         if (i2) { *ni = 2; return; }
         return;
@@ -738,25 +567,201 @@ inline void shape_for(int K, int Cin, int Cout, int *ni, int *no) {
     if (o2) { *no = 2; return; }
 }
 
-template <int KS, int NI, int NO>
-constexpr int pf_bf16() {
-    using C = WB<KS, NI, NO>;
-    constexpr int acc_regs = C::NTAP * NI * NO * 4, set_regs = (C::XSLOTS + C::YSLOTS) * 4;
-    constexpr int budget = (wgrad_occ<KS, NI, NO>() == 1 ? 300 : (wgrad_occ<KS, NI, NO>() == 4 ? 100 : (wgrad_occ<KS, NI, NO>() == 3 ? 140 : SQ_WGRAD_BUDGET2))) - acc_regs - 40;
-    return budget / set_regs >= 4 ? 4 : (budget / set_regs >= 3 ? 3 : (budget / set_regs >= 2 ? 2 : 1));
+// blocks of the finish kernel's groups: >= 16 consecutive floats (64 B) per load of a group
+int wg_finish_groups(int gx) {
+    const int G = sq_group_size(gx);
+    return G > 16 ? 16 : G;
 }
 
-// one grouped main launch + one grouped finish launch for items [0, n) (n <= GROUP_MAX), all of block shape <KS, NI, NO>
+inline int wg_red_floats(int KS, int NI, int NO) { return (KS * KS * 16 * NI + 1) * 16 * NO; }   // WB<>::RED_FLOATS
+
+struct WgPlan {
+    int KS, NI, NO, kind, PF, npairs, gx, tpb, G;               // tpb < 0: interleaved tile runs (block bx: tiles bx, bx + gx, ...)
+    int64_t ws_floats;                                          // partials: gx x npairs x RED_FLOATS
+};
+
+// N, H, W: the image the kernel tiles (for WG_MOSAIC the mosaic's); es: bytes per tensor element (2 bf16, 4 mixed)
+WgPlan wg_plan(int N, int H, int W, int Cin, int Cout, int K, int es, int kind) {
+    WgPlan p;
+    p.KS = K;
+    p.kind = kind;
+    wg_shape(K, Cin, Cout, &p.NI, &p.NO);
+    p.PF = wg_pf(K, p.NI, p.NO, es, kind == WG_RAGGED);
+    const int ci = 16 * p.NI, co = 16 * p.NO;
+    p.npairs = ((Cin + ci - 1) / ci) * ((Cout + co - 1) / co);
+    const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
+    // (512: targets that leave a layer with a number of tile ranges that is not a multiple of 8 -- 384, 768 -- put the channel-block
+    // pairs of one range on different XCDs, their shared operands are then fetched once per pair: 2.81 -> 3.2 ms per training step)
+    int want = (512 + p.npairs - 1) / p.npairs;
+    if (want < 1) want = 1;
+    int t = (ntiles + want - 1) / want;
+    if (t < 1) t = 1;
+    p.gx = (ntiles + t - 1) / t;
+    p.tpb = wgrad_interleave() ? -t : t;
+    p.G = wg_finish_groups(p.gx);
+    p.ws_floats = (int64_t)p.gx * p.npairs * wg_red_floats(K, p.NI, p.NO);
+    return p;
+}
+
+template <int KS, int NI, int NO>
+int finish(float *ws, float *dw, float *db, const WgPlan &p, int Cin, int Cout, hipStream_t st) {
+    using C = WB<KS, NI, NO>;
+    const int64_t total = (int64_t)p.npairs * C::RED_FLOATS;
+    const int OUT = 256 / p.G;
+    hipLaunchKernelGGL((conv_wgrad_bf16_finish_kernel<KS, NI, NO>), dim3((unsigned)((total + OUT - 1) / OUT)), dim3(256), 0, st,
+                       ws, dw, db, p.gx, Cin, Cout, p.G, t_dw_scale, KS == 1 ? t_convT_cout : 0);
+    return sq_check_launch("sq_conv2d_nhwc_wgrad_bf16(finish)");
+}
+
+// one layer: the main launch of plan p, then the finish.  MOS: X / dY are the compact small-image tensors of t_mos (3x3, same
+// plan and finish as the mosaic they form); RAG: the 16-channel plane past Cin / Cout loads as zeros
+template <int KS, int NI, int NO, typename TIO, bool MOS = false, bool RAG = false>
+int launch(const TIO *x, const TIO *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin, int Cout, const WgPlan &p,
+           hipStream_t st, const char *who) {
+    using C = WB<KS, NI, NO>;
+    constexpr int PF = wg_pf(KS, NI, NO, (int)sizeof(TIO), RAG);
+    static bool attr_set = false;
+    auto kern = conv_wgrad_bf16_kernel<KS, NI, NO, PF, TIO, MOS, RAG>;
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                C::LDS_BYTES) != hipSuccess) {
+            sq_set_error("conv_wgrad_bf16: cannot reserve %d bytes of LDS", C::LDS_BYTES);
+            return SQ_ELAUNCH;
+        }
+        attr_set = true;
+    }
+    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
+    hipLaunchKernelGGL(kern, dim3(p.gx, p.npairs), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout, tiles_x, tiles_y,
+                       tiles_x * tiles_y * N, p.tpb, MOS ? t_mos : SqMos{});
+    int rc = sq_check_launch(who);
+    if (rc) return rc;
+    return finish<KS, NI, NO>(ws, dw, db, p, Cin, Cout, st);
+}
+
+// kind of a one-layer call: the channel counts and the forms the entry points set around their dispatch
+inline int call_kind(int Cin, int Cout) {
+    return (Cin % 16 || Cout % 16) ? WG_RAGGED : (t_mos.h ? WG_MOSAIC : (t_convT_cout ? WG_CONVT : WG_PLAIN));
+}
+
+template <typename TIO>
+int launch_any(const TIO *x, const TIO *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin, int Cout, int K,
+               hipStream_t st) {
+    const int kind = call_kind(Cin, Cout);
+    const WgPlan p = wg_plan(N, H, W, Cin, Cout, K, (int)sizeof(TIO), kind);
+    if constexpr (sizeof(TIO) == 2) {
+        if (kind == WG_RAGGED)
+            return K == 3 ? launch<3, 1, 1, TIO, false, true>(x, dy, dw, db, ws, N, H, W, Cin, Cout, p, st, "sq_conv2d_nhwc_wgrad_bf16(ragged)")
+                          : launch<1, 1, 1, TIO, false, true>(x, dy, dw, db, ws, N, H, W, Cin, Cout, p, st, "sq_conv2d_nhwc_wgrad_bf16(ragged)");
+    }
+    if (kind == WG_MOSAIC) {
+#define SQ_WG_MOS(K_, I_, O_)                                                                                                 \
+        if (K == K_ && p.NI == I_ && p.NO == O_)                                                                              \
+            return launch<K_, I_, O_, TIO, true>(x, dy, dw, db, ws, N, H, W, Cin, Cout, p, st, "sq_conv2d_nhwc_wgrad_mixed_mosaic_f32");
+        SQ_WG_SHAPES3(SQ_WG_MOS)
+#undef SQ_WG_MOS
+    } else {
+#define SQ_WG_ONE(K_, I_, O_)                                                                                                 \
+        if (K == K_ && p.NI == I_ && p.NO == O_)                                                                              \
+            return launch<K_, I_, O_, TIO>(x, dy, dw, db, ws, N, H, W, Cin, Cout, p, st, "sq_conv2d_nhwc_wgrad_bf16");
+        SQ_WG_SHAPES(SQ_WG_ONE)
+#undef SQ_WG_ONE
+    }
+    sq_set_error("sq_conv2d_nhwc_wgrad_bf16: no kernel for K=%d blocks %dx%d kind %d", K, p.NI, p.NO, kind);
+    return SQ_EINVAL;
+}
+
 // geometry the kernel tiles: the tensor itself, or the mosaic of its small images
 inline void item_geom(const sq_wgrad_item &it, int *N, int *H, int *W) {
     if (it.mosaic_R > 0) { *N = 1; *H = it.mosaic_R * (it.H + 1); *W = it.mosaic_Cc * (it.W + 1); }
     else { *N = it.N; *H = it.H; *W = it.W; }
 }
+// the kernel form a grouped item runs (a transpose-conv item is a plain 1x1 one with its own finish)
+inline int item_kind(const sq_wgrad_item &it) { return it.mosaic_R > 0 ? WG_MOSAIC : ((it.Cin % 16 || it.Cout % 16) ? WG_RAGGED : WG_PLAIN); }
+// the plan of an item launched alone: what sq_conv2d_nhwc_wgrad_group_workspace_bf16 reserves for it
+inline WgPlan item_plan(const sq_wgrad_item &it) {
+    int N, H, W;
+    item_geom(it, &N, &H, &W);
+    return wg_plan(N, H, W, it.Cin, it.Cout, it.K, 2, it.convT_cout ? WG_CONVT : item_kind(it));
+}
 
+inline int pair_major_on() {                                    // SQ_WGRAD_PAIR_MAJOR=0: the plain block mapping in grouped launches
+    static const int v = [] { const char *e = getenv("SQ_WGRAD_PAIR_MAJOR"); return e ? atoi(e) : 1; }();
+    return v;
+}
+
+// one grouped launch ("bucket") per block shape and kind, GROUP_MAX items each; items in a bucket keep their order
+struct WgItemPlan {
+    int bucket;
+    WgPlan p;                                                   // gx, tpb: after the shrink; ws_floats: the floats the item writes
+    int pair_major;                                             // the pair-major block mapping applies (SQ_WGRAD_PAIR_MAJOR, gx % 8 == 0)
+    int64_t ws_offset;                                          // its partials' offset in the workspace, in floats
+};
+
+// plans of n items (group_item_ok each); returns the number of buckets
+int wg_group_plan(const sq_wgrad_item *items, int n, WgItemPlan *out) {
+    // Tiles per block: a layer launched alone is cut into ~512 blocks to fill the chip, and every block pays the cross-wave
+    // reduction and an 18 KB partial at its end -- the "fixed cost" of these launches.  Sharing the grid, the layers fill the
+    // chip together, so each is cut into a quarter as many, four times longer blocks (measured on one box, 13 + 4 layers of the
+    // training step: own plans 3.10 ms, / 2: 3.00, / 4: 2.95, / 8: 3.03; an equal-work split into ~1500 blocks that gave the
+    // four transpose-conv layers 1500 blocks instead of 512: 3.29).  SQ_WGRAD_GROUP_SHRINK overrides the divisor.
+    static const int shrink_env = [] { const char *e = getenv("SQ_WGRAD_GROUP_SHRINK"); return e ? atoi(e) : 0; }();
+    std::vector<char> done(n, 0);
+    int nbk = 0;
+    for (int i = 0; i < n; ++i) {
+        if (done[i]) continue;
+        const WgPlan pi = item_plan(items[i]);
+        const int kind = item_kind(items[i]);
+        int bucket[GROUP_MAX];
+        int nb = 0;
+        for (int j = i; j < n && nb < GROUP_MAX; ++j) {
+            if (done[j]) continue;
+            const WgPlan pj = item_plan(items[j]);
+            if (items[j].K != items[i].K || pj.NI != pi.NI || pj.NO != pi.NO || item_kind(items[j]) != kind) continue;
+            // two contributions to one gradient never share a launch (their finish blocks would race): the later one waits
+            // for the next round of this shape -- rounds run in item order, so "write, then accumulate" stays in order
+            bool clash = false;
+            for (int b2 = 0; b2 < nb && !clash; ++b2)
+                clash = items[bucket[b2]].dw == items[j].dw || (items[j].db && items[bucket[b2]].db == items[j].db);
+            for (int j2 = i; j2 < j && !clash; ++j2)              // ... nor overtake an earlier one that is still waiting
+                clash = !done[j2] && (items[j2].dw == items[j].dw || (items[j].db && items[j2].db == items[j].db));
+            if (clash) continue;
+            bucket[nb++] = j;
+            done[j] = 1;
+        }
+        // every bucket lays its partials out from the start of the workspace, each item in the room its own plan reserves
+        const int shrink = shrink_env > 0 ? shrink_env : (nb < 4 ? nb : 4);
+        int64_t off = 0;
+        for (int b = 0; b < nb; ++b) {
+            const sq_wgrad_item &it = items[bucket[b]];
+            WgItemPlan &q = out[bucket[b]];
+            q.bucket = nbk;
+            q.p = item_plan(it);
+            q.ws_offset = off;
+            off += q.p.ws_floats;
+            if (shrink > 1) {
+                int gN, gH, gW;
+                item_geom(it, &gN, &gH, &gW);
+                const int ntl = ((gW + TW - 1) / TW) * ((gH + TH - 1) / TH) * gN;
+                int g2 = q.p.gx / shrink;
+                if (g2 < 1) g2 = 1;
+                const int tpb = (ntl + g2 - 1) / g2;
+                q.p.gx = (ntl + tpb - 1) / tpb;
+                q.p.tpb = wgrad_interleave() ? -tpb : tpb;
+                q.p.G = wg_finish_groups(q.p.gx);
+                q.p.ws_floats = (int64_t)q.p.gx * q.p.npairs * wg_red_floats(q.p.KS, q.p.NI, q.p.NO);
+            }
+            q.pair_major = pair_major_on() && (q.p.gx & 7) == 0;
+        }
+        ++nbk;
+    }
+    return nbk;
+}
+
+// one grouped main launch + one grouped finish launch for the n items of a bucket, all of block shape <KS, NI, NO>
 template <int KS, int NI, int NO, bool MOS = false, bool RAG = false>
-int launch_group(const sq_wgrad_item *const *items, int n, float *ws, hipStream_t st) {
+int launch_group(const sq_wgrad_item *const *items, const WgItemPlan *const *plans, int n, float *ws, hipStream_t st) {
     using C = WB<KS, NI, NO>;
-    constexpr int PF = pf_bf16<KS, NI, NO>();
+    constexpr int PF = wg_pf(KS, NI, NO, 2, false);
     static bool attr_set = false;
     auto kern = conv_wgrad_bf16_group_kernel<KS, NI, NO, PF, __bf16, MOS, RAG>;
     if (!attr_set) {
@@ -770,34 +775,17 @@ int launch_group(const sq_wgrad_item *const *items, int n, float *ws, hipStream_
     SqWgradGroup g;
     SqWgradFinishGroup f;
     g.n = f.n = n;
-    static const int pair_major = [] { const char *e = getenv("SQ_WGRAD_PAIR_MAJOR"); return e ? atoi(e) : 1; }();
-    g.pair_major = pair_major;
+    g.pair_major = pair_major_on();                             // the kernel applies it to the items with gx % 8 == 0
     int blocks = 0, fblocks = 0;
-    float *wp = ws;
-    // Tiles per block: a layer launched alone is cut into ~512 blocks to fill the chip, and every block pays the cross-wave
-    // reduction and an 18 KB partial at its end -- the "fixed cost" of these launches.  Sharing the grid, the layers fill the
-    // chip together, so each is cut into a quarter as many, four times longer blocks (measured on one box, 13 + 4 layers of the
-    // training step: own plans 3.10 ms, / 2: 3.00, / 4: 2.95, / 8: 3.03; an equal-work split into ~1500 blocks that gave the
-    // four transpose-conv layers 1500 blocks instead of 512: 3.29).  SQ_WGRAD_GROUP_SHRINK overrides the divisor.
-    static const int shrink_env = [] { const char *e = getenv("SQ_WGRAD_GROUP_SHRINK"); return e ? atoi(e) : 0; }();
-    const int shrink = shrink_env > 0 ? shrink_env : (n < 4 ? n : 4);
+    static const int dbg = [] { const char *e = getenv("SQ_WGRAD_GROUP_DEBUG"); return e ? atoi(e) : 0; }();
     for (int e = 0; e < n; ++e) {
         const sq_wgrad_item &it = *items[e];
-        int gx, tpb, gN, gH, gW;
-        int64_t wsf;
+        const WgPlan &p = plans[e]->p;
+        int gN, gH, gW;
         item_geom(it, &gN, &gH, &gW);
-        plan<KS, NI, NO>(gN, gH, gW, it.Cin, it.Cout, &gx, &tpb, &wsf);
-        const int npairs = ((it.Cin + C::CI - 1) / C::CI) * ((it.Cout + C::CO - 1) / C::CO);
-        static const int dbg = [] { const char *e = getenv("SQ_WGRAD_GROUP_DEBUG"); return e ? atoi(e) : 0; }();
-        if (shrink > 1) {
-            const int ntl = ((gW + TW - 1) / TW) * ((gH + TH - 1) / TH) * gN;
-            int g2 = gx / shrink;
-            if (g2 < 1) g2 = 1;
-            tpb = (ntl + g2 - 1) / g2;
-            gx = (ntl + tpb - 1) / tpb;
-        }
         if (dbg) fprintf(stderr, "group<%d,%d,%d,%d,%d> item %d/%d: N=%d H=%d W=%d Cin=%d Cout=%d npairs=%d tpb=%d gx=%d acc=%d\n", KS, NI, NO,
-                         (int)MOS, (int)RAG, e, n, gN, gH, gW, it.Cin, it.Cout, npairs, tpb, gx, it.accumulate);
+                         (int)MOS, (int)RAG, e, n, gN, gH, gW, it.Cin, it.Cout, p.npairs, p.tpb, p.gx, it.accumulate);
+        float *wp = ws + plans[e]->ws_offset;
         g.first[e] = blocks;
         g.x[e] = it.x; g.dy[e] = it.dy; g.partials[e] = wp;
         g.N[e] = gN; g.H[e] = gH; g.W[e] = gW; g.Cin[e] = it.Cin; g.Cout[e] = it.Cout;
@@ -808,19 +796,16 @@ int launch_group(const sq_wgrad_item *const *items, int n, float *ws, hipStream_
             g.mos[e].mh = (65536u + (unsigned)it.H) / (unsigned)(it.H + 1);
             g.mos[e].mw = (65536u + (unsigned)it.W) / (unsigned)(it.W + 1);
         }
-        g.tpb[e] = wgrad_interleave() ? -tpb : tpb; g.gx[e] = gx;
-        blocks += gx * npairs;
-        int G = sq_group_size(gx);
-        if (G > 16) G = 16;
-        const int64_t total = (int64_t)npairs * C::RED_FLOATS;
-        const int OUT = 256 / G;
+        g.tpb[e] = p.tpb; g.gx[e] = p.gx;
+        blocks += p.gx * p.npairs;
+        const int64_t total = (int64_t)p.npairs * C::RED_FLOATS;
+        const int OUT = 256 / p.G;
         f.first[e] = fblocks;
         f.partials[e] = wp; f.dw[e] = it.dw; f.db[e] = it.db;
-        f.nblk[e] = gx; f.Cin[e] = it.Cin; f.Cout[e] = it.Cout; f.G[e] = G; f.dw_scale[e] = it.dw_scale;
+        f.nblk[e] = p.gx; f.Cin[e] = it.Cin; f.Cout[e] = it.Cout; f.G[e] = p.G; f.dw_scale[e] = it.dw_scale;
         f.ct[e] = KS == 1 ? it.convT_cout : 0;
         f.acc[e] = it.accumulate;
         fblocks += (int)((total + OUT - 1) / OUT);
-        wp += wsf;
     }
     g.first[n] = blocks;
     f.first[n] = fblocks;
@@ -831,18 +816,19 @@ int launch_group(const sq_wgrad_item *const *items, int n, float *ws, hipStream_
     return sq_check_launch("sq_conv2d_nhwc_wgrad_group_bf16(finish)");
 }
 
-int launch_group_any(int K, int ni, int no, int kind, const sq_wgrad_item *const *items, int n, float *ws, hipStream_t st) {
-    if (kind == 2)                                              // ragged channel counts: 16 x 16 channel blocks
-        return K == 3 ? launch_group<3, 1, 1, false, true>(items, n, ws, st) : launch_group<1, 1, 1, false, true>(items, n, ws, st);
-    if (kind == 1) {                                            // small-image mosaics (3x3)
-#define SQ_GM(I_, O_) if (ni == I_ && no == O_) return launch_group<3, I_, O_, true>(items, n, ws, st)
-        SQ_GM(1, 4); SQ_GM(2, 2); SQ_GM(1, 2); SQ_GM(2, 1); SQ_GM(1, 1);
+int launch_group_any(int kind, const sq_wgrad_item *const *items, const WgItemPlan *const *plans, int n, float *ws, hipStream_t st) {
+    const int K = plans[0]->p.KS, ni = plans[0]->p.NI, no = plans[0]->p.NO;
+    if (kind == WG_RAGGED)                                      // ragged channel counts: 16 x 16 channel blocks
+        return K == 3 ? launch_group<3, 1, 1, false, true>(items, plans, n, ws, st) : launch_group<1, 1, 1, false, true>(items, plans, n, ws, st);
+    if (kind == WG_MOSAIC) {                                    // small-image mosaics (3x3)
+#define SQ_GM(K_, I_, O_) if (K == K_ && ni == I_ && no == O_) return launch_group<K_, I_, O_, true>(items, plans, n, ws, st);
+        SQ_WG_SHAPES3(SQ_GM)
 #undef SQ_GM
-    }
-#define SQ_G(K_, I_, O_) if (K == K_ && ni == I_ && no == O_) return launch_group<K_, I_, O_>(items, n, ws, st)
-    SQ_G(3, 1, 4); SQ_G(3, 2, 2); SQ_G(3, 1, 2); SQ_G(3, 2, 1); SQ_G(3, 1, 1);
-    SQ_G(1, 2, 4); SQ_G(1, 2, 2); SQ_G(1, 2, 1); SQ_G(1, 1, 2); SQ_G(1, 1, 1);
+    } else {
+#define SQ_G(K_, I_, O_) if (K == K_ && ni == I_ && no == O_) return launch_group<K_, I_, O_>(items, plans, n, ws, st);
+        SQ_WG_SHAPES(SQ_G)
 #undef SQ_G
+    }
     sq_set_error("sq_conv2d_nhwc_wgrad_group_bf16: no kernel for K=%d blocks %dx%d", K, ni, no);
     return SQ_EINVAL;
 }
@@ -858,7 +844,7 @@ bool ok_shape(int N, int H, int W, int Cin, int Cout, int K, int elem_bytes = 2)
 
 extern "C" int64_t sq_conv2d_nhwc_wgrad_workspace_bf16(int N, int H, int W, int Cin, int Cout, int K) {
     if (!ok_shape(N, H, W, Cin, Cout, K)) return -1;
-    return plan_floats(N, H, W, Cin, Cout, K) * 4;
+    return wg_plan(N, H, W, Cin, Cout, K, 2, call_kind(Cin, Cout)).ws_floats * 4;
 }
 
 // dW (K,K,Cin,Cout) f32 and db (Cout) f32 from bf16 X (N,H,W,Cin) and bf16 dY (N,H,W,Cout).
@@ -879,7 +865,7 @@ extern "C" int sq_conv2d_nhwc_wgrad_bf16(const void *x, const void *dy, float *d
 // sq_conv2d_nhwc_fwd_mixed_f32.  Same block shapes, workspace and fixed-order finish as the bf16 entry.
 extern "C" int64_t sq_conv2d_nhwc_wgrad_workspace_mixed_f32(int N, int H, int W, int Cin, int Cout, int K) {
     if (!ok_shape(N, H, W, Cin, Cout, K, 4)) return -1;
-    return plan_floats(N, H, W, Cin, Cout, K) * 4;
+    return wg_plan(N, H, W, Cin, Cout, K, 4, WG_PLAIN).ws_floats * 4;
 }
 
 extern "C" int sq_conv2d_nhwc_wgrad_mixed_f32(const float *x, const float *dy, float *dw, float *db, float *workspace,
@@ -889,7 +875,7 @@ extern "C" int sq_conv2d_nhwc_wgrad_mixed_f32(const float *x, const float *dy, f
                "sq_conv2d_nhwc_wgrad_mixed_f32: unsupported shape Cin=%d Cout=%d K=%d (both %% 16, K 1|3, < 2 GiB)", Cin,
                Cout, K);
     SQ_REQUIRE_ALIGNED(x); SQ_REQUIRE_ALIGNED(dy); SQ_REQUIRE_ALIGNED(workspace);
-    return launch_any_mixed(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, reinterpret_cast<hipStream_t>(stream));
+    return launch_any(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, reinterpret_cast<hipStream_t>(stream));
 }
 
 // parameter gradients of conv_transpose_layer (2x2, stride 2; unet.py:312-318) from its input x (N,H,W,Cin) and the
@@ -964,16 +950,6 @@ extern "C" int sq_conv2d_nhwc_wgrad_mosaic_bf16(const void *x, const void *dy, f
 }
 
 // ---- several layers in one launch (sq_wgrad_item, include/sequitr_hip.h) ----------------------------------------------------
-static int item_kind(const sq_wgrad_item &it) { return it.mosaic_R > 0 ? 1 : ((it.Cin % 16 || it.Cout % 16) ? 2 : 0); }
-static void item_shape(const sq_wgrad_item &it, int *ni, int *no) {
-    if (item_kind(it) == 2) { *ni = *no = 1; return; }
-    shape_for(it.K, it.Cin, it.Cout, ni, no);
-}
-static int64_t item_floats(const sq_wgrad_item &it) {
-    int N, H, W;
-    item_geom(it, &N, &H, &W);
-    return plan_floats(N, H, W, it.Cin, it.Cout, it.K);
-}
 static bool group_item_ok(const sq_wgrad_item &it) {
     int N, H, W;
     item_geom(it, &N, &H, &W);
@@ -990,14 +966,14 @@ extern "C" int64_t sq_conv2d_nhwc_wgrad_group_workspace_bf16(const sq_wgrad_item
     int64_t total = 0;
     for (int i = 0; i < n; ++i) {
         if (!group_item_ok(items[i])) return -1;
-        total += item_floats(items[i]) * 4;
+        total += item_plan(items[i]).ws_floats * 4;
     }
     return total;
 }
 
 // dW / db of n layers (bf16 X and dY, channel counts multiples of 16) with one main launch and one finish launch per block
-// shape among them: each layer's result is bit-identical to sq_conv2d_nhwc_wgrad_scaled_bf16 / sq_convT2x2s2_wgrad_bf16 on it.
-// workspace: sq_conv2d_nhwc_wgrad_group_workspace_bf16(items, n) bytes.
+// shape among them: each layer's result equals that of sq_conv2d_nhwc_wgrad_scaled_bf16 / sq_convT2x2s2_wgrad_bf16 on it to
+// f32 rounding (the group plan cuts it into longer tile runs).  workspace: sq_conv2d_nhwc_wgrad_group_workspace_bf16(items, n) bytes.
 extern "C" int sq_conv2d_nhwc_wgrad_group_bf16(const sq_wgrad_item *items, int n, float *workspace, void *stream) {
     SQ_REQUIRE(items && n > 0 && workspace, "sq_conv2d_nhwc_wgrad_group_bf16: null pointer / no items");
     SQ_REQUIRE_ALIGNED(workspace);
@@ -1007,34 +983,72 @@ extern "C" int sq_conv2d_nhwc_wgrad_group_bf16(const sq_wgrad_item *items, int n
         SQ_REQUIRE_ALIGNED(items[i].x); SQ_REQUIRE_ALIGNED(items[i].dy);
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // buckets by (K, ni, no), GROUP_MAX items per launch.  Launches of one stream run in order, so every bucket lays its
+    // buckets by (K, ni, no, kind), GROUP_MAX items per launch.  Launches of one stream run in order, so every bucket lays its
     // partials out from the start of the workspace (the previous bucket's finish pass has read its own by then).
-    std::vector<char> done(n, 0);
-    for (int i = 0; i < n; ++i) {
-        if (done[i]) continue;
-        int ni, no;
-        item_shape(items[i], &ni, &no);
-        const int kind = item_kind(items[i]);
+    std::vector<WgItemPlan> plans(n);
+    const int nbk = wg_group_plan(items, n, plans.data());
+    for (int b = 0; b < nbk; ++b) {
         const sq_wgrad_item *bucket[GROUP_MAX];
+        const WgItemPlan *bp[GROUP_MAX];
         int nb = 0;
-        for (int j = i; j < n && nb < GROUP_MAX; ++j) {
-            if (done[j]) continue;
-            int nj, oj;
-            item_shape(items[j], &nj, &oj);
-            if (items[j].K != items[i].K || nj != ni || oj != no || item_kind(items[j]) != kind) continue;
-            // two contributions to one gradient never share a launch (their finish blocks would race): the later one waits
-            // for the next round of this shape -- rounds run in item order, so "write, then accumulate" stays in order
-            bool clash = false;
-            for (int b2 = 0; b2 < nb && !clash; ++b2)
-                clash = bucket[b2]->dw == items[j].dw || (items[j].db && bucket[b2]->db == items[j].db);
-            for (int j2 = i; j2 < j && !clash; ++j2)              // ... nor overtake an earlier one that is still waiting
-                clash = !done[j2] && (items[j2].dw == items[j].dw || (items[j].db && items[j2].db == items[j].db));
-            if (clash) continue;
-            bucket[nb++] = &items[j];
-            done[j] = 1;
-        }
-        const int rc = launch_group_any(items[i].K, ni, no, kind, bucket, nb, workspace, st);
+        for (int j = 0; j < n; ++j)
+            if (plans[j].bucket == b) bucket[nb] = &items[j], bp[nb++] = &plans[j];
+        const int rc = launch_group_any(item_kind(*bucket[0]), bucket, bp, nb, workspace, st);
         if (rc) return rc;
     }
     return SQ_OK;
+}
+
+// ---- launch plans without a HIP call (include/sequitr_hip.h) ----------------------------------------------------------------
+static void put_plan(const WgPlan &p, int64_t *out) {
+    const int64_t v[SQ_WGP_N] = {p.KS, p.NI, p.NO, p.kind, p.PF, p.npairs, p.gx, p.tpb, p.G, p.ws_floats};
+    for (int i = 0; i < SQ_WGP_N; ++i) out[i] = v[i];
+}
+
+extern "C" int sq_wgrad_plan(int family, int N, int H, int W, int Cin, int Cout, int K, const int *mosaic, int convT_cout,
+                             int64_t *out) {
+    SQ_REQUIRE(out, "sq_wgrad_plan: null out");
+    if (family == SQ_PLAN_F32) {
+        SQ_REQUIRE(!mosaic && !convT_cout, "sq_wgrad_plan: the f32 kernels have no mosaic / transpose-conv form");
+        SQ_REQUIRE(sq_wgrad_f32_plan(N, H, W, Cin, Cout, K, out) == SQ_OK,
+                   "sq_wgrad_plan: no f32 kernel takes N=%d H=%d W=%d Cin=%d Cout=%d K=%d", N, H, W, Cin, Cout, K);
+        return SQ_OK;
+    }
+    SQ_REQUIRE(family == SQ_PLAN_BF16 || family == SQ_PLAN_MIXED, "sq_wgrad_plan: bad family %d", family);
+    const int es = family == SQ_PLAN_BF16 ? 2 : 4;
+    int kind = WG_PLAIN, NN = N, HH = H, WW = W;
+    if (mosaic) {
+        SQ_REQUIRE(!convT_cout && K == 3 && N > 0 && H > 0 && W > 0 && H <= 8 && W <= 8 && mosaic[0] > 0 && mosaic[1] > 0 &&
+                       (int64_t)mosaic[0] * mosaic[1] >= N && Cin % 16 == 0 && Cout % 16 == 0,
+                   "sq_wgrad_plan: a mosaic is 3x3, of R x Cc >= N cells of images up to 8 x 8, channel counts %% 16");
+        NN = 1, HH = mosaic[0] * (H + 1), WW = mosaic[1] * (W + 1);
+        SQ_REQUIRE(HH < (1 << 13) && WW < (1 << 13), "sq_wgrad_plan: mosaic < 8192");
+        kind = WG_MOSAIC;
+    } else if (convT_cout) {
+        SQ_REQUIRE(family == SQ_PLAN_BF16 && K == 1 && Cout == 4 * convT_cout && Cin % 16 == 0 && Cout % 16 == 0,
+                   "sq_wgrad_plan: the transpose-conv form is bf16, K = 1, Cout = 4 * convT_cout, channel counts %% 16");
+        kind = WG_CONVT;
+    } else if (Cin % 16 || Cout % 16) {
+        kind = WG_RAGGED;
+    }
+    SQ_REQUIRE(ok_shape(NN, HH, WW, Cin, Cout, K, es), "sq_wgrad_plan: unsupported shape Cin=%d Cout=%d K=%d", Cin, Cout, K);
+    put_plan(wg_plan(NN, HH, WW, Cin, Cout, K, es, kind), out);
+    return SQ_OK;
+}
+
+extern "C" int sq_wgrad_group_plan(const sq_wgrad_item *items, int n, int64_t *out) {
+    SQ_REQUIRE(items && n > 0 && out, "sq_wgrad_group_plan: null pointer / no items");
+    for (int i = 0; i < n; ++i)
+        SQ_REQUIRE(group_item_ok(items[i]), "sq_wgrad_group_plan: item %d is not one the grouped kernel takes", i);
+    std::vector<WgItemPlan> plans(n);
+    const int nbk = wg_group_plan(items, n, plans.data());
+    for (int i = 0; i < n; ++i) {
+        const WgItemPlan &q = plans[i];
+        int64_t *o = out + (size_t)i * SQ_WGP_GROUP_N;
+        o[0] = q.bucket;
+        put_plan(q.p, o + 1);
+        o[1 + SQ_WGP_N] = q.pair_major;
+        o[2 + SQ_WGP_N] = q.ws_offset;
+    }
+    return nbk;
 }

@@ -236,24 +236,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_finish_kernel(const float *__r
 }
 
 template <int BN, int KS, int KC>
-int64_t ws_floats(int N, int H, int W, int Cin, int Cout, int *gx_out, int *tpb_out) {
-    using C = WCfg<BN, KS, KC>;
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int ntiles = tiles_x * tiles_y * N;
-    const int npairs = (Cin / KC) * ((Cout + BN - 1) / BN);
-    int want = (512 + npairs - 1) / npairs;                    // ~2 resident blocks per CU overall
-    if (want < 1) want = 1;
-    int tpb = (ntiles + want - 1) / want;
-    if (tpb < 1) tpb = 1;
-    const int gx = (ntiles + tpb - 1) / tpb;
-    if (gx_out) *gx_out = gx;
-    if (tpb_out) *tpb_out = tpb;
-    return (int64_t)gx * npairs * C::RED_FLOATS;
-}
-
-template <int BN, int KS, int KC>
 int launch(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin,
-           int Cout, hipStream_t st) {
+           int Cout, const int64_t *p, hipStream_t st) {
     using C = WCfg<BN, KS, KC>;
     static bool attr_set = false;
     auto kern = conv_wgrad_f32_kernel<BN, KS, KC>;
@@ -265,39 +249,27 @@ int launch(const float *x, const float *dy, float *dw, float *db, float *ws, int
         }
         attr_set = true;
     }
-    int gx, tpb;
-    ws_floats<BN, KS, KC>(N, H, W, Cin, Cout, &gx, &tpb);
+    const int gx = (int)p[SQ_WGP_GX], G = (int)p[SQ_WGP_G];
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const int npairs = (Cin / KC) * ((Cout + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3(gx, npairs), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout,
-                       tiles_x, tiles_y, tiles_x * tiles_y * N, tpb);
+    hipLaunchKernelGGL(kern, dim3(gx, (unsigned)p[SQ_WGP_NPAIRS]), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout,
+                       tiles_x, tiles_y, tiles_x * tiles_y * N, (int)p[SQ_WGP_TPB]);
     int rc = sq_check_launch("sq_conv2d_nhwc_wgrad_f32");
     if (rc) return rc;
-    const int G = sq_group_size(gx);
     const int64_t total = ((int64_t)KS * KS * Cin * Cout + Cout) * G;
     hipLaunchKernelGGL((conv_wgrad_finish_kernel<BN, KS, KC>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws,
                        dw, db, gx, Cin, Cout, G, t_dw_scale_f32);
     return sq_check_launch("sq_conv2d_nhwc_wgrad_f32(finish)");
 }
 
-#define SQ_WGRAD_DISPATCH(FN, ...)                                                        \
-    do {                                                                                  \
-        if (Cin % 16 == 0) {                                                              \
-            if (K == 3) { if (Cout > 16) return FN<32, 3, 16>(__VA_ARGS__); return FN<16, 3, 16>(__VA_ARGS__); } \
-            if (Cout > 16) return FN<32, 1, 16>(__VA_ARGS__);                             \
-            return FN<16, 1, 16>(__VA_ARGS__);                                            \
-        }                                                                                 \
-        if (K == 3) { if (Cout > 16) return FN<32, 3, 8>(__VA_ARGS__); return FN<16, 3, 8>(__VA_ARGS__); } \
-        if (Cout > 16) return FN<32, 1, 8>(__VA_ARGS__);                                  \
-        return FN<16, 1, 8>(__VA_ARGS__);                                                 \
-    } while (0)
-
-int64_t ws_dispatch(int N, int H, int W, int Cin, int Cout, int K) {
-    SQ_WGRAD_DISPATCH(ws_floats, N, H, W, Cin, Cout, nullptr, nullptr);
-}
 int launch_dispatch(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int H, int W,
-                    int Cin, int Cout, int K, hipStream_t st) {
-    SQ_WGRAD_DISPATCH(launch, x, dy, dw, db, ws, N, H, W, Cin, Cout, st);
+                    int Cin, int Cout, int K, const int64_t *p, hipStream_t st) {
+    const int KC = (int)p[SQ_WGP_NI], BN = (int)p[SQ_WGP_NO];
+#define SQ_W32(BN_, KS_, KC_) if (BN == BN_ && K == KS_ && KC == KC_) return launch<BN_, KS_, KC_>(x, dy, dw, db, ws, N, H, W, Cin, Cout, p, st);
+    SQ_W32(32, 3, 16) SQ_W32(16, 3, 16) SQ_W32(32, 1, 16) SQ_W32(16, 1, 16)
+    SQ_W32(32, 3, 8) SQ_W32(16, 3, 8) SQ_W32(32, 1, 8) SQ_W32(16, 1, 8)
+#undef SQ_W32
+    sq_set_error("sq_conv2d_nhwc_wgrad_f32: no kernel for BN=%d K=%d KC=%d", BN, K, KC);
+    return SQ_EINVAL;
 }
 
 // ---- first layer (Cin = 1..7, 3x3): the 9 taps ride the 16 MFMA rows, one accumulator per input channel ------
@@ -440,8 +412,9 @@ bool shape_ok(int N, int H, int W, int Cin, int Cout, int K) {
 template <typename TY>
 int launch_cin_small(const float *x, const TY *dy, float *dw, float *db, float *workspace, int N, int H, int W, int Cin,
                      int Cout, hipStream_t st, const char *who) {
-    int tpb;
-    const int gx = cin1_grid(N, H, W, &tpb);
+    int64_t p[SQ_WGP_N];
+    SQ_REQUIRE(sq_wgrad_f32_plan(N, H, W, Cin, Cout, 3, p) == SQ_OK && p[SQ_WGP_KIND] == SQ_WGP_F32_SMALL, "%s: Cin=%d unsupported (1..7)", who, Cin);
+    const int gx = (int)p[SQ_WGP_GX], tpb = (int)p[SQ_WGP_TPB];
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     const dim3 grid(gx, (Cout + 15) / 16);
 #define SQ_CIN_SMALL(C)                                                                                              \
@@ -456,7 +429,7 @@ int launch_cin_small(const float *x, const TY *dy, float *dw, float *db, float *
 #undef SQ_CIN_SMALL
     int rc = sq_check_launch(who);
     if (rc) return rc;
-    const int G = sq_group_size(gx), rows = 9 * Cin + 1;
+    const int G = (int)p[SQ_WGP_G], rows = 9 * Cin + 1;
     hipLaunchKernelGGL(conv_wgrad_cin1_finish_kernel, dim3((rows * Cout * G + 255) / 256), dim3(256), 0, st, workspace, dw,
                        db, gx, Cout, G, rows);
     return sq_check_launch(who);
@@ -464,10 +437,35 @@ int launch_cin_small(const float *x, const TY *dy, float *dw, float *db, float *
 
 }  // namespace
 
+// the plan of a call (sq_wgrad_plan, family SQ_PLAN_F32): out[SQ_WGP_N]
+int sq_wgrad_f32_plan(int N, int H, int W, int Cin, int Cout, int K, int64_t *out) {
+    if (!shape_ok(N, H, W, Cin, Cout, K)) return SQ_EINVAL;
+    int gx, tpb, npairs, kc, bn;
+    int64_t wsf;
+    if (Cin <= 7) {                                             // the small-Cin kernel: 16-channel co groups, one input chunk
+        gx = cin1_grid(N, H, W, &tpb);
+        kc = Cin, bn = 16, npairs = (Cout + 15) / 16;
+        wsf = (int64_t)gx * (9 * Cin + 1) * Cout;
+    } else {
+        kc = Cin % 16 == 0 ? 16 : 8;
+        bn = Cout > 16 ? 32 : 16;
+        const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
+        npairs = (Cin / kc) * ((Cout + bn - 1) / bn);
+        int want = (512 + npairs - 1) / npairs;                 // ~2 resident blocks per CU overall
+        if (want < 1) want = 1;
+        tpb = (ntiles + want - 1) / want;
+        if (tpb < 1) tpb = 1;
+        gx = (ntiles + tpb - 1) / tpb;
+        wsf = (int64_t)gx * npairs * (K * K * 16 + 1) * bn;    // WCfg<>::RED_FLOATS per pair
+    }
+    const int64_t v[SQ_WGP_N] = {K, kc, bn, Cin <= 7 ? SQ_WGP_F32_SMALL : SQ_WGP_F32, 1, npairs, gx, tpb, sq_group_size(gx), wsf};
+    for (int i = 0; i < SQ_WGP_N; ++i) out[i] = v[i];
+    return SQ_OK;
+}
+
 extern "C" int64_t sq_conv2d_nhwc_wgrad_workspace_f32(int N, int H, int W, int Cin, int Cout, int K) {
-    if (!shape_ok(N, H, W, Cin, Cout, K)) return -1;
-    if (Cin <= 7) return (int64_t)cin1_grid(N, H, W, nullptr) * (9 * Cin + 1) * Cout * 4;
-    return ws_dispatch(N, H, W, Cin, Cout, K) * 4;
+    int64_t p[SQ_WGP_N];
+    return sq_wgrad_f32_plan(N, H, W, Cin, Cout, K, p) == SQ_OK ? p[SQ_WGP_WS] * 4 : -1;
 }
 
 extern "C" int sq_conv2d_nhwc_wgrad_f32(const float *x, const float *dy, float *dw, float *db,
@@ -481,7 +479,9 @@ extern "C" int sq_conv2d_nhwc_wgrad_f32(const float *x, const float *dy, float *
     if (Cin <= 7)
         return launch_cin_small<float>(x, dy, dw, db, workspace, N, H, W, Cin, Cout, reinterpret_cast<hipStream_t>(stream),
                                        "sq_conv2d_nhwc_wgrad_f32(small Cin)");
-    return launch_dispatch(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, reinterpret_cast<hipStream_t>(stream));
+    int64_t p[SQ_WGP_N];
+    sq_wgrad_f32_plan(N, H, W, Cin, Cout, K, p);
+    return launch_dispatch(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, p, reinterpret_cast<hipStream_t>(stream));
 }
 
 // dW multiplied by dw_scale in the finish kernel (MFMA kernels: Cin 8 or a multiple of 16; the small-Cin kernel has no
@@ -497,8 +497,9 @@ extern "C" int sq_conv2d_nhwc_wgrad_scaled_f32(const float *x, const float *dy, 
 
 // first-layer weight gradient with a bf16 dY (the bf16 training graph): same MFMA-over-taps kernel
 extern "C" int64_t sq_conv3x3_first_wgrad_workspace_bf16(int N, int H, int W, int Cin, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || Cin < 1 || Cin > 7 || Cout <= 0 || Cout % 4) return -1;
-    return (int64_t)cin1_grid(N, H, W, nullptr) * (9 * Cin + 1) * Cout * 4;
+    int64_t p[SQ_WGP_N];
+    if (Cin < 1 || Cin > 7 || sq_wgrad_f32_plan(N, H, W, Cin, Cout, 3, p) != SQ_OK) return -1;
+    return p[SQ_WGP_WS] * 4;
 }
 
 extern "C" int sq_conv3x3_first_wgrad_bf16(const float *x, const void *dy, float *dw, float *db, float *workspace,
