@@ -772,6 +772,47 @@ int sq_wgrad_plan(int family, int N, int H, int W, int Cin, int Cout, int K, con
 int sq_wgrad_group_plan(const sq_wgrad_item *items, int n, int64_t *out);
 
 /* ------------------------------------------------------------------------------------------
+ * Volumes (UNet3D inference).  Layout NDHWC: x (N,D,H,W,C).  Numerics contract -- every 3-D op is DEFINED through the
+ * planar f32 entries above, so its result is pinned bit for bit by oracle/sq_oracle.c:
+ *   sq_conv3d_ndhwc_fwd_f32: 3x3x3 SAME stride-1 convolution + bias + activation.  w (3,3,3,Cin,Cout) (TF conv3d layout
+ *     kd,kh,kw,in,out), bias (Cout) or NULL, y (N,D,H,W,Cout).  y equals sq_conv2d_nhwc_fwd_f32 (K = 3) applied to the
+ *     N*D planar images of the depth-stacked input xs[n,d,h,w, kd*Cin + c] = x[n, d+kd-1, h, w, c] (zero slices beyond
+ *     the depth ends) with the stacked filter ws[kh,kw, kd*Cin + c, o] = w[kd,kh,kw,c,o]: one fmaf chain from +0 per
+ *     output, reduction order
+ *       Cin % 16 == 0: depth tap, 16-channel chunk, in-plane tap (raster), channel;
+ *       Cin in {1,2} (a single chunk of 3*Cin): in-plane tap, depth tap, channel;
+ *     then "+ bias", then the activation.  Supported: Cin in {1,2} or Cin % 16 == 0, Cout % 4 == 0, one depth slice
+ *     (H*W*max(Cin,Cout) floats) < 2 GiB; whole tensors may exceed 2 GiB (SQ_C3_WINDOW addressing).
+ *   sq_maxpool2x2x2_fwd_f32: 2x2x2 stride-2 VALID max pooling, the max of 8 values.  D,H,W even, C % 4 == 0.
+ *   sq_convT2x2x2s2_ndhwc_fwd_f32: 2x2x2 stride-2 transpose convolution + bias, then bridge(upscale, skip).  x (N,D,H,W,Cin),
+ *     w (2,2,2,Cout,Cin) (TF conv3d_transpose layout), skip / y (N,2D,2H,2W,Cout).  Output slice 2d+a equals
+ *     sq_convT2x2s2_nhwc_fwd_f32 of input slice d with w[a] (bias and bridge included).  Cin % 16 == 0, Cout % 4 == 0.
+ *   The 1x1x1 head + argmax, the bridges and batch-norm inference are pointwise: the planar entries on the
+ *   (N*D, H, W, C) view.
+ * sq_conv3d_plan: the launch plan of sq_conv3d_ndhwc_fwd_f32, computed on the host without a HIP call (the launcher calls
+ *   the same function).  out[SQ_C3P_N] = {kind SQ_C3_MFMA / SQ_C3_DIRECT, BN output channels per block, KC stacked input
+ *   channels per staged chunk, gx blocks over the pixel tiles (direct kernel: one per tile and 4 output slices), gy channel blocks, addressing SQ_C3_FLAT / SQ_C3_WINDOW}.  Returns SQ_OK, or
+ *   SQ_EINVAL for a shape no kernel takes.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_C3P_KIND 0
+#define SQ_C3P_BN 1
+#define SQ_C3P_KC 2
+#define SQ_C3P_GX 3
+#define SQ_C3P_GY 4
+#define SQ_C3P_ADDR 5
+#define SQ_C3P_N 6
+#define SQ_C3_MFMA 0
+#define SQ_C3_DIRECT 1
+#define SQ_C3_FLAT 0
+#define SQ_C3_WINDOW 1
+int sq_conv3d_plan(int N, int D, int H, int W, int Cin, int Cout, int *out);
+int sq_conv3d_ndhwc_fwd_f32(const float *x, const float *w, const float *bias, float *y, int N, int D, int H, int W,
+                            int Cin, int Cout, int act, void *stream);
+int sq_maxpool2x2x2_fwd_f32(const float *x, float *y, int N, int D, int H, int W, int C, void *stream);
+int sq_convT2x2x2s2_ndhwc_fwd_f32(const float *x, const float *w, const float *bias, const float *skip, float *y, int N,
+                                  int D, int H, int W, int Cin, int Cout, int bridge, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tile front end: raw single-channel camera frames in HBM (OctopusData .dat memmap,
  * sequitr/dataio/octopus.py:231-245) -> ImageNorm (sequitr/pipeline.py:350-356) -> network tiles, and the
  * tile masks back to full-frame masks.

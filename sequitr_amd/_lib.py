@@ -183,6 +183,10 @@ SIGNATURES = {
     "sq_conv2d_nhwc_wgrad_group_bf16": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "sq_wgrad_plan": (c_int, [c_int] * 7 + [c_void_p, c_int, c_void_p]),
     "sq_wgrad_group_plan": (c_int, [c_void_p, c_int, c_void_p]),
+    "sq_conv3d_plan": (c_int, [c_int] * 6 + [c_void_p]),
+    "sq_conv3d_ndhwc_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
+    "sq_maxpool2x2x2_fwd_f32": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
+    "sq_convT2x2x2s2_ndhwc_fwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     "sq_act_bwd_bf16": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
     "sq_bridge_fwd_bf16": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
     "sq_bridge_bwd_bf16": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_void_p]),

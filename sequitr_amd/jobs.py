@@ -154,6 +154,94 @@ def SERVER_segment(params, options):
     return info
 
 
+def _load_volumes(params):
+    """(N, Z, X, Y, C) float32 volumes from a .npy path, an ndarray or {'synthetic': True, 'volumes': n, 'seed': s}
+    (params['shape'] = (X, Y, Z) as UNet3D takes it); (Z, X, Y) and (N, Z, X, Y) inputs gain the missing axes."""
+    src = params.get('input')
+    if isinstance(src, np.ndarray):
+        x = src
+    elif isinstance(src, str) and src.endswith('.npy'):
+        x = np.load(src, mmap_mode='r', allow_pickle=False)
+    elif isinstance(src, dict) and src.get('synthetic'):
+        if len(tuple(params.get('shape', ()))) != 3:
+            raise ValueError("synthetic volumes need params['shape'] = (X, Y, Z), got %r" % (params.get('shape'),))
+        X, Y, Z = tuple(params['shape'])
+        x = np.random.default_rng(src.get('seed', 0)).standard_normal(
+            (src.get('volumes', 1), Z, X, Y, params.get('num_inputs', 1))).astype(np.float32)
+    else:
+        raise ValueError("params['input'] must be a .npy path, an ndarray or {'synthetic': True, ...}")
+    if x.ndim == 3:
+        x = x[np.newaxis, ..., np.newaxis]
+    elif x.ndim == 4:
+        x = x[..., np.newaxis]
+    if x.ndim != 5:
+        raise ValueError('volumes must be (N, Z, X, Y[, C]), got shape %s' % (x.shape,))
+    return x
+
+
+def SERVER_segment_volume(params, options):
+    """Segment volumes (z-stacks) with UNet3D, one volume per launch: writes ``mask.npy`` (uint8, N x Z x X x Y),
+    with options['save_logits'] ``logits.npy``, with options['centroids'] the centroid file (``tracks.hdf5``, or
+    ``.npz`` without h5py) as CentroidWriter.write makes it from the (N,Z,X,Y) mask, and ``segment_volume.json``.
+    params: as SERVER_segment (input, num_inputs, num_outputs, filters, bridge, batch_norm, model for a warm start);
+    shape defaults to (X, Y, Z) of the input (synthetic input needs it).  options: gpu, save_logits, centroids.
+
+    ``segment_volume.json``: ``seconds`` / ``mvoxels_per_s`` cover the volumes (upload, network, download);
+    ``setup_seconds`` is weights plus one warm-up volume."""
+    import torch
+    from .networks.unet import UNet3D
+    from . import utils
+
+    device = _resolve_device(params, options)
+    torch.cuda.set_device(torch.device(device))
+    out_dir = params['output']
+    x = _load_volumes(params)
+    N, Z, X, Y = x.shape[:4]
+    net_p = _net_params(params, device)
+    net_p.setdefault('shape', (X, Y, Z))
+    net_p.setdefault('num_inputs', x.shape[4])
+    t_setup = time.time()
+    net = UNet3D(net_p, 'infer')
+    model = params.get('model')
+    if model:
+        model_dir = model if os.path.isdir(model) else utils.get_latest_model_dir(
+            os.path.join(utils.core.TensorflowConfiguration.MODELDIR, model))
+        if model_dir is None:
+            raise IOError('No saved model found for {0}'.format(model))
+        net.load_state_dict(utils.load_model_weights(model_dir))
+        logger.info('Loaded weights from {0:s}'.format(model_dir))
+    else:
+        net.initialize()
+    want_logits = bool(options.get('save_logits'))
+    net.predict(np.ascontiguousarray(x[:1]))                    # warm-up: first-launch costs stay in the set-up time
+    torch.cuda.synchronize()
+    masks = np.zeros((N, Z, X, Y), np.uint8)
+    logits = np.zeros((N, Z, X, Y, net.n_outputs), np.float32) if want_logits else None
+    t0 = time.time()
+    for i in range(N):
+        m = net.predict(np.ascontiguousarray(x[i:i + 1]))
+        masks[i] = m[0].cpu().numpy()
+        if logits is not None:
+            logits[i] = net.logits()[0].cpu().numpy()
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    np.save(os.path.join(out_dir, 'mask.npy'), masks)
+    if logits is not None:
+        np.save(os.path.join(out_dir, 'logits.npy'), logits)
+    voxels = N * Z * X * Y
+    info = {'volumes': int(N), 'shape': [int(Z), int(X), int(Y)], 'seconds': dt, 'setup_seconds': t0 - t_setup,
+            'mvoxels_per_s': float(voxels / max(dt, 1e-9) / 1e6), 'device': device}
+    if options.get('centroids'):
+        from .centroids import CentroidWriter
+        with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
+            frames = cw.write(masks, device=device)
+        info['centroids'] = {'file': os.path.basename(cw.filename), 'objects': int(sum(len(f) for f in frames))}
+    with open(os.path.join(out_dir, 'segment_volume.json'), 'w') as f:
+        json.dump(info, f, indent=2)
+    logger.info('Segmented {volumes} volumes in {seconds:.3f}s on {device}'.format(**info))
+    return info
+
+
 def SERVER_segment_frames(params, options):
     """Segment whole camera frames (larger than the network tile): params['input'] = an Octopus stream stem
     (sequitr/dataio/octopus.py), a .npy of (F,H,W) uint8/uint16/float32 frames, or an ndarray.  Raw frames

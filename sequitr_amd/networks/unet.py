@@ -841,3 +841,122 @@ class UNet2DBf16(UNet2D):
     def build(self, features):
         self._skip_boxes = {}
         return UNet2D.build(self, features)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Volumes: the reference's UNet base class is written for them (unet.py:56, 148-216: `slices`, an (N, slices, width,
+# height, C) input).  UNet3D is its volumetric subclass, inference only, on the 3-D HIP kernels (sq_conv3d_f32.hip).
+
+def unet3d_variable_shapes(params):
+    """(key, shape) of every UNet3D variable in creation order: the 2-D scope names with 3x3x3 kernels (3,3,3,Cin,Cout),
+    2x2x2 transpose-conv kernels (2,2,2,Cout,Cin) and the 1x1x1 head (1,1,1,C,n_out)."""
+    p = dict(params, kernel=(3, 3, 3), up_kernel=(2, 2, 2))
+    out = []
+    for key, shape in unet_variable_shapes(p):
+        if key == 'UNet/to_image/kernel':
+            shape = (1,) + tuple(shape)
+        out.append((key, tuple(shape)))
+    return out
+
+
+def init_unet3d_weights(params, seed=0):
+    """Host-side initial UNet3D weights {key: float32 ndarray}, drawn as init_unet_weights draws them (variance_scaling's
+    fan-in rule shape[-2] * prod(shape[:-2]) covers the 5-D kernels)."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for key, shape in unet3d_variable_shapes(params):
+        if key.endswith('kernel'):
+            w[key] = variance_scaling(shape, rng)
+        else:
+            w[key] = (np.ones if key.endswith('gamma') else np.zeros)(shape, np.float32)
+    return w
+
+
+class UNet3D(UNet2D):
+    """Volumetric U-Net (the reference's UNet3D, unet.py:56) whose leaf ops are the 3-D HIP kernels: conv_layer = 3x3x3
+    SAME conv + bias + ReLU (ops.conv3d), pool = 2x2x2/s2 max, conv_transpose_layer = 2x2x2/s2 transpose conv + bias,
+    conv_layer_1x1 = 1x1x1 head (+ argmax) on the flat (N*D, H, W, C) view.  params['shape'] = (width, height, slices);
+    the input is (N, slices, width, height[, C]).  Inference only: mode 'train' raises."""
+
+    def __init__(self, params, mode=PREDICT):
+        if mode == TRAIN:
+            raise NotImplementedError('UNet3D is inference only: 3-D training needs the conv3d input and weight gradients '
+                                      '(dgrad, wgrad), the 2x2x2 pool / transpose-conv backward and a volumetric loss, '
+                                      'none of which exist yet')
+        p = dict(params)
+        p.setdefault('kernel', (3, 3, 3))
+        p.setdefault('up_kernel', (2, 2, 2))
+        if tuple(p['kernel']) != (3, 3, 3):
+            raise ValueError('kernel %s unsupported: UNet3D convolutions are 3x3x3' % (tuple(p['kernel']),))
+        if tuple(p['up_kernel']) != (2, 2, 2):
+            raise ValueError('up_kernel %s unsupported: UNet3D transpose convolutions are 2x2x2' % (tuple(p['up_kernel']),))
+        if len(tuple(p.get('shape', ()))) != 3:
+            raise ValueError("UNet3D needs params['shape'] = (width, height, slices), got %r" % (p.get('shape'),))
+        UNet2D.__init__(self, dict(p, kernel=(3, 3), up_kernel=(2, 2), fuse=False), mode)
+        self.kernel, self.up_kernel = (3, 3, 3), (2, 2, 2)
+        self._params = p
+
+    def expected_variables(self):
+        req = dict(unet3d_variable_shapes(self._params))
+        opt = {}
+        if self.batch_norm:
+            for k, shp in list(req.items()):
+                if k.endswith('/gamma'):
+                    sc = k.rsplit('/', 1)[0]
+                    opt[sc + '/moving_mean'] = opt[sc + '/moving_variance'] = shp
+        return req, opt
+
+    def _initial_weights(self):
+        return init_unet3d_weights(self._params, self._seed)
+
+    def build(self, features):
+        """unet.py:224-262 hook by hook: none of UNet2D's fused planar kernels may see a 5-D tensor."""
+        self._mask = None
+        self._dropout_calls = 0
+        self._builds += 1
+        return UNet.build(self, features)
+
+    # -- leaf hooks ------------------------------------------------------------------------
+    def conv_layer(self, x, filters):
+        w, b = self._kernel((3, 3, 3, x.shape[-1], filters)), self._bias(filters)
+        if self.batch_norm:
+            return self.batch_norm_layer(ops.conv3d(x, w, b, act=None), act='relu')   # pointwise: any leading shape
+        return ops.conv3d(x, w, b, act='relu')
+
+    def conv_layer_1x1(self, x, filters):
+        N, D, H, W, C = x.shape
+        w, b = self._kernel((1, 1, 1, C, filters)), self._bias(filters)
+        flat, w2 = x.view(N * D, H, W, C), w.view(1, 1, C, filters)
+        if filters <= 7 and C % 4 == 0:
+            logits, mask = ops.conv1x1_argmax(flat, w2, b)     # logits + prediction in one pass
+            self._mask = mask.view(N, D, H, W)
+            return logits.view(N, D, H, W, filters)
+        return ops.conv2d(flat, w2, b, act=None).view(N, D, H, W, filters)
+
+    def conv_transpose_layer(self, x, filters):
+        w, b = self._kernel((2, 2, 2, filters, x.shape[-1])), self._bias(filters)
+        return ops.convT2x2x2s2(x, w, b)
+
+    def pool_layer(self, x):
+        return ops.maxpool2x2x2(x)
+
+    def up_layer(self, x, filters, bridge, name=None):
+        """The base wiring; add / mul / sub bridges run inside the transpose conv's epilogue while neither the transpose
+        conv nor the bridge is overridden (same bits)."""
+        fused = (type(self).conv_transpose_layer is UNet3D.conv_transpose_layer and self.bridge is self._default_bridge
+                 and self.bridge_type in ('eltwise_add', 'eltwise_mul', 'eltwise_sub'))
+        if not fused:
+            return UNet.up_layer(self, x, filters, bridge, name=name)
+        with self.variable_scope('up{0:d}'.format(name)):
+            with self.variable_scope('upscale'):
+                w, b = self._kernel((2, 2, 2, filters, x.shape[-1])), self._bias(filters)
+            merged = ops.convT2x2x2s2(x, w, b, skip=bridge, bridge=self.bridge_type)
+            out = self.conv_block(merged, filters)
+        return out
+
+    def predict(self, features):
+        """build + argmax: the uint8 class mask (N, slices, width, height), ties -> lowest class."""
+        return UNet2D.predict(self, features)
+
+    def predict_stream(self, *a, **k):
+        raise NotImplementedError('UNet3D segments one volume per call (predict); the streamed tile path is planar')

@@ -393,6 +393,72 @@ def convT2x2s2(x, w, bias=None, skip=None, bridge=None, out=None):
     return y
 
 
+def conv3d_plan(N, D, H, W, Cin, Cout):
+    """Launch plan of sq_conv3d_ndhwc_fwd_f32 (host only, no HIP call): dict kind ('mfma' / 'direct'), bn, kc, gx, gy,
+    addressing ('flat' / 'window').  Raises SequitrHipError for a shape no kernel takes."""
+    import ctypes
+    out = (ctypes.c_int * 6)()
+    lib = _lib.load()
+    _lib.check(lib.sq_conv3d_plan(N, D, H, W, Cin, Cout, out), "sq_conv3d_plan")
+    return {'kind': ('mfma', 'direct')[out[0]], 'bn': out[1], 'kc': out[2], 'gx': out[3], 'gy': out[4],
+            'addressing': ('flat', 'window')[out[5]]}
+
+
+def conv3d(x, w, bias=None, act=None, out=None):
+    """3x3x3 SAME conv + bias + activation on a volume.  x (N,D,H,W,Cin), w (3,3,3,Cin,Cout) (TF conv3d layout).
+    Defined as the planar conv2d of the depth-stacked input (include/sequitr_hip.h); Cin in {1,2} or Cin % 16 == 0,
+    Cout % 4 == 0."""
+    _chk(x, "x", ndim=5), _chk(w, "w", ndim=5)
+    N, D, H, W, Cin = x.shape
+    if tuple(w.shape[:4]) != (3, 3, 3, Cin):
+        raise ValueError("conv3d weight must be (3,3,3,%d,Cout), got %s" % (Cin, tuple(w.shape)))
+    Cout = w.shape[4]
+    if bias is not None:
+        _chk(bias, "bias")
+        if bias.numel() != Cout:
+            raise ValueError("bias must have %d elements" % Cout)
+    y = _out(out, (N, D, H, W, Cout), x)
+    _lib.check(_lib.load().sq_conv3d_ndhwc_fwd_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), N, D, H, W, Cin, Cout, ACT[act],
+                                                  _stream()), "sq_conv3d_ndhwc_fwd_f32")
+    return y
+
+
+def maxpool2x2x2(x, out=None):
+    """2x2x2 stride-2 VALID max pooling.  x (N,D,H,W,C), D, H, W even, C % 4 == 0."""
+    _chk(x, "x", ndim=5)
+    N, D, H, W, C = x.shape
+    y = _out(out, (N, D // 2, H // 2, W // 2, C), x)
+    _lib.check(_lib.load().sq_maxpool2x2x2_fwd_f32(_ptr(x), _ptr(y), N, D, H, W, C, _stream()), "sq_maxpool2x2x2_fwd_f32")
+    return y
+
+
+def convT2x2x2s2(x, w, bias=None, skip=None, bridge=None, out=None):
+    """2x2x2/s2 transpose conv (+bias) fused with bridge(upscale, skip).  x (N,D,H,W,Cin), w (2,2,2,Cout,Cin)
+    (TF conv3d_transpose layout); output slice 2d+a is convT2x2s2 of input slice d with w[a]."""
+    _chk(x, "x", ndim=5), _chk(w, "w", ndim=5)
+    N, D, H, W, Cin = x.shape
+    if tuple(w.shape[:3]) != (2, 2, 2) or w.shape[4] != Cin:
+        raise ValueError("3-D transpose-conv weight must be (2,2,2,Cout,%d), got %s" % (Cin, tuple(w.shape)))
+    Cout = w.shape[3]
+    b = BRIDGE[bridge]
+    oshape = (N, 2 * D, 2 * H, 2 * W, Cout)
+    if b:
+        if skip is None:
+            raise ValueError("bridge %r needs a skip tensor" % bridge)
+        _chk(skip, "skip", ndim=5)
+        if tuple(skip.shape) != oshape:
+            raise ValueError("skip has shape %s, expected %s" % (tuple(skip.shape), oshape))
+    if bias is not None:
+        _chk(bias, "bias")
+        if bias.numel() != Cout:
+            raise ValueError("bias must have %d elements" % Cout)
+    y = _out(out, oshape, x)
+    _lib.check(_lib.load().sq_convT2x2x2s2_ndhwc_fwd_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(skip) if b else None, _ptr(y),
+                                                        N, D, H, W, Cin, Cout, b, _stream()),
+               "sq_convT2x2x2s2_ndhwc_fwd_f32")
+    return y
+
+
 def bridge(a, b, kind, out=None):
     _chk(a, "a"), _chk(b, "b")
     if a.shape != b.shape:
