@@ -812,6 +812,35 @@ int sq_maxpool2x2x2_fwd_f32(const float *x, float *y, int N, int D, int H, int W
 int sq_convT2x2x2s2_ndhwc_fwd_f32(const float *x, const float *w, const float *bias, const float *skip, float *y, int N,
                                   int D, int H, int W, int Cin, int Cout, int bridge, void *stream);
 
+/* Volumes, training side (f32; UNet3DTrain).  Pointwise gradients (activation, bridge, dropout, batch norm, head, loss)
+ * are the planar entries on flat views.
+ *   sq_conv3d_weight_transform_f32: wt[kd][kh][kw][co][ci] = w[2-kd][2-kh][2-kw][ci][co].  The input gradient of
+ *     sq_conv3d_ndhwc_fwd_f32 is DEFINED as sq_conv3d_ndhwc_fwd_f32(dY, wt, NULL, ..., Cin := Cout, Cout := Cin, act none):
+ *     it inherits that entry's reduction order and oracle.  Supported where the forward takes the swapped channels:
+ *     Cout % 16 == 0 or Cout in {1,2}, and Cin % 4 == 0; anything else SQ_EINVAL.
+ *   sq_conv3d_ndhwc_wgrad_f32: dw (3,3,3,Cin,Cout), dw[kd,kh,kw,c,o] = sum_{n,d,h,w} x[n,d+kd-1,h+kh-1,w+kw-1,c] *
+ *     dy[n,d,h,w,o] (zeros outside the volume), db[o] = sum dy[...,o] (db may be NULL): the planar weight gradient of the
+ *     depth-stacked input.  Two-stage fixed-order sums, no float atomics, run-to-run bit-identical; every element of dw and
+ *     db is written (dw[0], dw[2] are exact zeros at D == 1).  Supported: Cin in {1,2} or Cin % 16 == 0, Cout % 4 == 0,
+ *     every tensor < 2 GiB.  workspace: sq_conv3d_ndhwc_wgrad_workspace_f32 bytes (-1: shape not taken).
+ *   sq_conv3d_wgrad_plan: its launch plan, host only (the launcher and the workspace query call it).  out[SQ_WGP_N] as
+ *     sq_wgrad_plan: KS 3; NI = stacked input channels per chunk (16, or 3*Cin for Cin in {1,2}); NO = output channels per
+ *     block; kind SQ_WGP_F32 / SQ_WGP_F32_SMALL; PF 1; npairs = (depth tap, ci chunk, co chunk) triples (small: co groups);
+ *     gx tile ranges over the N*D*tiles pixel tiles; tpb; G; workspace floats.  SQ_EINVAL for a shape no kernel takes.
+ *   sq_maxpool2x2x2_bwd_f32: x the pool input (N,D,H,W,C), dy (N,D/2,H/2,W/2,C); the gradient goes to the FIRST maximum
+ *     of each window in (depth, row, column) raster order, zeros elsewhere; every element of dx is written.  D,H,W even,
+ *     C % 4 == 0.
+ *   sq_space_to_depth2x2x2_f32: dy (N,2D,2H,2W,C) -> g (N,D,H,W,8C), g[n,d,i,j, ((2a+b)*2+e)*C + c] = dy[n,2d+a,2i+b,2j+e,c]
+ *     (D,H,W the small side): the transpose conv's backward is then a planar 1x1 conv and a planar 1x1 weight gradient
+ *     on the (N*D, H, W, .) views.  C % 4 == 0. */
+int sq_conv3d_weight_transform_f32(const float *w, float *wt, int Cin, int Cout, void *stream);
+int sq_conv3d_wgrad_plan(int N, int D, int H, int W, int Cin, int Cout, int64_t *out);
+int64_t sq_conv3d_ndhwc_wgrad_workspace_f32(int N, int D, int H, int W, int Cin, int Cout);
+int sq_conv3d_ndhwc_wgrad_f32(const float *x, const float *dy, float *dw, float *db, float *workspace, int N, int D, int H,
+                              int W, int Cin, int Cout, void *stream);
+int sq_maxpool2x2x2_bwd_f32(const float *x, const float *dy, float *dx, int N, int D, int H, int W, int C, void *stream);
+int sq_space_to_depth2x2x2_f32(const float *dy, float *g, int N, int D, int H, int W, int C, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Tile front end: raw single-channel camera frames in HBM (OctopusData .dat memmap,
  * sequitr/dataio/octopus.py:231-245) -> ImageNorm (sequitr/pipeline.py:350-356) -> network tiles, and the

@@ -187,6 +187,12 @@ SIGNATURES = {
     "sq_conv3d_ndhwc_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
     "sq_maxpool2x2x2_fwd_f32": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
     "sq_convT2x2x2s2_ndhwc_fwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
+    "sq_conv3d_weight_transform_f32": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
+    "sq_conv3d_wgrad_plan": (c_int, [c_int] * 6 + [c_void_p]),
+    "sq_conv3d_ndhwc_wgrad_workspace_f32": (c_int64, [c_int] * 6),
+    "sq_conv3d_ndhwc_wgrad_f32": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
+    "sq_maxpool2x2x2_bwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p]),
+    "sq_space_to_depth2x2x2_f32": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
     "sq_act_bwd_bf16": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
     "sq_bridge_fwd_bf16": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
     "sq_bridge_bwd_bf16": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_void_p]),

@@ -144,11 +144,17 @@ def _want(pid):
     return pid is not None and (_WANTED is None or pid in _WANTED)
 
 
-def convT_param_grads(dwp, dbp, Cin, Cout, sinks):
-    """(dW (2,2,Cout,Cin), db (Cout)) of the 2x2/s2 transpose conv from the 1x1 wgrad of its
-    space-to-depth form (dwp (1,1,Cin,4Cout), dbp (4Cout) or None); written into the sinks when set."""
+def convT_param_grads(dwp, dbp, Cin, Cout, sinks, taps=(2, 2)):
+    """(dW taps + (Cout,Cin), db (Cout)) of the stride-2 transpose conv with 2x2 (taps=(2,2)) or 2x2x2 (taps=(2,2,2))
+    kernel from the 1x1 wgrad of its space-to-depth form (dwp (1,1,Cin,T*Cout), dbp (T*Cout) or None, T = 4 or 8 taps);
+    written into the sinks when set."""
     sw, sb = sinks
-    dw = dwp.reshape(Cin, 2, 2, Cout).permute(1, 2, 3, 0)
+    taps = tuple(taps)
+    T = 1
+    for t in taps:
+        T *= t
+    nt = len(taps)
+    dw = dwp.reshape((Cin,) + taps + (Cout,)).permute(*(tuple(range(1, nt + 2)) + (0,)))
     if sw is not None:
         sw.copy_(dw)
         dw = None
@@ -157,9 +163,9 @@ def convT_param_grads(dwp, dbp, Cin, Cout, sinks):
     db = None
     if dbp is not None:
         if sb is not None:
-            torch.sum(dbp.reshape(4, Cout), 0, out=sb)
+            torch.sum(dbp.reshape(T, Cout), 0, out=sb)
         else:
-            db = dbp.reshape(4, Cout).sum(0)
+            db = dbp.reshape(T, Cout).sum(0)
     return dw, db
 
 
@@ -763,6 +769,93 @@ class _ConvT(torch.autograd.Function):
 
 def convT2x2s2(x, w, bias=None):
     return _ConvT.apply(x, w, bias)
+
+
+# ---------------------------------------------------------------------------------------------
+# Volumes (UNet3DTrain; first order): conv3d, 2x2x2 max-pool, 2x2x2/s2 transpose conv
+# ---------------------------------------------------------------------------------------------
+class _Conv3d(torch.autograd.Function):
+    """act(conv3d(x, w) + bias) on (N,D,H,W,C).  Backward: the flat activation backward, then the input gradient as a
+    forward conv3d with the transformed filter (ops.conv3d_dgrad) and the 3-D weight-gradient kernel (ops.conv3d_wgrad),
+    which writes the parameters' gradient sinks directly when a trainer attached them."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, act):
+        y = ops.conv3d(x, w, bias, act=act)
+        ctx.act, ctx.has_bias = act, bias is not None
+        ctx.sinks = (grad_sink(w), grad_sink(bias))
+        ctx.save_for_backward(x, w, y if ops.ACT[act] else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        dpre = ops.act_bwd(dy.contiguous(), y, ctx.act) if y is not None else dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.conv3d_dgrad(dpre, w)
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or need_b:
+            sw, sb = ctx.sinks
+            dw, db = ops.conv3d_wgrad(x, dpre, want_bias=need_b, dw_out=sw, db_out=sb if need_b else None)
+            if sw is not None:
+                dw = None
+            if sb is not None or not need_b:
+                db = None
+        return dx, dw, db, None
+
+
+def conv3d(x, w, bias=None, act=None):
+    return _Conv3d.apply(x, w, bias, act)
+
+
+class _MaxPool3d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.maxpool2x2x2(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool2x2x2_bwd(x, dy.contiguous())
+
+
+def maxpool2x2x2(x):
+    return _MaxPool3d.apply(x)
+
+
+class _ConvT3d(torch.autograd.Function):
+    """2x2x2/s2 transpose conv + bias.  Backward = 2x2x2 space-to-depth, then a planar 1x1 dgrad and a planar 1x1 wgrad on
+    the (N*D, H, W, .) views: convT(x) == depth_to_space(conv1x1(x, W')), W'[c][((2a+b)*2+e)*Cout + o] = W[a,b,e,o,c]."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        ctx.sinks = (grad_sink(w), grad_sink(bias))
+        return ops.convT2x2x2s2(x, w, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        N, D, H, W, Cin = x.shape
+        Cout = w.shape[3]
+        g = ops.space_to_depth2x2x2(dy.contiguous()).view(N * D, H, W, 8 * Cout)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.conv2d(g, w.reshape(1, 1, 8 * Cout, Cin), None, act=None).view(N, D, H, W, Cin)
+        if ctx.needs_input_grad[1] or ctx.has_bias:
+            dwp, dbp = ops.conv2d_wgrad(x.view(N * D, H, W, Cin), g, 1, want_bias=ctx.has_bias)   # (1,1,Cin,8Cout), (8Cout)
+            dw, db = convT_param_grads(dwp, dbp if ctx.has_bias else None, Cin, Cout, ctx.sinks, taps=(2, 2, 2))
+        return dx, dw, db
+
+
+def convT2x2x2s2(x, w, bias=None):
+    return _ConvT3d.apply(x, w, bias)
 
 
 class _Bridge(torch.autograd.Function):

@@ -494,3 +494,105 @@ def SERVER_train(params, options):
             json.dump(dict(info, losses=losses), f, indent=2)
         logger.info('Trained {steps} steps, loss {first_loss:.4f} -> {last_loss:.4f}, saved {model_dir}'.format(**info))
     return info
+
+
+def SERVER_train_volume(params, options):
+    """Train the volumetric U-Net (UNet3DTrain, f32) on a stack of volumes with the weighted softmax cross-entropy.
+
+    params: images (.npy (N, slices, width, height[, C]) float), labels (.npy (N, slices, width, height) class indices,
+    or one-hot with a trailing class axis), weights (.npy, one value per voxel; absent: a uniform weight of 1 -- a
+    volumetric weight map is not computed here), the NetConfiguration keys (name, shape = (width, height, slices),
+    num_outputs, learning_rate, num_epochs, dropout, filters, bridge, batch_norm, warm_start ...), batch_size (default
+    1), warmup_steps.  Learning-rate defaults are the trainer's (train.DEFAULT_LEARNING_RATE ramped over
+    train.DEFAULT_WARMUP_STEPS), as in SERVER_train.  options: gpu, max_steps.
+
+    Single process, eager steps: the volumes, labels and weights are uploaded once, a batch is an index_select.  Writes
+    ``weights.npz`` + ``net.config`` into the next numbered folder of MODELDIR/<name>/ and ``train.json`` (losses,
+    ms_per_step) into params['output'].  The model loads strictly into UNet3D (SERVER_segment_volume's ``model``).
+    """
+    import torch
+    from . import utils
+    from .networks.unet import UNet3DTrain
+    from .train import UNetTrainer
+
+    if int(os.environ.get('WORLD_SIZE', 1)) > 1:
+        raise RuntimeError('SERVER_train_volume runs in a single process (data-parallel volume training does not exist)')
+    device = _resolve_device(params, options)
+    torch.cuda.set_device(torch.device(device))
+    dev = torch.device(device)
+    x = np.load(params['images'], mmap_mode='r', allow_pickle=False)
+    if x.ndim == 4:
+        x = x[..., np.newaxis]
+    if x.ndim != 5:
+        raise ValueError('images must be (N, slices, width, height[, C]), got shape %s' % (x.shape,))
+    N, Z, X, Y, C = x.shape
+    cfg_keys = ('name', 'shape', 'num_inputs', 'num_outputs', 'num_epochs', 'learning_rate', 'warm_start', 'dropout')
+    cfg = {k: params[k] for k in cfg_keys if k in params}
+    cfg.setdefault('shape', (X, Y, Z))
+    cfg.setdefault('num_inputs', int(C))
+    config = utils.NetConfiguration.from_params(cfg)
+    labels = np.load(params['labels'], allow_pickle=False)
+    if labels.ndim == 5:
+        onehot = np.ascontiguousarray(labels[..., :config.num_outputs], dtype=np.uint8)
+    else:
+        onehot = np.stack([(labels == c) for c in range(config.num_outputs)], -1).astype(np.uint8)
+    if tuple(onehot.shape[:4]) != (N, Z, X, Y):
+        raise ValueError('labels %s do not match the images %s' % (labels.shape, x.shape))
+    if params.get('weights'):
+        wmap = np.load(params['weights'], allow_pickle=False).reshape((N, Z, X, Y, 1)).astype(np.float32)
+    else:
+        wmap = np.ones((N, Z, X, Y, 1), np.float32)
+
+    net_p = _net_params(params, device)
+    net_p['shape'] = tuple(config.shape)
+    net_p['num_inputs'], net_p['num_outputs'] = int(config.num_inputs), int(config.num_outputs)
+    net_p['dropout'] = float(params.get('dropout', 0.4))
+    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'),
+                          net_cls=UNet3DTrain)
+    config.learning_rate = trainer.lr                          # net.config records what was used
+    config.warmup_steps = trainer.warmup_steps
+    if config.warm_start:
+        latest = config.warm_start_from()
+        if latest:
+            trainer.load_state_dict(utils.load_model_weights(latest))
+            logger.info('Warm start from {0:s}'.format(latest))
+
+    batch = max(1, min(int(params.get('batch_size', 1)), N))
+    steps_per_epoch = N // batch
+    epochs = int(params.get('num_epochs', config.num_epochs))
+    max_steps = options.get('max_steps')
+    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    x_dev = torch.from_numpy(np.array(x, dtype=np.float32, order='C')).to(dev)
+    y_dev = torch.from_numpy(np.ascontiguousarray(onehot)).to(dev)
+    w_dev = torch.from_numpy(np.ascontiguousarray(wmap)).to(dev)
+    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    rng = np.random.default_rng(int(params.get('seed', 0)))
+    done = 0
+    t_start = t_steady = time.time()
+    for epoch in range(epochs):
+        if done >= total_steps:
+            break
+        order = torch.from_numpy(rng.permutation(N)).to(dev)
+        for s in range(steps_per_epoch):
+            if done >= total_steps:
+                break
+            idx = order[s * batch:(s + 1) * batch]
+            loss_log[done].copy_(trainer.step(x_dev.index_select(0, idx), y_dev.index_select(0, idx),
+                                              w_dev.index_select(0, idx)))
+            done += 1
+            if done == 1:                                      # the first step carries the first-launch costs
+                torch.cuda.synchronize()
+                t_steady = time.time()
+    torch.cuda.synchronize()
+    t_end = time.time()
+    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
+    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
+            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady) * 1e3 / (done - 1) if done > 1 else None,
+            'steady_steps': max(done - 1, 0), 'batch_size': batch, 'volumes': int(N), 'shape': [int(Z), int(X), int(Y)],
+            'graph': False, 'dtype': 'f32', 'warmup_steps': trainer.warmup_steps, 'learning_rate': trainer.lr,
+            'world': 1, 'device': device}
+    info['model_dir'] = utils.save_model(trainer.state_dict(), config)
+    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
+        json.dump(dict(info, losses=losses), f, indent=2)
+    logger.info('Trained {steps} steps on volumes, loss {first_loss} -> {last_loss}, saved {model_dir}'.format(**info))
+    return info

@@ -282,6 +282,11 @@ class UNet2D(UNet):
         self._mask = None
 
     # -- variables ---------------------------------------------------------------------
+    @classmethod
+    def variable_shapes(cls, params):
+        """(key, shape) of the trainable variables in creation order: what a trainer's flat buckets are laid out by"""
+        return unet_variable_shapes(params)
+
     def get_variable(self, name, shape, init):
         key = self.scope + '/' + name
         v = self._vars.get(key)
@@ -876,13 +881,16 @@ class UNet3D(UNet2D):
     """Volumetric U-Net (the reference's UNet3D, unet.py:56) whose leaf ops are the 3-D HIP kernels: conv_layer = 3x3x3
     SAME conv + bias + ReLU (ops.conv3d), pool = 2x2x2/s2 max, conv_transpose_layer = 2x2x2/s2 transpose conv + bias,
     conv_layer_1x1 = 1x1x1 head (+ argmax) on the flat (N*D, H, W, C) view.  params['shape'] = (width, height, slices);
-    the input is (N, slices, width, height[, C]).  Inference only: mode 'train' raises."""
+    the input is (N, slices, width, height[, C]).  Inference only: mode 'train' raises; its subclass UNet3DTrain trains
+    (f32) and produces models this class loads strictly."""
+
+    _TRAINABLE = False                                         # only UNet3DTrain sets it
 
     def __init__(self, params, mode=PREDICT):
-        if mode == TRAIN:
+        if mode == TRAIN and not type(self)._TRAINABLE:
             raise NotImplementedError('UNet3D is inference only: 3-D training needs the conv3d input and weight gradients '
                                       '(dgrad, wgrad), the 2x2x2 pool / transpose-conv backward and a volumetric loss, '
-                                      'none of which exist yet')
+                                      'none of which exist yet in this class -- train with UNet3DTrain')
         p = dict(params)
         p.setdefault('kernel', (3, 3, 3))
         p.setdefault('up_kernel', (2, 2, 2))
@@ -895,6 +903,10 @@ class UNet3D(UNet2D):
         UNet2D.__init__(self, dict(p, kernel=(3, 3), up_kernel=(2, 2), fuse=False), mode)
         self.kernel, self.up_kernel = (3, 3, 3), (2, 2, 2)
         self._params = p
+
+    @classmethod
+    def variable_shapes(cls, params):
+        return unet3d_variable_shapes(params)
 
     def expected_variables(self):
         req = dict(unet3d_variable_shapes(self._params))
@@ -960,3 +972,54 @@ class UNet3D(UNet2D):
 
     def predict_stream(self, *a, **k):
         raise NotImplementedError('UNet3D segments one volume per call (predict); the streamed tile path is planar')
+
+
+class UNet3DTrain(UNet3D):
+    """UNet3D that can be trained in f32 (train.UNetTrainer(params, net_cls=UNet3DTrain)): in mode 'train' the leaf hooks
+    are the differentiable wrappers of sequitr_amd.functional -- F.conv3d (3-D weight gradient, input gradient as a
+    forward conv3d with the transformed filter), F.maxpool2x2x2, F.convT2x2x2s2 (space-to-depth + planar 1x1 kernels) --
+    the 1x1x1 head is the planar head on the flat (N*D, H, W, C) view, dropout and batch norm are the shape-agnostic
+    planar functions, and up_layer runs transpose conv and bridge unfused (the fused epilogue does not keep the
+    pre-bridge tensor the multiplicative bridge's gradient needs).  In modes 'infer' / 'eval' every hook defers to
+    UNet3D (the fused transpose conv + bridge included): same kernels, same bits, same variable names, so a trained
+    state_dict loads strictly into UNet3D."""
+
+    _TRAINABLE = True
+
+    def conv_layer(self, x, filters):
+        if not self.training:
+            return UNet3D.conv_layer(self, x, filters)
+        w, b = self._kernel((3, 3, 3, x.shape[-1], filters)), self._bias(filters)
+        if self.batch_norm:
+            return self.batch_norm_layer(F.conv3d(x, w, b, act=None), act='relu')
+        return F.conv3d(x, w, b, act='relu')
+
+    def conv_layer_1x1(self, x, filters):
+        if not self.training:
+            return UNet3D.conv_layer_1x1(self, x, filters)
+        N, D, H, W, C = x.shape
+        w, b = self._kernel((1, 1, 1, C, filters)), self._bias(filters)
+        flat, w2 = x.view(N * D, H, W, C), w.view(1, 1, C, filters)
+        if filters <= 4 and C in (8, 16, 32):
+            return F.conv1x1_head(flat, w2, b).view(N, D, H, W, filters)
+        return F.conv2d(flat, w2, b, act=None).view(N, D, H, W, filters)
+
+    def pool_layer(self, x):
+        return F.maxpool2x2x2(x) if self.training else ops.maxpool2x2x2(x)
+
+    def up_layer(self, x, filters, bridge, name=None):
+        """Training: the base wiring with the differentiable transpose conv, then the bridge as its own op.  The
+        transpose-conv hook itself is not overridden, so outside training UNet3D.up_layer still finds its own hook and
+        fuses the bridge into the transpose conv's epilogue.  A subclass that overrides the hook gets the base wiring."""
+        if not self.training:
+            return UNet3D.up_layer(self, x, filters, bridge, name=name)
+        if type(self).conv_transpose_layer is not UNet3D.conv_transpose_layer:
+            return UNet.up_layer(self, x, filters, bridge, name=name)
+        with self.variable_scope('up{0:d}'.format(name)):
+            with self.variable_scope('upscale'):
+                w, b = self._kernel((2, 2, 2, filters, x.shape[-1])), self._bias(filters)
+                upscale = F.convT2x2x2s2(x, w, b)
+            with self.variable_scope('bridge'):
+                merged = self.bridge(upscale, bridge)
+            out = self.conv_block(merged, filters)
+        return out

@@ -799,6 +799,88 @@ def space_to_depth2(dy):
     return g
 
 
+def conv3d_weight_transform(w):
+    """(3,3,3,Cin,Cout) -> the input gradient's filter (3,3,3,Cout,Cin), all three tap axes reversed.  Not cached: a
+    U-Net weight is differentiated once per step and the optimiser rewrites it before the next."""
+    _chk(w, "w", ndim=5)
+    if tuple(w.shape[:3]) != (3, 3, 3):
+        raise ValueError("conv3d weight must be (3,3,3,Cin,Cout), got %s" % (tuple(w.shape),))
+    Cin, Cout = w.shape[3], w.shape[4]
+    wt = torch.empty((3, 3, 3, Cout, Cin), dtype=torch.float32, device=w.device)
+    _lib.check(_lib.load().sq_conv3d_weight_transform_f32(_ptr(w), _ptr(wt), Cin, Cout, _stream()),
+               "sq_conv3d_weight_transform_f32")
+    return wt
+
+
+def conv3d_dgrad(dy, w):
+    """dX of conv3d: the forward conv3d of dY (N,D,H,W,Cout) with the transformed filter of w (3,3,3,Cin,Cout).
+    Cout in {1,2} or Cout % 16 == 0, Cin % 4 == 0."""
+    _chk(dy, "dy", ndim=5), _chk(w, "w", ndim=5)
+    if w.shape[4] != dy.shape[4]:
+        raise ValueError("conv3d_dgrad: weight %s does not match dy channels %d" % (tuple(w.shape), dy.shape[4]))
+    return conv3d(dy, conv3d_weight_transform(w), None, act=None)
+
+
+_WGP_KEYS = ('ks', 'ni', 'no', 'kind', 'pf', 'npairs', 'gx', 'tpb', 'g', 'workspace_floats')
+
+
+def conv3d_wgrad_plan(N, D, H, W, Cin, Cout):
+    """Launch plan of sq_conv3d_ndhwc_wgrad_f32 (host only, no HIP call): dict ks, ni (stacked input channels per chunk),
+    no (output channels per block), kind ('mfma' / 'small'), pf, npairs, gx, tpb, g, workspace_floats.  Raises
+    SequitrHipError for a shape no kernel takes."""
+    import ctypes
+    out = (ctypes.c_int64 * 10)()
+    _lib.check(_lib.load().sq_conv3d_wgrad_plan(N, D, H, W, Cin, Cout, out), "sq_conv3d_wgrad_plan")
+    plan = dict(zip(_WGP_KEYS, (int(v) for v in out)))
+    plan['kind'] = {4: 'mfma', 5: 'small'}[plan['kind']]
+    return plan
+
+
+def conv3d_wgrad(x, dy, want_bias=True, dw_out=None, db_out=None):
+    """(dW (3,3,3,Cin,Cout), db (Cout) or None) from X (N,D,H,W,Cin) and dY (N,D,H,W,Cout).  dw_out / db_out: optional
+    float32 destinations the finish kernel writes straight into.  Cin in {1,2} or Cin % 16 == 0, Cout % 4 == 0."""
+    _chk(x, "x", ndim=5), _chk(dy, "dy", ndim=5)
+    N, D, H, W, Cin = x.shape
+    Cout = dy.shape[4]
+    if tuple(dy.shape[:4]) != (N, D, H, W):
+        raise ValueError("x %s and dy %s differ in N,D,H,W" % (tuple(x.shape), tuple(dy.shape)))
+    lib = _lib.load()
+    nbytes = lib.sq_conv3d_ndhwc_wgrad_workspace_f32(N, D, H, W, Cin, Cout)
+    if nbytes < 0:
+        raise _lib.SequitrHipError("conv3d_wgrad: unsupported shape %s Cin=%d Cout=%d: %s"
+                                   % ((N, D, H, W), Cin, Cout, (lib.sq_last_error() or b"?").decode()))
+    ws = _workspace(nbytes, x.device)
+    dw = _grad_out(dw_out, (3, 3, 3, Cin, Cout), x.device)
+    db = _grad_out(db_out, (Cout,), x.device) if want_bias else None
+    _lib.check(lib.sq_conv3d_ndhwc_wgrad_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), N, D, H, W, Cin, Cout,
+                                            _stream()), "sq_conv3d_ndhwc_wgrad_f32")
+    return dw, db
+
+
+def maxpool2x2x2_bwd(x, dy):
+    """dX of maxpool2x2x2: x the pool input (N,D,H,W,C), dy (N,D/2,H/2,W/2,C); first maximum in raster order takes it."""
+    _chk(x, "x", ndim=5), _chk(dy, "dy", ndim=5)
+    N, D, H, W, C = x.shape
+    if tuple(dy.shape) != (N, D // 2, H // 2, W // 2, C):
+        raise ValueError("dy has shape %s, expected %s" % (tuple(dy.shape), (N, D // 2, H // 2, W // 2, C)))
+    dx = torch.empty_like(x)
+    _lib.check(_lib.load().sq_maxpool2x2x2_bwd_f32(_ptr(x), _ptr(dy), _ptr(dx), N, D, H, W, C, _stream()),
+               "sq_maxpool2x2x2_bwd_f32")
+    return dx
+
+
+def space_to_depth2x2x2(dy):
+    """(N,2D,2H,2W,C) -> (N,D,H,W,8C), channel index ((2a+b)*2+e)*C + c."""
+    _chk(dy, "dy", ndim=5)
+    N, D2, H2, W2, C = dy.shape
+    if D2 % 2 or H2 % 2 or W2 % 2:
+        raise ValueError("space_to_depth2x2x2 needs even D,H,W, got %s" % (tuple(dy.shape),))
+    g = torch.empty((N, D2 // 2, H2 // 2, W2 // 2, 8 * C), dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.load().sq_space_to_depth2x2x2_f32(_ptr(dy), _ptr(g), N, D2 // 2, H2 // 2, W2 // 2, C, _stream()),
+               "sq_space_to_depth2x2x2_f32")
+    return g
+
+
 def conv1x1_small_bwd(x, w, dz, want_dx=True, dw_out=None, db_out=None):
     """Backward of the to_image head: returns (dx or None, dw (1,1,Cin,Cout), db (Cout))."""
     _chk(x, "x", ndim=4), _chk(w, "w", ndim=4), _chk(dz, "dz", ndim=4)

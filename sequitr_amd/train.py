@@ -43,7 +43,7 @@ class UNetTrainer(object):
         self.group = group
         self.step_count = 0
         dev = self.net.device
-        shapes = unet_variable_shapes(params)
+        shapes = net_cls.variable_shapes(params) if hasattr(net_cls, 'variable_shapes') else unet_variable_shapes(params)
         self.pbucket = FlatBucket(shapes, dev)
         self.gbucket = FlatBucket(shapes, dev)
         self.m = torch.zeros_like(self.pbucket.flat)
