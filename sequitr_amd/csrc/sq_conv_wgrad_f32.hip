@@ -12,12 +12,27 @@
 // The reduction over the 4.2M pixels of a level-0 batch is split across blocks and finished
 // by a second kernel that adds the block partials IN A FIXED ORDER: no float atomics, results
 // are run-to-run reproducible (MI355X_MICROARCH.md "Global float atomics").
+//
+// One kernel family serves the planar (NHWC) and the volumetric (NDHWC, 3x3x3 SAME) convolution: every kernel takes the
+// number of depth taps DT at compile time (1 = planar, 3 = volumetric).  The volumetric gradient
+//   dW[kd][kh][kw][ci][co] = sum over voxels p of X[p + (kd-1, kh-1, kw-1)][ci] * dY[p][co],  db[co] = sum_p dY[p][co]
+// is the planar one of the depth-stacked input xs[n,d,h,w, kd*Cin + c] = x[n, d+kd-1, h, w, c] over the N*D planar
+// images; xs is never built.  At DT = 3
+//   - the MFMA kernel's pair is (depth tap kd, ci chunk, co chunk): the X halo of the tile at output slice nd = n*D + d
+//     is read from slice nd + kd - 1, or is all zeros when d + kd - 1 leaves [0, D) -- the tap never reaches into the
+//     neighbouring volume of the batch; the dY tile comes from slice nd.  Accumulators and LDS per block are the planar
+//     kernel's.  db is taken from the centre depth tap's partials only (every pair sums dY; the centre tap always reads
+//     a real slice);
+//   - the small-Cin kernel stages DT halo slices and keeps DT*CIN accumulators (Cin 1 and 2 only).
+// Every element of dW and db is written: at D == 1 the taps kd = 0 and kd = 2 see only zero halos and come out as exact
+// zeros.  Everything under DT is `if constexpr`: the DT = 1 instances compile to what they were without it.
 #include "sq_common.h"
 #include <stdlib.h>
 
 namespace {
 
 constexpr int TH = 16, TW = 16;
+constexpr int64_t LIM32 = (int64_t)1 << 31;
 
 template <int BN, int KS, int KC>
 struct WCfg {
@@ -42,11 +57,12 @@ struct WCfg {
     static_assert((XS_FLOATS * 4) % 16 == 0, "dY image must start 16-B aligned");
 };
 
-// partials layout: [gridDim.x][npairs][ROWS][BN]
-template <int BN, int KS, int KC>
+// partials layout: [gridDim.x][npairs][ROWS][BN]; pair = (kd * (Cin/KC) + ci chunk) * nco + co chunk = blockIdx.y.
+// N counts planar images (N * D at DT = 3, D slices per volume); a tile is (tx, ty, n), walked n-major.
+template <int BN, int KS, int KC, int DT>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_f32_kernel(
     const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ partials,
-    int N, int H, int W, int Cin, int Cout, int tiles_x, int tiles_y, int ntiles, int tiles_per_block) {
+    int N, int H, int W, int Cin, int Cout, int tiles_x, int tiles_y, int ntiles, int tiles_per_block, int D) {
     using C = WCfg<BN, KS, KC>;
     constexpr int NR = C::NR, PAD = KS / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -56,10 +72,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f32_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 15, kk = lane >> 4;
     const int nco = (Cout + BN - 1) / BN;
-    const int ci0 = (blockIdx.y / nco) * KC, co0 = (blockIdx.y % nco) * BN;
+    unsigned pair = blockIdx.y;
+    int kd = 0;
+    if constexpr (DT > 1) {
+        const unsigned per_tap = (Cin / KC) * nco;
+        kd = pair / per_tap, pair %= per_tap;
+    }
+    const int ci0 = (pair / nco) * KC, co0 = (pair % nco) * BN;
     const int t_begin = blockIdx.x * tiles_per_block;
     const int t_end = min(t_begin + tiles_per_block, ntiles);
 
+    // whole tensors are < 2 GiB (the plans refuse anything else): one resource each, 32-bit byte offsets
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(x), 0, (int)((size_t)N * H * W * Cin * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -72,14 +95,22 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f32_kernel(
     auto issue = [&](int tile) {
         const int tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
         const int x0 = tx * TW, y0 = ty * TH;
-        const int xbase = (((n * H + y0 - PAD) * W + x0 - PAD) * Cin) * 4;
+        // DT > 1: the depth tap reads slice n + kd - DT/2 of the SAME volume, else the depth border's zeros.  The slice
+        // index is formed only for a slice that exists: slice N of a tensor just under 2 GiB would overflow the int
+        bool depth_ok = true;
+        int nx = n;
+        if constexpr (DT > 1) {
+            depth_ok = (unsigned)(n % D + kd - DT / 2) < (unsigned)D;
+            nx = depth_ok ? n + kd - DT / 2 : 0;
+        }
+        const int xbase = (((nx * H + y0 - PAD) * W + x0 - PAD) * Cin) * 4;
         const int ybase = (((n * H + y0) * W + x0) * Cout) * 4;
 #pragma unroll
         for (int sl = 0; sl < C::XSLOTS; ++sl) {
             const int idx = tid + sl * 256;
             const int pix = idx / C::QPP, q = idx % C::QPP;
             const int py = pix / C::HALO_W, px = pix % C::HALO_W;
-            const bool inb = idx < C::XITEMS && (unsigned)(y0 - PAD + py) < (unsigned)H &&
+            const bool inb = depth_ok && idx < C::XITEMS && (unsigned)(y0 - PAD + py) < (unsigned)H &&
                              (unsigned)(x0 - PAD + px) < (unsigned)W;
             const unsigned off = inb ? (unsigned)(xbase + ((py * W + px) * Cin + ci0 + q * 4) * 4) : OOB;
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, off, 0, 0);
@@ -207,44 +238,46 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_f32_kernel(
     for (int i = tid; i < C::RED_FLOATS; i += 256) out[i] = red[i];
 }
 
-// factor the finish kernel applies to dW (not db): set by sq_conv2d_nhwc_wgrad_scaled_f32 around its dispatch
-thread_local float t_dw_scale_f32 = 1.0f;
-
-// second stage: dW[tap][ci][co] = sum_b partials[b][pair][tap*16 + ci%16][co%BN], b ascending
-template <int BN, int KS, int KC>
+// second stage: dW[kd][tap][ci][co] = sum_b partials[b][pair(kd, ci, co)][tap*16 + ci%KC][co%BN], b ascending, times
+// dw_scale (dW only, not db); db[co] from the pairs (centre depth tap, ci chunk 0)
+template <int BN, int KS, int KC, int DT>
 __global__ __launch_bounds__(256) void conv_wgrad_finish_kernel(const float *__restrict__ partials,
                                                                  float *__restrict__ dw, float *__restrict__ db,
                                                                  int nblk, int Cin, int Cout, int G, float dw_scale) {
     using C = WCfg<BN, KS, KC>;
-    const int nco = (Cout + BN - 1) / BN, npairs = (Cin / KC) * nco;
-    const int total = C::NTAP * Cin * Cout;
+    const int nco = (Cout + BN - 1) / BN, nci = Cin / KC, npairs = DT * nci * nco;
+    const int total = DT * C::NTAP * Cin * Cout;
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int i = t / G, g = t % G;
     const size_t stride = (size_t)npairs * C::RED_FLOATS;
     if (i < total) {
-        const int co = i % Cout, ci = (i / Cout) % Cin, tap = i / (Cout * Cin);
-        const int pair = (ci / KC) * nco + co / BN;
+        const int co = i % Cout, ci = (i / Cout) % Cin;
+        int tap = i / (Cout * Cin), kd = 0;
+        if constexpr (DT > 1) kd = tap / C::NTAP, tap %= C::NTAP;
+        const int pair = (kd * nci + ci / KC) * nco + co / BN;
         const size_t off = (size_t)pair * C::RED_FLOATS + (tap * 16 + ci % KC) * BN + co % BN;
         const float s = sq_group_reduce(partials + off, stride, nblk, g, G);
         if (g == 0) dw[i] = dw_scale == 1.0f ? s : s * dw_scale;
     } else if (i < total + Cout) {
         const int co = i - total;
-        const size_t off = (size_t)(co / BN) * C::RED_FLOATS + (C::NTAP * 16) * BN + co % BN;
+        const int pair = (DT / 2) * nci * nco + co / BN;
+        const size_t off = (size_t)pair * C::RED_FLOATS + (C::NTAP * 16) * BN + co % BN;
         const float s = sq_group_reduce(partials + off, stride, nblk, g, G);
         if (g == 0 && db) db[co] = s;
     }
 }
 
-template <int BN, int KS, int KC>
-int launch(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int H, int W, int Cin,
-           int Cout, const int64_t *p, hipStream_t st) {
+// N planar images (N * D at DT = 3); `who` names the entry point in a launch error
+template <int BN, int KS, int KC, int DT>
+int launch(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int D, int H, int W, int Cin,
+           int Cout, const int64_t *p, float dw_scale, hipStream_t st, const char *who) {
     using C = WCfg<BN, KS, KC>;
     static bool attr_set = false;
-    auto kern = conv_wgrad_f32_kernel<BN, KS, KC>;
+    auto kern = conv_wgrad_f32_kernel<BN, KS, KC, DT>;
     if (!attr_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 C::LDS_BYTES) != hipSuccess) {
-            sq_set_error("conv_wgrad_f32: cannot reserve %d bytes of LDS", C::LDS_BYTES);
+            sq_set_error("%s: cannot reserve %d bytes of LDS", who, C::LDS_BYTES);
             return SQ_ELAUNCH;
         }
         attr_set = true;
@@ -252,19 +285,19 @@ int launch(const float *x, const float *dy, float *dw, float *db, float *ws, int
     const int gx = (int)p[SQ_WGP_GX], G = (int)p[SQ_WGP_G];
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     hipLaunchKernelGGL(kern, dim3(gx, (unsigned)p[SQ_WGP_NPAIRS]), dim3(256), C::LDS_BYTES, st, x, dy, ws, N, H, W, Cin, Cout,
-                       tiles_x, tiles_y, tiles_x * tiles_y * N, (int)p[SQ_WGP_TPB]);
-    int rc = sq_check_launch("sq_conv2d_nhwc_wgrad_f32");
+                       tiles_x, tiles_y, tiles_x * tiles_y * N, (int)p[SQ_WGP_TPB], D);
+    int rc = sq_check_launch(who);
     if (rc) return rc;
-    const int64_t total = ((int64_t)KS * KS * Cin * Cout + Cout) * G;
-    hipLaunchKernelGGL((conv_wgrad_finish_kernel<BN, KS, KC>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws,
-                       dw, db, gx, Cin, Cout, G, t_dw_scale_f32);
-    return sq_check_launch("sq_conv2d_nhwc_wgrad_f32(finish)");
+    const int64_t total = ((int64_t)DT * KS * KS * Cin * Cout + Cout) * G;
+    hipLaunchKernelGGL((conv_wgrad_finish_kernel<BN, KS, KC, DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       ws, dw, db, gx, Cin, Cout, G, dw_scale);
+    return sq_check_launch(who);
 }
 
 int launch_dispatch(const float *x, const float *dy, float *dw, float *db, float *ws, int N, int H, int W,
-                    int Cin, int Cout, int K, const int64_t *p, hipStream_t st) {
+                    int Cin, int Cout, int K, const int64_t *p, float dw_scale, hipStream_t st) {
     const int KC = (int)p[SQ_WGP_NI], BN = (int)p[SQ_WGP_NO];
-#define SQ_W32(BN_, KS_, KC_) if (BN == BN_ && K == KS_ && KC == KC_) return launch<BN_, KS_, KC_>(x, dy, dw, db, ws, N, H, W, Cin, Cout, p, st);
+#define SQ_W32(BN_, KS_, KC_) if (BN == BN_ && K == KS_ && KC == KC_) return launch<BN_, KS_, KC_, 1>(x, dy, dw, db, ws, N, 1, H, W, Cin, Cout, p, dw_scale, st, "sq_conv2d_nhwc_wgrad_f32");
     SQ_W32(32, 3, 16) SQ_W32(16, 3, 16) SQ_W32(32, 1, 16) SQ_W32(16, 1, 16)
     SQ_W32(32, 3, 8) SQ_W32(16, 3, 8) SQ_W32(32, 1, 8) SQ_W32(16, 1, 8)
 #undef SQ_W32
@@ -272,15 +305,16 @@ int launch_dispatch(const float *x, const float *dy, float *dw, float *db, float
     return SQ_EINVAL;
 }
 
-// ---- first layer (Cin = 1..7, 3x3): the 9 taps ride the 16 MFMA rows, one accumulator per input channel ------
-//   A[i = tap][k = pixel] = X[pixel + tap][c] (rows 9..15 zero), B[k][j = co] = dY[pixel][co]
-// partials: [gridDim.x][9*CIN + 1][Cout]  (row tap*CIN + c as in dW, then the bias row); blockIdx.y = 16-channel co group.
-template <typename TY, int CIN>
+// ---- first layer (Cin = 1..7, 3x3): the 9 in-plane taps ride the 16 MFMA rows, one accumulator per STACKED channel ----
+//   A[i = tap][k = pixel] = X[slice n + kd - DT/2][pixel + tap][c] (rows 9..15 zero), B[k][j = co] = dY[slice n][pixel][co]
+// partials: [gridDim.x][9*CS + 1][Cout], CS = DT*CIN stacked channels, row tap*CS + kd*CIN + c (at DT = 1: tap*CIN + c as
+// in dW), then the bias row; blockIdx.y = 16-channel co group.  N counts planar images, D slices per volume.
+template <typename TY, int CIN, int DT>
 __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
     const float *__restrict__ x, const TY *__restrict__ dy, float *__restrict__ partials, int N, int H, int W,
-    int Cout, int tiles_x, int tiles_y, int ntiles, int tiles_per_block) {
-    constexpr int HW = TW + 2, ROWS = 9 * CIN + 1;
-    __shared__ float xs[HW * HW * CIN + 8];
+    int Cout, int tiles_x, int tiles_y, int ntiles, int tiles_per_block, int D) {
+    constexpr int CS = DT * CIN, HW = TW + 2, HPC = HW * HW * CIN, ROWS = 9 * CS + 1;
+    __shared__ float xs[DT * HPC + 8];                         // [kd][halo pixel][c]
     __shared__ __attribute__((aligned(16))) float ys[TH * TW * 16];
     __shared__ float red[4][ROWS * 16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -289,13 +323,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
     const int t_begin = blockIdx.x * tiles_per_block, t_end = min(t_begin + tiles_per_block, ntiles);
     const int ky = li / 3, kx = li % 3;
     const bool live_row = li < 9;
-    f32x4 acc[CIN];
+    f32x4 acc[CS];
 #pragma unroll
-    for (int c = 0; c < CIN; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < CS; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float bsum = 0.f;
     // register double buffer: the next tile's loads are in flight while this one is multiplied (the kernel used to
     // load, wait, compute, and hid the HBM latency only through resident blocks)
-    constexpr int XSL = (HW * HW * CIN + 255) / 256;            // halo items (one float) per thread
+    constexpr int XSL = (DT * HPC + 255) / 256;                 // halo items (one float) per thread
     constexpr int YV = sizeof(TY) == 4 ? 4 : 2;                 // 16-byte pieces of dY per thread: 256 px x 16 ch
     float xr[XSL];
     uint4 yr[YV];
@@ -305,10 +339,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
 #pragma unroll
         for (int sl = 0; sl < XSL; ++sl) {
             const int idx = tid + sl * 256;
-            const int pix = idx / CIN, c = idx % CIN;
+            const int kd = DT == 1 ? 0 : idx / HPC, r = idx - kd * HPC;
+            const int pix = r / CIN, c = r % CIN;
             const int gy = y0 - 1 + pix / HW, gx = x0 - 1 + pix % HW;
-            xr[sl] = (idx < HW * HW * CIN && gy >= 0 && gy < H && gx >= 0 && gx < W)
-                         ? x[(((size_t)n * H + gy) * W + gx) * CIN + c] : 0.f;
+            bool depth_ok = true;                               // slice n + kd - DT/2 of the same volume, else the
+            if constexpr (DT > 1) depth_ok = (unsigned)(n % D + kd - DT / 2) < (unsigned)D;   // depth border's zeros
+            xr[sl] = (idx < DT * HPC && depth_ok && gy >= 0 && gy < H && gx >= 0 && gx < W)
+                         ? x[(((size_t)(n + kd - DT / 2) * H + gy) * W + gx) * CIN + c] : 0.f;
         }
 #pragma unroll
         for (int v = 0; v < YV; ++v) {
@@ -327,7 +364,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
     auto commit = [&]() {
 #pragma unroll
         for (int sl = 0; sl < XSL; ++sl)
-            if (tid + sl * 256 < HW * HW * CIN) xs[tid + sl * 256] = xr[sl];
+            if (tid + sl * 256 < DT * HPC) xs[tid + sl * 256] = xr[sl];
 #pragma unroll
         for (int v = 0; v < YV; ++v) {
             const int idx = tid + v * 256;
@@ -354,9 +391,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
             bsum += b;
             const float *xp = xs + ((r + ky) * HW + 4 * g + kk + kx) * CIN;
 #pragma unroll
-            for (int c = 0; c < CIN; ++c) {
-                const float a = live_row ? xp[c] : 0.f;
-                acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[c], 0, 0, 0);
+            for (int sc = 0; sc < CS; ++sc) {
+                const float a = live_row ? xp[(sc / CIN) * HPC + sc % CIN] : 0.f;
+                acc[sc] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[sc], 0, 0, 0);
             }
         }
         __syncthreads();
@@ -365,11 +402,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
     bsum += __shfl_xor(bsum, 32);
     // D: rows (taps) 4*kk + j, column (co) li
 #pragma unroll
-    for (int c = 0; c < CIN; ++c)
+    for (int sc = 0; sc < CS; ++sc)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (4 * kk + j < 9) red[wv][((4 * kk + j) * CIN + c) * 16 + li] = acc[c][j];
-    if (kk == 0) red[wv][9 * CIN * 16 + li] = bsum;
+            if (4 * kk + j < 9) red[wv][((4 * kk + j) * CS + sc) * 16 + li] = acc[sc][j];
+    if (kk == 0) red[wv][9 * CS * 16 + li] = bsum;
     __syncthreads();
     for (int t = tid; t < ROWS * 16; t += 256) {
         const int row = t / 16, c = t % 16;
@@ -379,28 +416,42 @@ __global__ __launch_bounds__(256) void conv_wgrad_cin1_f32_kernel(
     }
 }
 
-// rows = 9*Cin + 1
+// rows = 9*DT*Cin + 1; row tap*(DT*Cin) + kd*Cin + c -> dW[kd][tap][c][co], which at DT = 1 is the row order itself
+template <int DT>
 __global__ __launch_bounds__(256) void conv_wgrad_cin1_finish_kernel(const float *__restrict__ partials,
                                                                       float *__restrict__ dw, float *__restrict__ db,
-                                                                      int nblk, int Cout, int G, int rows) {
+                                                                      int nblk, int Cin, int Cout, int G) {
+    const int CS = DT * Cin, rows = 9 * CS + 1;
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int i = t / G, g = t % G;
     if (i >= rows * Cout) return;
     const float s = sq_group_reduce(partials + i, (size_t)rows * Cout, nblk, g, G);
     if (g != 0) return;
-    if (i < (rows - 1) * Cout) dw[i] = s;
-    else if (db) db[i - (rows - 1) * Cout] = s;
+    if (i >= (rows - 1) * Cout) {
+        if (db) db[i - (rows - 1) * Cout] = s;
+    } else if constexpr (DT == 1) {
+        dw[i] = s;
+    } else {
+        const int row = i / Cout, co = i % Cout;
+        const int tap = row / CS, kd = (row % CS) / Cin, c = row % Cin;
+        dw[((kd * 9 + tap) * Cin + c) * Cout + co] = s;
+    }
 }
 
-int cin1_grid(int N, int H, int W, int *tpb_out) {
-    const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
-    // the kernel is single-buffered (load, barrier, 16 MFMAs, barrier): it hides latency only through resident blocks,
-    // so the grid fills the block slots of every CU (2048 blocks: -0.5 % on the bf16 step vs 1024, within noise of 4096)
-    static const int target = [] { const char *e = getenv("SQ_CIN1_BLOCKS"); return e ? atoi(e) : 2048; }();
-    int tpb = (ntiles + target - 1) / target;
-    if (tpb < 1) tpb = 1;
-    if (tpb_out) *tpb_out = tpb;
-    return (ntiles + tpb - 1) / tpb;
+// The grid arithmetic of every plan: npairs block columns (blockIdx.y) of gx persistent blocks, each walking tpb of the
+// ntiles 16x16 tiles and leaving one partial of `rows` rows: [rows][bn] per pair (MFMA kernels), [rows][Cout] per block
+// (small-Cin kernel).
+void fill_plan(int64_t *out, int K, int kc, int bn, int kind, int ntiles, int npairs, int rows, int Cout) {
+    // the small-Cin kernel hides latency only through resident blocks, so its grid fills the block slots of every CU
+    // (2048 blocks: -0.5 % on the bf16 step vs 1024, within noise of 4096)
+    static const int cin1_blocks = [] { const char *e = getenv("SQ_CIN1_BLOCKS"); return e ? atoi(e) : 2048; }();
+    int want = kind == SQ_WGP_F32_SMALL ? cin1_blocks : (512 + npairs - 1) / npairs;   // MFMA: ~2 resident blocks per CU overall
+    if (want < 1) want = 1;
+    const int tpb = (ntiles + want - 1) / want;
+    const int gx = (ntiles + tpb - 1) / tpb;
+    const int64_t wsf = (int64_t)gx * rows * (kind == SQ_WGP_F32_SMALL ? Cout : npairs * bn);
+    const int64_t v[SQ_WGP_N] = {K, kc, bn, kind, 1, npairs, gx, tpb, sq_group_size(gx), wsf};
+    for (int i = 0; i < SQ_WGP_N; ++i) out[i] = v[i];
 }
 
 bool shape_ok(int N, int H, int W, int Cin, int Cout, int K) {
@@ -409,57 +460,61 @@ bool shape_ok(int N, int H, int W, int Cin, int Cout, int K) {
            Cout > 0 && Cout % 4 == 0 && (size_t)N * H * W * (size_t)(Cin > Cout ? Cin : Cout) * 4 < ((size_t)1 << 31);
 }
 
-template <typename TY>
-int launch_cin_small(const float *x, const TY *dy, float *dw, float *db, float *workspace, int N, int H, int W, int Cin,
-                     int Cout, hipStream_t st, const char *who) {
-    int64_t p[SQ_WGP_N];
-    SQ_REQUIRE(sq_wgrad_f32_plan(N, H, W, Cin, Cout, 3, p) == SQ_OK && p[SQ_WGP_KIND] == SQ_WGP_F32_SMALL, "%s: Cin=%d unsupported (1..7)", who, Cin);
-    const int gx = (int)p[SQ_WGP_GX], tpb = (int)p[SQ_WGP_TPB];
-    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
-    const dim3 grid(gx, (Cout + 15) / 16);
-#define SQ_CIN_SMALL(C)                                                                                              \
-    case C:                                                                                                          \
-        hipLaunchKernelGGL((conv_wgrad_cin1_f32_kernel<TY, C>), grid, dim3(256), 0, st, x, dy, workspace, N, H, W,   \
-                           Cout, tiles_x, tiles_y, tiles_x * tiles_y * N, tpb);                                      \
-        break;
-    switch (Cin) {
-        SQ_CIN_SMALL(1) SQ_CIN_SMALL(2) SQ_CIN_SMALL(3) SQ_CIN_SMALL(4) SQ_CIN_SMALL(5) SQ_CIN_SMALL(6) SQ_CIN_SMALL(7)
-    default: sq_set_error("%s: Cin=%d unsupported (1..7)", who, Cin); return SQ_EINVAL;
-    }
+// p: a plan of kind SQ_WGP_F32_SMALL for N planar images (N * D at DT = 3: Cin 1 and 2 only)
+template <typename TY, int DT>
+int launch_cin_small(const float *x, const TY *dy, float *dw, float *db, float *workspace, int N, int D, int H, int W,
+                     int Cin, int Cout, const int64_t *p, hipStream_t st, const char *who) {
+    constexpr int MAXC = DT == 1 ? 7 : 2;
+    void (*kern)(const float *, const TY *, float *, int, int, int, int, int, int, int, int, int) = nullptr;
+#define SQ_CIN_SMALL(C) if constexpr (C <= MAXC) if (Cin == C) kern = conv_wgrad_cin1_f32_kernel<TY, C, DT>;
+    SQ_CIN_SMALL(1) SQ_CIN_SMALL(2) SQ_CIN_SMALL(3) SQ_CIN_SMALL(4) SQ_CIN_SMALL(5) SQ_CIN_SMALL(6) SQ_CIN_SMALL(7)
 #undef SQ_CIN_SMALL
+    SQ_REQUIRE(kern && p[SQ_WGP_KIND] == SQ_WGP_F32_SMALL, "%s: Cin=%d unsupported (1..%d)", who, Cin, MAXC);
+    const int gx = (int)p[SQ_WGP_GX], G = (int)p[SQ_WGP_G];
+    const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
+    hipLaunchKernelGGL(kern, dim3(gx, (Cout + 15) / 16), dim3(256), 0, st, x, dy, workspace, N, H, W, Cout, tiles_x, tiles_y,
+                       tiles_x * tiles_y * N, (int)p[SQ_WGP_TPB], D);
     int rc = sq_check_launch(who);
     if (rc) return rc;
-    const int G = (int)p[SQ_WGP_G], rows = 9 * Cin + 1;
-    hipLaunchKernelGGL(conv_wgrad_cin1_finish_kernel, dim3((rows * Cout * G + 255) / 256), dim3(256), 0, st, workspace, dw,
-                       db, gx, Cout, G, rows);
+    const int rows = 9 * DT * Cin + 1;
+    hipLaunchKernelGGL(conv_wgrad_cin1_finish_kernel<DT>, dim3((rows * Cout * G + 255) / 256), dim3(256), 0, st, workspace,
+                       dw, db, gx, Cin, Cout, G);
     return sq_check_launch(who);
 }
 
 }  // namespace
 
-// the plan of a call (sq_wgrad_plan, family SQ_PLAN_F32): out[SQ_WGP_N]
+// ---- launch plans (host only; the launchers and the workspace queries take their choices from here) -------------------
+// the plan of a planar call (sq_wgrad_plan, family SQ_PLAN_F32): out[SQ_WGP_N]
 int sq_wgrad_f32_plan(int N, int H, int W, int Cin, int Cout, int K, int64_t *out) {
     if (!shape_ok(N, H, W, Cin, Cout, K)) return SQ_EINVAL;
-    int gx, tpb, npairs, kc, bn;
-    int64_t wsf;
+    const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
     if (Cin <= 7) {                                             // the small-Cin kernel: 16-channel co groups, one input chunk
-        gx = cin1_grid(N, H, W, &tpb);
-        kc = Cin, bn = 16, npairs = (Cout + 15) / 16;
-        wsf = (int64_t)gx * (9 * Cin + 1) * Cout;
+        fill_plan(out, K, Cin, 16, SQ_WGP_F32_SMALL, ntiles, (Cout + 15) / 16, 9 * Cin + 1, Cout);
     } else {
-        kc = Cin % 16 == 0 ? 16 : 8;
-        bn = Cout > 16 ? 32 : 16;
-        const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N;
-        npairs = (Cin / kc) * ((Cout + bn - 1) / bn);
-        int want = (512 + npairs - 1) / npairs;                 // ~2 resident blocks per CU overall
-        if (want < 1) want = 1;
-        tpb = (ntiles + want - 1) / want;
-        if (tpb < 1) tpb = 1;
-        gx = (ntiles + tpb - 1) / tpb;
-        wsf = (int64_t)gx * npairs * (K * K * 16 + 1) * bn;    // WCfg<>::RED_FLOATS per pair
+        const int kc = Cin % 16 == 0 ? 16 : 8, bn = Cout > 16 ? 32 : 16;
+        fill_plan(out, K, kc, bn, SQ_WGP_F32, ntiles, (Cin / kc) * ((Cout + bn - 1) / bn), K * K * 16 + 1, Cout);   // WCfg<>::ROWS
     }
-    const int64_t v[SQ_WGP_N] = {K, kc, bn, Cin <= 7 ? SQ_WGP_F32_SMALL : SQ_WGP_F32, 1, npairs, gx, tpb, sq_group_size(gx), wsf};
-    for (int i = 0; i < SQ_WGP_N; ++i) out[i] = v[i];
+    return SQ_OK;
+}
+
+extern "C" int sq_conv3d_wgrad_plan(int N, int D, int H, int W, int Cin, int Cout, int64_t *out) {
+    SQ_REQUIRE(out, "sq_conv3d_wgrad_plan: null out");
+    SQ_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "sq_conv3d_wgrad_plan: bad shape");
+    SQ_REQUIRE(Cin == 1 || Cin == 2 || Cin % 16 == 0,
+               "sq_conv3d_wgrad_plan: Cin=%d unsupported (1, 2 or a multiple of 16, as the forward)", Cin);
+    SQ_REQUIRE(Cout % 4 == 0, "sq_conv3d_wgrad_plan: Cout=%d must be a multiple of 4", Cout);
+    const int64_t cmax = Cin > Cout ? Cin : Cout;
+    const int64_t bytes = (int64_t)N * D * H * W * cmax * 4;
+    SQ_REQUIRE(bytes < LIM32, "sq_conv3d_wgrad_plan: a tensor of %lld bytes; the gradient kernels address whole tensors "
+               "with 32-bit offsets (< 2 GiB)", (long long)bytes);
+    const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH) * N * D;
+    if (Cin <= 2) {                                             // the small-Cin kernel: 16-channel co groups, one stacked chunk
+        fill_plan(out, 3, 3 * Cin, 16, SQ_WGP_F32_SMALL, ntiles, (Cout + 15) / 16, 27 * Cin + 1, Cout);
+    } else {                                                    // pair = (depth tap, ci chunk, co chunk)
+        const int bn = Cout > 16 ? 32 : 16;
+        fill_plan(out, 3, 16, bn, SQ_WGP_F32, ntiles, 3 * (Cin / 16) * ((Cout + bn - 1) / bn), 9 * 16 + 1, Cout);
+    }
     return SQ_OK;
 }
 
@@ -468,20 +523,9 @@ extern "C" int64_t sq_conv2d_nhwc_wgrad_workspace_f32(int N, int H, int W, int C
     return sq_wgrad_f32_plan(N, H, W, Cin, Cout, K, p) == SQ_OK ? p[SQ_WGP_WS] * 4 : -1;
 }
 
-extern "C" int sq_conv2d_nhwc_wgrad_f32(const float *x, const float *dy, float *dw, float *db,
-                                        float *workspace, int N, int H, int W, int Cin, int Cout, int K,
-                                        void *stream) {
-    SQ_REQUIRE(x && dy && dw && workspace, "sq_conv2d_nhwc_wgrad_f32: null pointer");
-    SQ_REQUIRE(shape_ok(N, H, W, Cin, Cout, K),
-               "sq_conv2d_nhwc_wgrad_f32: unsupported shape N=%d H=%d W=%d Cin=%d Cout=%d K=%d "
-               "(Cin 1..7 with K 3, 8 or %%16; Cout %%4; K 1|3; tensors < 2 GiB)", N, H, W, Cin, Cout, K);
-    SQ_REQUIRE_ALIGNED(x); SQ_REQUIRE_ALIGNED(dy); SQ_REQUIRE_ALIGNED(workspace);
-    if (Cin <= 7)
-        return launch_cin_small<float>(x, dy, dw, db, workspace, N, H, W, Cin, Cout, reinterpret_cast<hipStream_t>(stream),
-                                       "sq_conv2d_nhwc_wgrad_f32(small Cin)");
+extern "C" int64_t sq_conv3d_ndhwc_wgrad_workspace_f32(int N, int D, int H, int W, int Cin, int Cout) {
     int64_t p[SQ_WGP_N];
-    sq_wgrad_f32_plan(N, H, W, Cin, Cout, K, p);
-    return launch_dispatch(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, p, reinterpret_cast<hipStream_t>(stream));
+    return sq_conv3d_wgrad_plan(N, D, H, W, Cin, Cout, p) == SQ_OK ? p[SQ_WGP_WS] * 4 : -1;
 }
 
 // dW multiplied by dw_scale in the finish kernel (MFMA kernels: Cin 8 or a multiple of 16; the small-Cin kernel has no
@@ -489,10 +533,39 @@ extern "C" int sq_conv2d_nhwc_wgrad_f32(const float *x, const float *dy, float *
 extern "C" int sq_conv2d_nhwc_wgrad_scaled_f32(const float *x, const float *dy, float *dw, float *db, float *workspace,
                                                int N, int H, int W, int Cin, int Cout, int K, float dw_scale, void *stream) {
     SQ_REQUIRE(Cin > 7 || dw_scale == 1.0f, "sq_conv2d_nhwc_wgrad_scaled_f32: Cin=%d has no scaled form", Cin);
-    t_dw_scale_f32 = dw_scale;
-    const int rc = sq_conv2d_nhwc_wgrad_f32(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, stream);
-    t_dw_scale_f32 = 1.0f;
-    return rc;
+    SQ_REQUIRE(x && dy && dw && workspace, "sq_conv2d_nhwc_wgrad_f32: null pointer");
+    SQ_REQUIRE(shape_ok(N, H, W, Cin, Cout, K),
+               "sq_conv2d_nhwc_wgrad_f32: unsupported shape N=%d H=%d W=%d Cin=%d Cout=%d K=%d "
+               "(Cin 1..7 with K 3, 8 or %%16; Cout %%4; K 1|3; tensors < 2 GiB)", N, H, W, Cin, Cout, K);
+    SQ_REQUIRE_ALIGNED(x); SQ_REQUIRE_ALIGNED(dy); SQ_REQUIRE_ALIGNED(workspace);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int64_t p[SQ_WGP_N];
+    sq_wgrad_f32_plan(N, H, W, Cin, Cout, K, p);
+    if (Cin <= 7)
+        return launch_cin_small<float, 1>(x, dy, dw, db, workspace, N, 1, H, W, Cin, Cout, p, st,
+                                          "sq_conv2d_nhwc_wgrad_f32(small Cin)");
+    return launch_dispatch(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, p, dw_scale, st);
+}
+
+extern "C" int sq_conv2d_nhwc_wgrad_f32(const float *x, const float *dy, float *dw, float *db,
+                                        float *workspace, int N, int H, int W, int Cin, int Cout, int K,
+                                        void *stream) {
+    return sq_conv2d_nhwc_wgrad_scaled_f32(x, dy, dw, db, workspace, N, H, W, Cin, Cout, K, 1.0f, stream);
+}
+
+extern "C" int sq_conv3d_ndhwc_wgrad_f32(const float *x, const float *dy, float *dw, float *db, float *workspace, int N,
+                                         int D, int H, int W, int Cin, int Cout, void *stream) {
+    SQ_REQUIRE(x && dy && dw && workspace, "sq_conv3d_ndhwc_wgrad_f32: null pointer");
+    int64_t p[SQ_WGP_N];
+    const int rc = sq_conv3d_wgrad_plan(N, D, H, W, Cin, Cout, p);
+    if (rc != SQ_OK) return rc;
+    SQ_REQUIRE_ALIGNED(x); SQ_REQUIRE_ALIGNED(dy); SQ_REQUIRE_ALIGNED(workspace);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const char *who = "sq_conv3d_ndhwc_wgrad_f32";
+    if (p[SQ_WGP_KIND] == SQ_WGP_F32_SMALL)
+        return launch_cin_small<float, 3>(x, dy, dw, db, workspace, N * D, D, H, W, Cin, Cout, p, st, who);
+    return p[SQ_WGP_NO] == 32 ? launch<32, 3, 16, 3>(x, dy, dw, db, workspace, N * D, D, H, W, Cin, Cout, p, 1.0f, st, who)
+                              : launch<16, 3, 16, 3>(x, dy, dw, db, workspace, N * D, D, H, W, Cin, Cout, p, 1.0f, st, who);
 }
 
 // first-layer weight gradient with a bf16 dY (the bf16 training graph): same MFMA-over-taps kernel
@@ -504,8 +577,10 @@ extern "C" int64_t sq_conv3x3_first_wgrad_workspace_bf16(int N, int H, int W, in
 
 extern "C" int sq_conv3x3_first_wgrad_bf16(const float *x, const void *dy, float *dw, float *db, float *workspace,
                                            int N, int H, int W, int Cin, int Cout, void *stream) {
-    SQ_REQUIRE(x && dy && dw && workspace && N > 0 && H > 0 && W > 0 && Cin >= 1 && Cin <= 7 && Cout > 0 && Cout % 4 == 0,
+    int64_t p[SQ_WGP_N];
+    SQ_REQUIRE(x && dy && dw && workspace && N > 0 && H > 0 && W > 0 && Cin >= 1 && Cin <= 7 && Cout > 0 && Cout % 4 == 0 &&
+               sq_wgrad_f32_plan(N, H, W, Cin, Cout, 3, p) == SQ_OK,
                "sq_conv3x3_first_wgrad_bf16: bad arguments (Cin 1..7, Cout %% 4 == 0)");
-    return launch_cin_small<__bf16>(x, reinterpret_cast<const __bf16 *>(dy), dw, db, workspace, N, H, W, Cin, Cout,
-                                    reinterpret_cast<hipStream_t>(stream), "sq_conv3x3_first_wgrad_bf16");
+    return launch_cin_small<__bf16, 1>(x, reinterpret_cast<const __bf16 *>(dy), dw, db, workspace, N, 1, H, W, Cin, Cout, p,
+                                       reinterpret_cast<hipStream_t>(stream), "sq_conv3x3_first_wgrad_bf16");
 }

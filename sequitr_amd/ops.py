@@ -714,9 +714,6 @@ def conv2d_wgrad(x, dy, K, want_bias=True, dw_out=None, db_out=None, dw_scale=1.
     _lib.check(fn(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), N, H, W, Cin, Cout, K, float(dw_scale), _stream()),
                "sq_conv2d_nhwc_wgrad_scaled_mixed_f32" if mixed else "sq_conv2d_nhwc_wgrad_scaled_f32")
     return dw, db
-    _lib.check(lib.sq_conv2d_nhwc_wgrad_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), N, H, W, Cin, Cout,
-                                           K, _stream()), "sq_conv2d_nhwc_wgrad_f32")
-    return dw, db
 
 
 def act_bwd(dy, y, act):
