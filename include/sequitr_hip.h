@@ -603,6 +603,23 @@ int sq_edt_sq_f32(const float *img, int32_t *d2, void *workspace, int N, int H, 
 int sq_weightmap_edt_f32(const float *img, double *out64, float *out32, void *workspace, int N, int H, int W,
                          double w0, double sigma, void *stream);
 
+/* Volumetric EDT weight maps: ImageWeightMap.pipe, sequitr/pipeline.py:475-479, called on a (Z, X, Y) array, where
+ * distance_transform_edt is the true 3-D Euclidean transform; dz = the depth spacing in in-plane pixels, scipy's
+ * sampling = (dz, 1, 1).  img (N,D,H,W) f32 binary label volumes (a voxel is a feature iff 1 - image == 0), one map
+ * per volume: the search never crosses from volume n into n +- 1.  0 < D, H, W < 30000, N*D*H*W < 2^31, dz finite
+ * and > 0; workspace: sq_weightmap3d_workspace bytes (-1: the request is out of range), 16-B aligned.
+ *   D3(n,z,x,y) = min over z' of A(z - z') + P(n,z',x,y), A(k) = fl(fl(k dz) fl(k dz)) in double, P = the exact planar
+ *   squared distance of slice z' (infinite for a slice without a feature); a volume without any feature reproduces
+ *   scipy's artefact, the distance to index (-1, 0, 0): D3 = fl(fl(((z+1) dz)^2 + x^2) + y^2).
+ *   sq_edt3d_sq_f64        : d2 (N,D,H,W) f64 = D3 (for dz == 1 an exact integer)
+ *   sq_weightmap3d_edt_f32 : d = sqrt(D3); out = w0*(1-image)*exp(-(d*d)/(2 sigma^2 + 1e-99)) + image + 1 in float64,
+ *                            written to out64 (N,D,H,W) and / or rounded once to out32, the `weights` tensor of the loss
+ * SQ_EDT3D_LDS=0 (read per launch) runs the depth pass on global memory instead of LDS: the same result, bit for bit. */
+int64_t sq_weightmap3d_workspace(int N, int D, int H, int W);
+int sq_edt3d_sq_f64(const float *img, double *d2, void *workspace, int N, int D, int H, int W, double dz, void *stream);
+int sq_weightmap3d_edt_f32(const float *img, double *out64, float *out32, void *workspace, int N, int D, int H, int W,
+                           double w0, double sigma, double dz, void *stream);
+
 /* ImageWeightMap2 (sequitr/pipeline.py:482-571), the per-pixel part on the device: `simplices` (nsimp,7) int32 rows
  * {tile, x0, y0, x1, y1, x2, y2} (x = row, y = column, as np.where orders them) and `longest` (nsimp) float64 = the
  * longest edge of each simplex, from scipy.spatial.Delaunay of the boundary points (host); img (N,H,W) binary f32.

@@ -69,7 +69,11 @@ __global__ __launch_bounds__(256) void edt_rows_kernel(const float *__restrict__
     if (any && lane == 0) atomicOr(&has_feature[r / H], 1);
 }
 
-template <bool WANT_D2>
+// INF_EMPTY (the planar half of the volumetric transform below): an image without any feature reports P_INF instead of
+// scipy's per-image artefact -- inside a volume it is a slice that contributes nothing to the minimum over depth
+constexpr int P_INF = 0x7fffffff;
+
+template <bool WANT_D2, bool INF_EMPTY = false>
 __global__ __launch_bounds__(256) void edt_cols_weight_kernel(const float *__restrict__ img,
                                                               const unsigned short *__restrict__ g,
                                                               const int *__restrict__ has_feature,
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(256) void edt_cols_weight_kernel(const float *__res
         if (!has_feature[n]) {
             // scipy's feature transform with no background pixel at all points every pixel at index
             // (-1, 0): reproduce the artefact rather than invent a value
-            best = (y + 1) * (y + 1) + x * x;
+            best = INF_EMPTY ? P_INF : (y + 1) * (y + 1) + x * x;
         } else {
             const int g0 = gc[(size_t)y * W];
             best = g0 * g0;
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(256) void edt_rows_v2_kernel(const float *__restric
 // in this image" is a block-local fact: every row with a feature has a finite g in every column.
 constexpr int CS = 32, RSPLIT = 8;                           // RSPLIT blocks share a strip, each maps H / RSPLIT of its rows (the
                                                               // strip is re-read from L2 by each: parallelism over bytes)
-template <bool WANT_D2>
+template <bool WANT_D2, bool INF_EMPTY = false>
 __global__ __launch_bounds__(256) void edt_cols_weight_v2_kernel(const float *__restrict__ img,
                                                                  const unsigned short *__restrict__ g,
                                                                  double *__restrict__ out64, float *__restrict__ out32,
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(256) void edt_cols_weight_v2_kernel(const float *__
         if (x >= W) continue;
         int best;
         if (!has) {
-            best = (y + 1) * (y + 1) + x * x;                   // scipy's artefact for an image without background (see above)
+            best = INF_EMPTY ? P_INF : (y + 1) * (y + 1) + x * x;   // scipy's artefact for an image without background (see above)
         } else {
             // min over y' of g(y')^2 + (y - y')^2, searched outwards in blocks of 8 rows: a block is skipped when its nearest
             // row is already too far (and with it every block beyond) or when (nearest row)^2 + (its smallest g)^2 cannot
@@ -271,7 +275,7 @@ inline bool edt_v2_fits(int H, int W) {
     return on && W <= 64 * ROW_SEGS && H <= 2048;
 }
 
-template <bool WANT_D2>
+template <bool WANT_D2, bool INF_EMPTY = false>
 int edt_v2(const float *img, unsigned short *g, double *out64, float *out32, int *d2, int N, int H, int W, double w0,
            double denom, hipStream_t st, const char *who) {
     const int rows = N * H;
@@ -279,7 +283,7 @@ int edt_v2(const float *img, unsigned short *g, double *out64, float *out32, int
     int rc = sq_check_launch(who);
     if (rc) return rc;
     const int lds = (H + (H + 7) / 8) * CS * 2;
-    auto kern = edt_cols_weight_v2_kernel<WANT_D2>;
+    auto kern = edt_cols_weight_v2_kernel<WANT_D2, INF_EMPTY>;
     if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                lds) != hipSuccess) {
         sq_set_error("%s: cannot reserve %d bytes of LDS", who, lds);
@@ -353,6 +357,208 @@ extern "C" int sq_weightmap_edt_f32(const float *img, double *out64, float *out3
     hipLaunchKernelGGL(edt_cols_weight_kernel<false>, dim3(wm_grid((int64_t)N * H * W)), dim3(256), 0, st, img, g, flag,
                        out64, out32, (int *)nullptr, N, H, W, w0, denom);
     return sq_check_launch("sq_weightmap_edt_f32");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Volumetric maps: ImageWeightMap.pipe (sequitr/pipeline.py:475-479) on a (Z, X, Y) array, where scipy's transform is
+// the true 3-D Euclidean one, with scipy's sampling = (dz, 1, 1) for anisotropic stacks.  One more separable pass:
+//     D3(n,z,x,y) = min over z' of A(z - z') + P(n,z',x,y),      A(k) = fl(fl(k dz) fl(k dz))
+// P = the exact planar squared distance of slice z' (the two passes above over the N*D slices, INF_EMPTY: a slice
+// without a feature is P_INF and contributes nothing).  The combine runs in DOUBLE for every dz: P <= 2 * 30000^2 and
+// A(k) for dz = 1 are integers far below 2^53, so the sum is exact there, and P_INF becomes +infinity before it meets
+// any A -- nothing can wrap.  A is non-decreasing in k and P >= 0, so a side of the outward search is finished once
+// A(k) >= best; A is the same on both sides, so both finish at the same k.
+// P(n,z',x,y) is finite iff slice z' holds a feature, whatever (x,y): a minimum that is still infinite after the whole
+// depth means "no feature in volume n" -- a per-volume fact that needs no flag -- and scipy's feature transform then
+// points every voxel at index (-1, 0, 0).  The search never leaves the D slices of volume n.
+namespace {
+
+constexpr int CS3 = 32;                                       // columns (y, the contiguous axis) of a block's strip
+
+__device__ __forceinline__ double edt3d_p(int p) { return p == P_INF ? (double)INFINITY : (double)p; }
+
+// LOAD(z') -> P of slice z' at this (n, x, y)
+template <class LOAD>
+__device__ __forceinline__ double edt3d_search(LOAD load, int z, int x, int y, int D, double dz) {
+    double best = edt3d_p(load(z));
+    for (int k = 1; k < D; ++k) {
+        const int za = z - k, zb = z + k;
+        if (za < 0 && zb >= D) break;
+        const double t = (double)k * dz;
+        const double a = t * t;
+        if (a >= best) break;
+        if (za >= 0) {
+            const double c = a + edt3d_p(load(za));
+            best = c < best ? c : best;
+        }
+        if (zb < D) {
+            const double c = a + edt3d_p(load(zb));
+            best = c < best ? c : best;
+        }
+    }
+    if (best == (double)INFINITY) {
+        // no feature in the whole volume: scipy's index (-1, 0, 0), summed in axis order as np.add.reduce does
+        const double t = (double)(z + 1) * dz;
+        best = (t * t + (double)x * (double)x) + (double)y * (double)y;
+    }
+    return best;
+}
+
+template <bool WANT_D2>
+__device__ __forceinline__ void edt3d_store(const float *__restrict__ img, double *__restrict__ out64,
+                                            float *__restrict__ out32, double *__restrict__ d2out, size_t p, double best,
+                                            double w0, double denom) {
+    if (WANT_D2) {
+        d2out[p] = best;
+    } else {
+        const double image = (double)img[p];
+        const double bg = 1.0 - image;
+        const double d = sqrt(best);
+        const double v = w0 * bg * exp(-(d * d) / denom) + image + 1.0;       // the reference's expression, as above
+        if (out64) out64[p] = v;
+        if (out32) out32[p] = (float)v;
+    }
+}
+
+// depth pass + map, LDS form: a block owns the strip of CS3 columns of one (n, x) row with P of ALL D slices in LDS
+// (D x CS3 x 4 bytes); lanes run along y, so the fill reads coalesced row segments and the search runs on LDS
+template <bool WANT_D2>
+__global__ __launch_bounds__(256) void edt3d_depth_lds_kernel(const float *__restrict__ img, const int *__restrict__ P,
+                                                              double *__restrict__ out64, float *__restrict__ out32,
+                                                              double *__restrict__ d2out, int D, int H, int W, double dz,
+                                                              double w0, double denom) {
+    extern __shared__ __attribute__((aligned(16))) int ps[];                  // [D][CS3]
+    const int strips = (W + CS3 - 1) / CS3;
+    const int y0 = (int)(blockIdx.x % strips) * CS3, x = (int)((blockIdx.x / strips) % H);
+    const int n = (int)(blockIdx.x / ((unsigned)strips * H));
+    const size_t plane = (size_t)H * W;
+    const int *pv = P + (size_t)n * D * plane + (size_t)x * W;
+    for (int i = threadIdx.x; i < D * CS3; i += 256) {
+        const int z = i / CS3, y = y0 + i % CS3;
+        ps[i] = y < W ? pv[(size_t)z * plane + y] : P_INF;
+    }
+    __syncthreads();
+    const int yl = threadIdx.x % CS3, y = y0 + yl;
+    if (y >= W) return;
+    const int *pc = ps + yl;
+    for (int z = threadIdx.x / CS3; z < D; z += 256 / CS3) {
+        const double best = edt3d_search([&](int zz) { return pc[zz * CS3]; }, z, x, y, D, dz);
+        edt3d_store<WANT_D2>(img, out64, out32, d2out, ((size_t)n * D + z) * plane + (size_t)x * W + y, best, w0, denom);
+    }
+}
+
+// the same search on global memory, for depths whose strip does not fit in LDS (and SQ_EDT3D_LDS=0)
+template <bool WANT_D2>
+__global__ __launch_bounds__(256) void edt3d_depth_kernel(const float *__restrict__ img, const int *__restrict__ P,
+                                                          double *__restrict__ out64, float *__restrict__ out32,
+                                                          double *__restrict__ d2out, int N, int D, int H, int W, double dz,
+                                                          double w0, double denom) {
+    const int64_t plane = (int64_t)H * W, total = (int64_t)N * D * plane;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+        const int y = (int)(p % W), x = (int)((p / W) % H), z = (int)((p / plane) % D);
+        const int *pc = P + (p - (int64_t)z * plane);                         // slice 0 of this voxel's own volume
+        const double best = edt3d_search([&](int zz) { return pc[(int64_t)zz * plane]; }, z, x, y, D, dz);
+        edt3d_store<WANT_D2>(img, out64, out32, d2out, (size_t)p, best, w0, denom);
+    }
+}
+
+struct Edt3dWs {
+    int64_t flags, field, total;                                // bytes: the per-slice flags, then P (int32), then g (u16)
+};
+
+inline bool edt3d_layout(int N, int D, int H, int W, Edt3dWs *l) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || D >= G_INF || H >= G_INF || W >= G_INF) return false;
+    const int64_t vox = (int64_t)N * D * H * W;                 // < 2^31 * 30000: no overflow before the test
+    if ((int64_t)N * D >= ((int64_t)1 << 31) || vox >= ((int64_t)1 << 31)) return false;
+    l->flags = (((int64_t)N * D + 3) / 4) * 16;
+    l->field = ((vox * 4 + 15) / 16) * 16;
+    l->total = l->flags + l->field + vox * 2;
+    return true;
+}
+
+inline int edt3d_lds_limit() {
+    static const int limit = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
+            return 64 * 1024;
+        return v;
+    }();
+    return limit;
+}
+
+template <bool WANT_D2>
+int edt3d_run(const float *img, double *out64, float *out32, double *d2, void *workspace, int N, int D, int H, int W,
+              double w0, double denom, double dz, hipStream_t st, const char *who) {
+    SQ_REQUIRE(img && workspace, "%s: null pointer", who);
+    Edt3dWs l;
+    SQ_REQUIRE(edt3d_layout(N, D, H, W, &l), "%s: need 0 < D, H, W < %d and N*D*H*W < 2^31", who, G_INF);
+    SQ_REQUIRE(std::isfinite(dz) && dz > 0.0, "%s: the depth spacing must be finite and > 0", who);
+    SQ_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
+    char *base = reinterpret_cast<char *>(workspace);
+    int *flag = reinterpret_cast<int *>(base);
+    int *P = reinterpret_cast<int *>(base + l.flags);
+    unsigned short *g = reinterpret_cast<unsigned short *>(base + l.flags + l.field);
+    // planar half: the row and column passes over the N*D slices, featureless slices reported as P_INF
+    const int S = N * D;
+    int rc;
+    if (edt_v2_fits(H, W)) {
+        rc = edt_v2<true, true>(img, g, nullptr, nullptr, P, S, H, W, 0.0, 1.0, st, who);
+        if (rc) return rc;
+    } else {
+        if (hipMemsetAsync(flag, 0, sizeof(int) * (size_t)S, st) != hipSuccess) {
+            sq_set_error("%s: cannot clear the feature flags", who);
+            return SQ_ELAUNCH;
+        }
+        const int rows = S * H;
+        hipLaunchKernelGGL(edt_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, img, g, flag, rows, H, W);
+        rc = sq_check_launch(who);
+        if (rc) return rc;
+        hipLaunchKernelGGL((edt_cols_weight_kernel<true, true>), dim3(wm_grid((int64_t)S * H * W)), dim3(256), 0, st, img, g,
+                           flag, (double *)nullptr, (float *)nullptr, P, S, H, W, 0.0, 1.0);
+        rc = sq_check_launch(who);
+        if (rc) return rc;
+    }
+    // depth pass + map; SQ_EDT3D_LDS=0: A/B switch to the global-memory form, read per launch
+    const char *e = getenv("SQ_EDT3D_LDS");
+    const int64_t lds = (int64_t)D * CS3 * 4;
+    if (!(e && e[0] == '0') && lds <= edt3d_lds_limit()) {
+        auto kern = edt3d_depth_lds_kernel<WANT_D2>;
+        if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            sq_set_error("%s: cannot reserve %d bytes of LDS", who, (int)lds);
+            return SQ_ELAUNCH;
+        }
+        const int64_t blocks = (int64_t)N * H * ((W + CS3 - 1) / CS3);         // <= N*H*W < 2^31
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), (size_t)lds, st, img, P, out64, out32, d2, D, H, W, dz, w0,
+                           denom);
+    } else {
+        hipLaunchKernelGGL(edt3d_depth_kernel<WANT_D2>, dim3(wm_grid((int64_t)S * H * W)), dim3(256), 0, st, img, P, out64,
+                           out32, d2, N, D, H, W, dz, w0, denom);
+    }
+    return sq_check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int64_t sq_weightmap3d_workspace(int N, int D, int H, int W) {
+    Edt3dWs l;
+    return edt3d_layout(N, D, H, W, &l) ? l.total : -1;
+}
+
+extern "C" int sq_edt3d_sq_f64(const float *img, double *d2, void *workspace, int N, int D, int H, int W, double dz,
+                               void *stream) {
+    SQ_REQUIRE(d2, "sq_edt3d_sq_f64: null output");
+    return edt3d_run<true>(img, nullptr, nullptr, d2, workspace, N, D, H, W, 0.0, 1.0, dz, (hipStream_t)stream,
+                           "sq_edt3d_sq_f64");
+}
+
+extern "C" int sq_weightmap3d_edt_f32(const float *img, double *out64, float *out32, void *workspace, int N, int D, int H,
+                                      int W, double w0, double sigma, double dz, void *stream) {
+    SQ_REQUIRE(out64 || out32, "sq_weightmap3d_edt_f32: no output requested");
+    const double denom = 2.0 * (sigma * sigma) + 1e-99;         // 2.*self.sigma**2 + 1e-99
+    return edt3d_run<false>(img, out64, out32, nullptr, workspace, N, D, H, W, w0, denom, dz, (hipStream_t)stream,
+                            "sq_weightmap3d_edt_f32");
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -500,8 +500,11 @@ def SERVER_train_volume(params, options):
     """Train the volumetric U-Net (UNet3DTrain, f32) on a stack of volumes with the weighted softmax cross-entropy.
 
     params: images (.npy (N, slices, width, height[, C]) float), labels (.npy (N, slices, width, height) class indices,
-    or one-hot with a trailing class axis), weights (.npy, one value per voxel; absent: a uniform weight of 1 -- a
-    volumetric weight map is not computed here), the NetConfiguration keys (name, shape = (width, height, slices),
+    or one-hot with a trailing class axis), weights (.npy, one value per voxel; absent: what `weightmap` says),
+    weightmap ('uniform', the default: a weight of 1 everywhere | 'edt': ImageWeightMap(w0, sigma),
+    sequitr/pipeline.py:455-479, of the foreground volume -- the 3-D Euclidean transform with the depth axis scaled by
+    `spacing`, the slice spacing in in-plane pixels -- computed once on the GPU, sq_weightmap3d_edt_f32, and kept there),
+    w0 (10), sigma (5), spacing (1), the NetConfiguration keys (name, shape = (width, height, slices),
     num_outputs, learning_rate, num_epochs, dropout, filters, bridge, batch_norm, warm_start ...), batch_size (default
     1), warmup_steps.  Learning-rate defaults are the trainer's (train.DEFAULT_LEARNING_RATE ramped over
     train.DEFAULT_WARMUP_STEPS), as in SERVER_train.  options: gpu, max_steps.
@@ -517,6 +520,10 @@ def SERVER_train_volume(params, options):
 
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
         raise RuntimeError('SERVER_train_volume runs in a single process (data-parallel volume training does not exist)')
+    wm_kind = params.get('weightmap', 'uniform')
+    if wm_kind not in ('uniform', 'edt'):
+        raise ValueError("weightmap must be 'uniform' or 'edt', got %r" % (wm_kind,))
+    wm_w0, wm_sigma, wm_spacing = float(params.get('w0', 10.)), float(params.get('sigma', 5.)), float(params.get('spacing', 1.))
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
     dev = torch.device(device)
@@ -540,6 +547,9 @@ def SERVER_train_volume(params, options):
         raise ValueError('labels %s do not match the images %s' % (labels.shape, x.shape))
     if params.get('weights'):
         wmap = np.load(params['weights'], allow_pickle=False).reshape((N, Z, X, Y, 1)).astype(np.float32)
+    elif wm_kind == 'edt':                                     # volumetric EDT weight maps on the device, left in HBM
+        from .weightmap import device_weightmaps3d
+        wmap = device_weightmaps3d(onehot[..., 1:].sum(-1), wm_w0, wm_sigma, wm_spacing, device=device)
     else:
         wmap = np.ones((N, Z, X, Y, 1), np.float32)
 
@@ -564,7 +574,7 @@ def SERVER_train_volume(params, options):
     total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
     x_dev = torch.from_numpy(np.array(x, dtype=np.float32, order='C')).to(dev)
     y_dev = torch.from_numpy(np.ascontiguousarray(onehot)).to(dev)
-    w_dev = torch.from_numpy(np.ascontiguousarray(wmap)).to(dev)
+    w_dev = wmap if isinstance(wmap, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wmap)).to(dev)
     loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
     rng = np.random.default_rng(int(params.get('seed', 0)))
     done = 0
@@ -591,6 +601,8 @@ def SERVER_train_volume(params, options):
             'steady_steps': max(done - 1, 0), 'batch_size': batch, 'volumes': int(N), 'shape': [int(Z), int(X), int(Y)],
             'graph': False, 'dtype': 'f32', 'warmup_steps': trainer.warmup_steps, 'learning_rate': trainer.lr,
             'world': 1, 'device': device}
+    if wm_kind == 'edt' and not params.get('weights'):
+        info.update(weightmap='edt', w0=wm_w0, sigma=wm_sigma, spacing=wm_spacing)
     info['model_dir'] = utils.save_model(trainer.state_dict(), config)
     with open(os.path.join(params['output'], 'train.json'), 'w') as f:
         json.dump(dict(info, losses=losses), f, indent=2)

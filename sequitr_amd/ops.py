@@ -1518,6 +1518,45 @@ def weightmap_edt(img, w0=10.0, sigma=5.0, dtype=torch.float32):
     return out
 
 
+def _wm3d_args(img, spacing, who):
+    _chk(img, "img")
+    if img.dim() == 5 and img.shape[-1] == 1:
+        img = img.reshape(img.shape[:4])
+    if img.dim() != 4:
+        raise ValueError("img must be (N,D,H,W) or (N,D,H,W,1), got %s" % (tuple(img.shape),))
+    spacing = float(spacing)
+    if not (spacing > 0.0 and spacing != float("inf")):
+        raise ValueError("%s: spacing must be finite and > 0, got %r" % (who, spacing))
+    N, D, H, W = img.shape
+    lib = _lib.load()
+    nbytes = lib.sq_weightmap3d_workspace(N, D, H, W)
+    if nbytes < 0:
+        raise ValueError("weight map volumes %s are too large for one call" % (tuple(img.shape),))
+    return img, N, D, H, W, spacing, lib, _workspace(nbytes, img.device)
+
+
+def edt3d_squared(img, spacing=1.0):
+    """Squared 3-D Euclidean distance (float64; an exact integer for spacing == 1) of every voxel of the (N,D,H,W) binary
+    f32 volumes to the nearest voxel with 1 - img == 0, the depth axis scaled by `spacing` (scipy's sampling=(dz, 1, 1))."""
+    img, N, D, H, W, dz, lib, ws = _wm3d_args(img, spacing, "edt3d_squared")
+    d2 = torch.empty((N, D, H, W), dtype=torch.float64, device=img.device)
+    _lib.check(lib.sq_edt3d_sq_f64(_ptr(img), _ptr(d2), _ptr(ws), N, D, H, W, dz, _stream()), "sq_edt3d_sq_f64")
+    return d2
+
+
+def weightmap_edt3d(img, w0=10.0, sigma=5.0, spacing=1.0, dtype=torch.float32):
+    """ImageWeightMap (pipeline.py:455-479) of a batch of binary label VOLUMES (N,D,H,W), on the device: the reference's
+    call on a (Z, X, Y) array, with the depth spacing in in-plane pixels.  dtype as in weightmap_edt."""
+    if dtype not in (torch.float64, torch.float32):
+        raise TypeError("weightmap_edt3d: dtype must be float32 or float64")
+    img, N, D, H, W, dz, lib, ws = _wm3d_args(img, spacing, "weightmap_edt3d")
+    out = torch.empty((N, D, H, W), dtype=dtype, device=img.device)
+    o64, o32 = (_ptr(out), None) if dtype == torch.float64 else (None, _ptr(out))
+    _lib.check(lib.sq_weightmap3d_edt_f32(_ptr(img), o64, o32, _ptr(ws), N, D, H, W, float(w0), float(sigma), dz, _stream()),
+               "sq_weightmap3d_edt_f32")
+    return out
+
+
 def wm2_boundary_points(img):
     """ImageWeightMap2's boundary-point mask (pipeline.py:516-528) of (N,H,W) binary f32 labels: uint8 (N,H,W)."""
     _chk(img, "img", ndim=3)

@@ -91,6 +91,22 @@ def device_weightmaps(labels, w0=10., sigma=5., device=None):
     return w.reshape(tuple(w.shape) + (1,))
 
 
+def device_weightmaps3d(labels, w0=10., sigma=5., spacing=1., device=None):
+    """EDT weight maps (ImageWeightMap, pipeline.py:455-479, called on a (Z, X, Y) array: the true 3-D Euclidean
+    transform) of a stack of binary label VOLUMES computed on the GPU and LEFT THERE as the (N,Z,X,Y,1) float32 `weights`
+    tensor the volumetric training step takes.  labels: (N,Z,X,Y) array or device tensor, non-zero = cell; spacing = the
+    depth spacing in in-plane pixels (scipy's sampling=(spacing, 1, 1))."""
+    import torch
+    from . import ops
+    if not isinstance(labels, torch.Tensor):
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels) > 0, dtype=np.float32)).to(dev)
+    else:
+        labels = (labels > 0).to(torch.float32).contiguous()
+    w = ops.weightmap_edt3d(labels, w0, sigma, spacing, dtype=torch.float32)
+    return w.reshape(tuple(w.shape) + (1,))
+
+
 def boundary_triangulation(label):
     """Host half of ImageWeightMap2 (pipeline.py:514-537), literally: boundary points = erosion outline of the mask
     XOR outline of the 3x-dilated mask (von Neumann element), scipy's Delaunay of them in np.where order.  Returns
