@@ -880,6 +880,34 @@ int sq_frames_to_tiles(const void *frames, int dtype, const float *mean, const f
 int sq_stitch_masks_u8(const uint8_t *tile_masks, const int32_t *ymap, const int32_t *xmap, uint8_t *out, int F, int H,
                        int W, int TR, int TC, int TS, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Volume front end: raw single-channel volumes (V, Z, X, Y) in HBM -> ImageNorm per volume -> network bricks, and
+ * the brick-shaped network output back into full-volume arrays (sequitr_amd/frontend.py: volume_bricks, VolumeTiler).
+ * A volume has KZ x KX x KY bricks of (BZ, BX, BY) voxels, numbered (v, kz, kx, ky) row-major.  `geom` is one int32
+ * array in HBM of 3 * (KZ + KX + KY) entries: the brick origins along z, x, y, then the first coordinate each brick
+ * owns along z, x, y, then one past the last (absolute coordinates; the owned boxes of a volume partition it).  An axis
+ * shorter than the brick has one brick at origin 0 that owns the whole axis.
+ *   sq_volume_stats     : per-volume float32 mean and std EXACTLY as np.mean / np.std of the float32 volume: float32
+ *                         pairwise sums per 8192-element chunk added in order, the division by nvox in double
+ *                         (numpy divides by an integer count), which sq_frame_stats' float32 division equals only up
+ *                         to 2^24 elements.  nvox <= 2^40; workspace: sq_volume_stats_workspace bytes.
+ *   sq_volume_to_bricks : out (count, BZ, BX, BY) f32 = bricks first .. first+count-1: (x - mean[v]) / std[v], or the
+ *                         plain cast when mean == std == NULL; 0.0f where the brick reaches beyond the volume.
+ *   sq_bricks_scatter_* : every brick's owned box copied from bricks (count, BZ, BX, BY[, C]) into out (V, Z, X, Y[, C]);
+ *                         owned boxes are disjoint, so batches may be scattered in any order.
+ * count <= 65535 and BZ <= 65535 (grid dimensions).
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_volume_stats_workspace(int V, int64_t nvox);
+int sq_volume_stats(const void *vols, int dtype, float *mean, float *stdv, void *workspace, int V, int64_t nvox,
+                    void *stream);
+int sq_volume_to_bricks(const void *vols, int dtype, const float *mean, const float *stdv, const int32_t *geom, float *out,
+                        int V, int Z, int X, int Y, int KZ, int KX, int KY, int BZ, int BX, int BY, int64_t first,
+                        int count, void *stream);
+int sq_bricks_scatter_u8(const uint8_t *bricks, const int32_t *geom, uint8_t *out, int V, int Z, int X, int Y, int KZ,
+                         int KX, int KY, int BZ, int BX, int BY, int64_t first, int count, void *stream);
+int sq_bricks_scatter_f32(const float *bricks, const int32_t *geom, float *out, int V, int Z, int X, int Y, int KZ, int KX,
+                          int KY, int BZ, int BX, int BY, int C, int64_t first, int count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

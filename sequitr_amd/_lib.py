@@ -71,6 +71,11 @@ SIGNATURES = {
     "sq_frame_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "sq_frames_to_tiles": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
     "sq_stitch_masks_u8": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "sq_volume_stats_workspace": (c_int64, [c_int, c_int64]),
+    "sq_volume_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
+    "sq_volume_to_bricks": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 10 + [c_int64, c_int, c_void_p]),
+    "sq_bricks_scatter_u8": (c_int, [c_void_p] * 3 + [c_int] * 10 + [c_int64, c_int, c_void_p]),
+    "sq_bricks_scatter_f32": (c_int, [c_void_p] * 3 + [c_int] * 11 + [c_int64, c_int, c_void_p]),
     "sq_dense_workspace_f32": (c_int64, [c_int, c_int, c_int]),
     "sq_dense_fwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "sq_convT_conv3x3_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

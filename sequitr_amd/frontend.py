@@ -8,6 +8,10 @@ float32 summation order).
 Tiling (build-defined: the reference only ever crops fixed-size tiles, pipeline.py:429-441): along an axis of
 length L, tiles of size T start at 0, T-2m, 2(T-2m), ... and the last one at L-T; every pixel is owned by the
 tile in which it lies at least `m` (margin) pixels from the tile border, except at the frame border.
+
+Volumes take the same path in three dimensions (VolumeTiler, segment_volumes): a brick is a box of the network's
+input shape, the rule above holds along each axis, and an axis shorter than the brick is padded with the
+normalised mean, 0.
 """
 import os
 import time
@@ -37,6 +41,53 @@ def axis_tiles(L, T, margin):
     owner = np.searchsorted(starts, np.arange(L), side='right') - 1
     local = np.arange(L) - origins[owner]
     return origins, ((owner.astype(np.int64) << 16) | local).astype(np.int32)
+
+
+def axis_bricks(L, T, margin):
+    """axis_tiles for volumes: (origins, lo, hi), brick k starts at origins[k] and owns the coordinates [lo[k], hi[k]).
+    The rule is axis_tiles'; an axis shorter than the brick (T > L, common for Z) has one brick at origin 0 that owns
+    [0, L) -- its coordinates >= L are padding."""
+    if L < 1:
+        raise ValueError('an axis of %d voxels has no bricks' % L)
+    if not 0 <= 2 * margin < T:
+        raise ValueError('margin %d too large for brick %d' % (margin, T))
+    if T > L:
+        return np.zeros(1, np.int32), np.zeros(1, np.int32), np.full(1, L, np.int32)
+    origins, owner = axis_tiles(L, T, margin)
+    k = owner >> 16                                             # non-decreasing: every brick owns one run
+    ks = np.arange(len(origins))
+    return origins, np.searchsorted(k, ks, side='left').astype(np.int32), np.searchsorted(k, ks, side='right').astype(np.int32)
+
+
+class BrickGeometry(object):
+    """Bricks of one volume shape (host only).  Axis order is the array's, (Z, X, Y); a volume has counts[0] * counts[1] *
+    counts[2] bricks numbered (kz, kx, ky) row-major, and brick number (v * per_volume + k) is brick k of volume v."""
+
+    def __init__(self, vol_shape, brick, margin):
+        self.shape = tuple(int(s) for s in vol_shape)
+        self.brick = tuple(int(s) for s in brick)
+        self.margin = (int(margin),) * 3 if np.isscalar(margin) else tuple(int(m) for m in margin)
+        if len(self.shape) != 3 or len(self.brick) != 3 or len(self.margin) != 3:
+            raise ValueError('vol_shape, brick and margin are (Z, X, Y) triples, got %r, %r, %r' % (vol_shape, brick, margin))
+        axes = [axis_bricks(L, T, m) for L, T, m in zip(self.shape, self.brick, self.margin)]
+        self.origins, self.lo, self.hi = ([a[i] for a in axes] for i in range(3))
+        self.counts = tuple(len(o) for o in self.origins)
+        self.per_volume = self.counts[0] * self.counts[1] * self.counts[2]
+
+    def box(self, k):
+        """brick k of a volume: (origin, first owned, one past the last owned), each (z, x, y) in volume coordinates"""
+        idx = np.unravel_index(int(k), self.counts)
+        return tuple(tuple(int(t[a][idx[a]]) for a in range(3)) for t in (self.origins, self.lo, self.hi))
+
+    def table(self):
+        """the int32 `geom` array of include/sequitr_hip.h: origins z, x, y | first owned z, x, y | one past z, x, y"""
+        return np.concatenate([np.concatenate(t) for t in (self.origins, self.lo, self.hi)]).astype(np.int32)
+
+
+def volume_bricks(vol_shape, brick, margin):
+    """Brick geometry of a (Z, X, Y) volume cut into `brick`-shaped boxes with `margin` (an int, or one per axis) voxels
+    of context: axis_bricks along each axis.  The owned boxes partition the volume."""
+    return BrickGeometry(vol_shape, brick, margin)
 
 
 class FrameTiler(object):
@@ -197,6 +248,204 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         drain(pending)
     torch.cuda.synchronize(dev)
     return out
+
+
+def volume_stats(vols):
+    """per-volume float32 (mean, std) of a contiguous (V, ...) uint8 / uint16 / float32 tensor in GPU memory, exactly as
+    np.mean / np.std of each float32 volume (sq_volume_stats: any number of voxels up to 2^40)."""
+    if not isinstance(vols, torch.Tensor) or not vols.is_cuda:
+        raise _lib.SequitrHipError('volumes must be a tensor in GPU memory (no CPU fallback exists)')
+    if vols.dtype not in PIX or vols.dim() < 2 or not vols.is_contiguous():
+        raise ValueError('volumes must be a contiguous (V, ...) uint8 / uint16 / float32 tensor')
+    V = int(vols.shape[0])
+    nvox = vols.numel() // max(V, 1)
+    lib = _lib.load()
+    nbytes = lib.sq_volume_stats_workspace(V, nvox)
+    if nbytes < 0:
+        raise ValueError('%d volumes of %d voxels are out of range (1 .. 65535 volumes of 1 .. 2^40 voxels)' % (V, nvox))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=vols.device)
+    mean = torch.empty(V, dtype=torch.float32, device=vols.device)
+    std = torch.empty(V, dtype=torch.float32, device=vols.device)
+    _lib.check(lib.sq_volume_stats(vols.data_ptr(), PIX[vols.dtype], mean.data_ptr(), std.data_ptr(), ws.data_ptr(), V,
+                                   nvox, torch.cuda.current_stream().cuda_stream), 'sq_volume_stats')
+    return mean, std
+
+
+class VolumeTiler(object):
+    """Geometry + device kernels for single-channel volumes of one (Z, X, Y) shape cut into network bricks
+    (include/sequitr_hip.h "Volume front end").  brick / margin are in the array's (Z, X, Y) order."""
+
+    def __init__(self, vol_shape, brick, margin=0, device=None):
+        self.geometry = volume_bricks(vol_shape, brick, margin)
+        self.shape, self.brick, self.margin = self.geometry.shape, self.geometry.brick, self.geometry.margin
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise _lib.SequitrHipError('VolumeTiler runs on the HIP back end only')
+        self._geom = torch.from_numpy(self.geometry.table()).to(self.device)
+
+    @property
+    def bricks_per_volume(self):
+        return self.geometry.per_volume
+
+    def _dims(self, V):
+        return (int(V),) + self.shape + self.geometry.counts + self.brick
+
+    def _check_volumes(self, vols):
+        if not isinstance(vols, torch.Tensor) or not vols.is_cuda:
+            raise _lib.SequitrHipError('volumes must be a tensor in GPU memory (no CPU fallback exists)')
+        if vols.dtype not in PIX or vols.dim() != 4 or not vols.is_contiguous():
+            raise ValueError('volumes must be a contiguous (V,Z,X,Y) uint8 / uint16 / float32 tensor')
+        if tuple(vols.shape[1:]) != self.shape:
+            raise ValueError('volumes are %s, tiler was built for %s' % (tuple(vols.shape[1:]), self.shape))
+
+    def _range(self, V, first, count):
+        total = V * self.bricks_per_volume
+        count = total - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > total:
+            raise ValueError('bricks %d .. %d are not among the %d bricks of %d volumes' % (first, first + count - 1, total, V))
+        return int(first), count
+
+    def stats(self, vols):
+        """per-volume float32 (mean, std) exactly as np.mean / np.std of the float32 volume."""
+        self._check_volumes(vols)
+        return volume_stats(vols)
+
+    def bricks(self, vols, first=0, count=None, normalise=True, stats=None):
+        """(count, BZ, BX, BY, 1) float32 bricks first .. first+count-1 of the stack (default: all that follow `first`),
+        ImageNorm applied per volume when `normalise` -- with `stats` = self.stats(vols) when the caller already has them;
+        0.0 where a brick reaches beyond a volume shorter than the brick."""
+        self._check_volumes(vols)
+        V = vols.shape[0]
+        first, count = self._range(V, first, count)
+        mean, std = (stats if stats is not None else self.stats(vols)) if normalise else (None, None)
+        if normalise and not all(t.is_cuda and t.dtype == torch.float32 and t.numel() == V and t.is_contiguous()
+                                 for t in (mean, std)):
+            raise ValueError('stats must be the (mean, std) float32 tensors of these %d volumes in GPU memory' % V)
+        lib = _lib.load()
+        out = torch.empty((count,) + self.brick + (1,), dtype=torch.float32, device=self.device)
+        for lo in range(0, count, 65535):                       # a launch takes at most 65535 bricks
+            n = min(65535, count - lo)
+            _lib.check(lib.sq_volume_to_bricks(vols.data_ptr(), PIX[vols.dtype], mean.data_ptr() if normalise else None,
+                                               std.data_ptr() if normalise else None, self._geom.data_ptr(),
+                                               out[lo:].data_ptr(), *(self._dims(V) + (first + lo, n)),
+                                               torch.cuda.current_stream().cuda_stream), 'sq_volume_to_bricks')
+        return out
+
+    def scatter(self, values, out, first=0):
+        """Copy the owned boxes of bricks first .. first+len(values)-1 into the full-volume array `out`, in place:
+        uint8 (n, BZ, BX, BY) masks into (V, Z, X, Y), or float32 (n, BZ, BX, BY, C) logits into (V, Z, X, Y, C)."""
+        for t, what in ((values, 'values'), (out, 'out')):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise _lib.SequitrHipError('%s must be a tensor in GPU memory (no CPU fallback exists)' % what)
+            if not t.is_contiguous():
+                raise ValueError('%s must be contiguous' % what)
+        if values.dtype != out.dtype or values.dtype not in (torch.uint8, torch.float32):
+            raise ValueError('values and out must both be uint8 masks or float32 logits, got %s and %s' % (values.dtype, out.dtype))
+        logits = values.dtype == torch.float32
+        if values.dim() != 4 + logits or tuple(values.shape[1:4]) != self.brick or values.shape[0] < 1:
+            raise ValueError('values %s are not bricks of %s' % (tuple(values.shape), self.brick))
+        if out.dim() != 4 + logits or tuple(out.shape[1:4]) != self.shape or (logits and out.shape[4] != values.shape[4]):
+            raise ValueError('out %s does not hold volumes of %s for values %s' % (tuple(out.shape), self.shape, tuple(values.shape)))
+        V = out.shape[0]
+        first, count = self._range(V, first, values.shape[0])
+        lib = _lib.load()
+        st = torch.cuda.current_stream().cuda_stream
+        for lo in range(0, count, 65535):
+            n = min(65535, count - lo)
+            if logits:
+                _lib.check(lib.sq_bricks_scatter_f32(values[lo:].data_ptr(), self._geom.data_ptr(), out.data_ptr(),
+                                                     *(self._dims(V) + (int(values.shape[4]), first + lo, n, st))),
+                           'sq_bricks_scatter_f32')
+            else:
+                _lib.check(lib.sq_bricks_scatter_u8(values[lo:].data_ptr(), self._geom.data_ptr(), out.data_ptr(),
+                                                    *(self._dims(V) + (first + lo, n, st))), 'sq_bricks_scatter_u8')
+        return out
+
+
+def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise=True, want_logits=False, on_masks=None):
+    """Segment whole volumes brick by brick: `volumes` is an (N, Z, X, Y) uint8 | uint16 | float32 numpy array or memmap,
+    `net` a UNet3D built at the brick shape (brick and margin in the array's (Z, X, Y) order).  Raw volume i+1 goes
+    through two pinned Z-slab buffers of bounded size and is uploaded on a side stream while volume i runs: statistics,
+    then per batch of bricks cut -> net.predict -> scatter of the masks (and of the logits when asked) into full-volume
+    arrays in HBM, which drain to the host on a third stream while volume i+1 runs.  Returns (masks (N, Z, X, Y) uint8,
+    logits (N, Z, X, Y, n_outputs) float32 or None) on the host.  With on_masks the masks are not downloaded: each
+    volume's device mask is handed to on_masks(i, mask (1, Z, X, Y)) instead, valid until volume i+2 is started, and
+    the first value returned is None."""
+    arr = volumes
+    if getattr(arr, 'ndim', 0) != 4:
+        raise ValueError('volumes must be (N, Z, X, Y), got shape %s' % (getattr(arr, 'shape', None),))
+    N, Z, X, Y = (int(s) for s in arr.shape)
+    np_dtype = np.dtype(arr.dtype)
+    if np_dtype not in NP_TORCH:
+        raise TypeError('volumes must be uint8, uint16 or float32, got %s' % np_dtype)
+    tdt = NP_TORCH[np_dtype]
+    tiler = VolumeTiler((Z, X, Y), brick, margin, device=net.device)
+    dev = tiler.device
+    B, nb, n_out = max(1, int(bricks_per_batch)), tiler.bricks_per_volume, int(net.n_outputs)
+    SZ = max(1, min(Z, (32 << 20) // (X * Y * np_dtype.itemsize)))  # Z-slices per pinned slab: 32 MB at the most
+    pinned = [_pinned('vol_in%d' % i, (SZ, X, Y), tdt) for i in range(2)]
+    staged = [torch.empty((1, Z, X, Y), dtype=tdt, device=dev) for _ in range(2)]
+    mask_dev = [torch.empty((1, Z, X, Y), dtype=torch.uint8, device=dev) for _ in range(2)]
+    logits_dev = [torch.empty((1, Z, X, Y, n_out), dtype=torch.float32, device=dev) for _ in range(2)] if want_logits else None
+    copy_stream, out_stream = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    slab_sent = [torch.cuda.Event(), torch.cuda.Event()]       # the upload out of pinned[j] finished
+    ready = [torch.cuda.Event(), torch.cuda.Event()]            # volume k is complete in staged[k]
+    freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[k]
+    done = [torch.cuda.Event(), torch.cuda.Event()]             # mask_dev[k] / logits_dev[k] are complete
+    out_masks = None if on_masks is not None else np.empty((N, Z, X, Y), np.uint8)
+    out_logits = np.empty((N, Z, X, Y, n_out), np.float32) if want_logits else None
+    cur = torch.cuda.current_stream(dev)
+    for e in slab_sent + freed:
+        e.record(cur)
+
+    def upload(i):
+        k = i & 1
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(freed[k])                    # volume i-2 has been cut
+        for s, z0 in enumerate(range(0, Z, SZ)):
+            j, n = s & 1, min(SZ, Z - z0)
+            slab_sent[j].synchronize()                          # the previous upload out of this pinned slab is done
+            pinned[j][:n].numpy()[...] = arr[i, z0:z0 + n]      # page cache / memmap -> pinned
+            with torch.cuda.stream(copy_stream):
+                staged[k][0, z0:z0 + n].copy_(pinned[j][:n], non_blocking=True)
+                slab_sent[j].record(copy_stream)
+        ready[k].record(copy_stream)
+
+    def drain(i):
+        """volume i's results -> the host arrays; blocks this thread on out_stream only, the compute stream runs on"""
+        k = i & 1
+        with torch.cuda.stream(out_stream):
+            out_stream.wait_event(done[k])
+            if out_masks is not None:
+                torch.from_numpy(out_masks[i]).copy_(mask_dev[k][0])
+            if out_logits is not None:
+                torch.from_numpy(out_logits[i]).copy_(logits_dev[k][0])
+        out_stream.synchronize()
+
+    if N:
+        upload(0)
+    for i in range(N):
+        k = i & 1
+        cur.wait_event(ready[k])
+        stats = tiler.stats(staged[k]) if normalise else None
+        for first in range(0, nb, B):
+            bricks = tiler.bricks(staged[k], first, min(B, nb - first), normalise=normalise, stats=stats)
+            masks = net.predict(bricks)
+            tiler.scatter(masks, mask_dev[k], first)
+            if want_logits:
+                tiler.scatter(net.logits(), logits_dev[k], first)
+        freed[k].record(cur)
+        done[k].record(cur)
+        if on_masks is not None:
+            on_masks(i, mask_dev[k])
+        if i + 1 < N:
+            upload(i + 1)                                       # host copies and H2D, under this volume's kernels
+        if i >= 1:
+            drain(i - 1)                                        # before volume i+1 reuses its output arrays
+    if N:
+        drain(N - 1)
+    torch.cuda.synchronize(dev)
+    return out_masks, out_logits
 
 
 class TileStreamer(object):

@@ -179,6 +179,96 @@ def _load_volumes(params):
     return x
 
 
+def _load_net_weights(net, params):
+    """params['model'] (a numbered model dir, or a name under MODELDIR) into `net`; seeded initial weights without it"""
+    from . import utils
+    model = params.get('model')
+    if not model:
+        net.initialize()
+        return
+    model_dir = model if os.path.isdir(model) else utils.get_latest_model_dir(
+        os.path.join(utils.core.TensorflowConfiguration.MODELDIR, model))
+    if model_dir is None:
+        raise IOError('No saved model found for {0}'.format(model))
+    net.load_state_dict(utils.load_model_weights(model_dir))
+    logger.info('Loaded weights from {0:s}'.format(model_dir))
+
+
+def _segment_volume_bricks(params, options):
+    """SERVER_segment_volume with params['brick']: volumes of any size, raw, brick by brick (frontend.segment_volumes)."""
+    from .frontend import NP_TORCH, volume_bricks
+
+    device = _resolve_device(params, options)
+    out_dir = params['output']
+    x = _load_volumes(params)
+    if x.shape[4] != 1 or int(params.get('num_inputs', 1)) != 1:
+        raise ValueError("params['brick'] segments single-channel volumes only, got %d channels" % x.shape[4])
+    x = x[..., 0]                                              # (N, Z, X, Y), still the raw array or memmap: no host cast
+    if np.dtype(x.dtype) not in NP_TORCH:
+        raise TypeError("with params['brick'] the volumes must be uint8, uint16 or float32, got %s" % x.dtype)
+    N, Z, X, Y = (int(s) for s in x.shape)
+    if len(tuple(params['brick'])) != 3:
+        raise ValueError("params['brick'] must be (X, Y, Z), got %r" % (params['brick'],))
+    bx, by, bz = (int(s) for s in params['brick'])
+    margin = params.get('margin', 0)
+    if not np.isscalar(margin):
+        if len(tuple(margin)) != 3:
+            raise ValueError("params['margin'] must be an int or (X, Y, Z), got %r" % (margin,))
+        margin = (int(margin[2]), int(margin[0]), int(margin[1]))
+    geometry = volume_bricks((Z, X, Y), (bz, bx, by), margin)  # raises on a margin too large for the brick
+
+    import torch
+    from .networks.unet import UNet3D
+    from .frontend import segment_volumes
+    torch.cuda.set_device(torch.device(device))
+    net_p = _net_params(params, device)
+    net_p['shape'] = (bx, by, bz)
+    net_p['num_inputs'] = 1
+    t_setup = time.time()
+    net = UNet3D(net_p, 'infer')
+    _load_net_weights(net, params)
+    want_logits = bool(options.get('save_logits'))
+    want_centroids = bool(options.get('centroids'))
+    batch = int(params.get('bricks_per_batch', 8))
+    net.predict(torch.zeros((min(batch, geometry.per_volume), bz, bx, by, 1), device=device))   # first-launch costs
+    torch.cuda.synchronize()
+    per_volume = {}
+    masks = np.zeros((N, Z, X, Y), np.uint8) if want_centroids else None
+
+    def sink(i, m):                                            # centroids straight from the mask in HBM: no second upload
+        from .centroids import mask_centroids
+        masks[i] = m[0].cpu().numpy()
+        coords = mask_centroids(m.transpose(1, 3).contiguous())[0]    # the axes as CentroidWriter.write swaps them
+        coords[:, 0] = i
+        per_volume[i] = coords
+
+    t0 = time.time()
+    out, logits = segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch,
+                                  normalise=bool(params.get('normalise', True)), want_logits=want_logits,
+                                  on_masks=sink if want_centroids else None)
+    if not want_centroids:
+        masks = out
+    dt = time.time() - t0
+    np.save(os.path.join(out_dir, 'mask.npy'), masks)
+    if logits is not None:
+        np.save(os.path.join(out_dir, 'logits.npy'), logits)
+    voxels = N * Z * X * Y
+    info = {'volumes': int(N), 'shape': [Z, X, Y], 'seconds': dt, 'setup_seconds': t0 - t_setup,
+            'mvoxels_per_s': float(voxels / max(dt, 1e-9) / 1e6), 'device': device,
+            'brick': [bx, by, bz], 'margin': [geometry.margin[1], geometry.margin[2], geometry.margin[0]],
+            'bricks_per_volume': int(geometry.per_volume)}
+    if want_centroids:
+        from .centroids import CentroidWriter
+        with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
+            for i in sorted(per_volume):
+                cw.add_frame(i, per_volume[i])
+        info['centroids'] = {'file': os.path.basename(cw.filename), 'objects': int(sum(len(v) for v in per_volume.values()))}
+    with open(os.path.join(out_dir, 'segment_volume.json'), 'w') as f:
+        json.dump(info, f, indent=2)
+    logger.info('Segmented {volumes} volumes in {seconds:.3f}s on {device}, {bricks_per_volume} bricks each'.format(**info))
+    return info
+
+
 def SERVER_segment_volume(params, options):
     """Segment volumes (z-stacks) with UNet3D, one volume per launch: writes ``mask.npy`` (uint8, N x Z x X x Y),
     with options['save_logits'] ``logits.npy``, with options['centroids'] the centroid file (``tracks.hdf5``, or
@@ -186,12 +276,22 @@ def SERVER_segment_volume(params, options):
     params: as SERVER_segment (input, num_inputs, num_outputs, filters, bridge, batch_norm, model for a warm start);
     shape defaults to (X, Y, Z) of the input (synthetic input needs it).  options: gpu, save_logits, centroids.
 
+    With params['brick'] = (X, Y, Z), the network's `shape` convention, volumes of any size are segmented brick by brick
+    (frontend.segment_volumes): the network is built at the brick shape, the input is raw uint8 / uint16 / float32 single-
+    channel volumes that cross PCIe as they are, and ImageNorm per volume (params['normalise'], default True), brick
+    cutting and the scatter of masks and logits run on the GPU.  params['margin'] (an int, or (X, Y, Z); default 0) is
+    the context every owned voxel keeps to its brick's faces, params['bricks_per_batch'] (default 8) the bricks per
+    network launch.  The centroids come from the masks while they are in HBM.  ``segment_volume.json`` gains ``brick``,
+    ``margin`` (both (X, Y, Z)) and ``bricks_per_volume``.
+
     ``segment_volume.json``: ``seconds`` / ``mvoxels_per_s`` cover the volumes (upload, network, download);
     ``setup_seconds`` is weights plus one warm-up volume."""
     import torch
     from .networks.unet import UNet3D
     from . import utils
 
+    if params.get('brick') is not None:
+        return _segment_volume_bricks(params, options)
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
     out_dir = params['output']
