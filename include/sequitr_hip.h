@@ -908,6 +908,42 @@ int sq_bricks_scatter_u8(const uint8_t *bricks, const int32_t *geom, uint8_t *ou
 int sq_bricks_scatter_f32(const float *bricks, const int32_t *geom, float *out, int V, int Z, int X, int Y, int KZ, int KX,
                           int KY, int BZ, int BX, int BY, int C, int64_t first, int count, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Volume sampler: the training counterpart of the volume front end (sequitr/pipeline.py: ImageSample crops random ROIs
+ * and repeats the coordinates for labels and weights, ImageFlip mirrors, ImageRotate turns; sequitr_amd/frontend.py:
+ * sample_plan, VolumeSampler).  Volumes, labels and weight maps (V, Z, X, Y[, ...]) stay in HBM; a SAMPLE PLAN is an int32
+ * array (count, 5) in HBM with rows [v, oz, ox, oy, op]: the volume, the origin of a (BZ, BX, BY) box in the array's
+ * (Z, X, Y) order, and a 4-bit symmetry -- bit 0 flips z, bit 1 flips x, bit 2 flips y, bit 3 transposes x and y.  As
+ * numpy says it:
+ *
+ *     box = zero-padded crop vol[v, oz:oz+BZ, ox:ox+BX, oy:oy+BY]      # fill where the box leaves the volume
+ *     if op & 8: box = box.transpose(0, 2, 1)                          # needs BX == BY
+ *     if op & 1: box = box[::-1];  if op & 2: box = box[:, ::-1];  if op & 4: box = box[:, :, ::-1]
+ *
+ * that is out[z, x, y] = box[fz(z), a, b] with (a, b) = (fx(x), fy(y)), or (fy(y), fx(x)) under bit 3, f the identity
+ * or the mirror of its axis.  The 16 ops are the group the three flips and the in-plane transpose generate; it holds
+ * every in-plane quarter turn, and every op is exact (no interpolation).
+ *   sq_volume_sample_f32       : raw SQ_PIX_* volumes -> out (count, BZ, BX, BY) f32 = (x - mean[v]) / std[v] (the
+ *                                expression of sq_volume_to_bricks: op 0 at a brick's origin gives that brick bit for
+ *                                bit), or the plain cast when mean == std == NULL; fill 0.0f.
+ *   sq_volume_sample_copy      : voxels of elem_bytes in {1, 2, 3, 4, 8} bytes moved verbatim (4: the f32 weight map, C:
+ *                                one-hot uint8 labels of C classes); fill zero bytes.
+ *   sq_volume_sample_onehot_u8 : class-index labels (V, Z, X, Y) uint8 -> out (count, BZ, BX, BY, C) uint8,
+ *                                out[..., c] = (label == c), C in 1 .. 16; fill all zero.
+ * `plan` points at the first of `count` rows.  The plan is data in HBM, so the kernels trust none of it: a coordinate
+ * outside the volume -- a negative origin, one beyond the volume, v outside 0 .. V-1 -- reads as fill, no load leaves
+ * the volumes.  Bits of op above bit 3 are ignored.  allow_transpose != 0 requires BX == BY (refused before any launch
+ * otherwise); with allow_transpose == 0 any BX, BY are taken and bit 3 is ignored.  count <= 65535 and BZ <= 65535
+ * (grid dimensions).  Transposed ops go through padded LDS tiles, so that global loads and stores both run along the
+ * contiguous axis; SQ_SAMPLE_LDS=0 (read per launch) gathers them directly instead, with the same bits.
+ * ---------------------------------------------------------------------------------------- */
+int sq_volume_sample_f32(const void *vols, int dtype, const float *mean, const float *stdv, const int32_t *plan, float *out,
+                         int V, int Z, int X, int Y, int BZ, int BX, int BY, int count, int allow_transpose, void *stream);
+int sq_volume_sample_copy(const void *src, int elem_bytes, const int32_t *plan, void *out, int V, int Z, int X, int Y,
+                          int BZ, int BX, int BY, int count, int allow_transpose, void *stream);
+int sq_volume_sample_onehot_u8(const uint8_t *labels, int C, const int32_t *plan, uint8_t *out, int V, int Z, int X, int Y,
+                               int BZ, int BX, int BY, int count, int allow_transpose, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

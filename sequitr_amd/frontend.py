@@ -12,6 +12,10 @@ tile in which it lies at least `m` (margin) pixels from the tile border, except 
 Volumes take the same path in three dimensions (VolumeTiler, segment_volumes): a brick is a box of the network's
 input shape, the rule above holds along each axis, and an axis shorter than the brick is padded with the
 normalised mean, 0.
+
+Training on volumes goes the other way round (sample_plan, VolumeSampler): the raw volumes, their labels and weight maps
+stay in HBM and every step's batch of bricks is cut there at random origins under a random exact symmetry -- the
+reference's ImageSample, ImageFlip and the quarter turns of ImageRotate (sequitr/pipeline.py) in front of UNet3DTrain.
 """
 import os
 import time
@@ -446,6 +450,141 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
         drain(N - 1)
     torch.cuda.synchronize(dev)
     return out_masks, out_logits
+
+
+OP_FLIP_Z, OP_FLIP_X, OP_FLIP_Y, OP_TRANSPOSE = 1, 2, 4, 8     # the symmetry bits of a sample plan's `op`
+
+
+def sample_plan(vol_shape, brick, volumes, count, rng, augment=('flip', 'rot90')):
+    """A sample plan (include/sequitr_hip.h "Volume sampler"): (count, 5) int32 rows [v, oz, ox, oy, op], host only.
+    vol_shape and brick are (Z, X, Y) triples, `volumes` the number of volumes, `rng` a numpy.random.Generator.  v is
+    uniform over the volumes; an origin is uniform over [0, L - T] inclusive along its axis, and 0 along an axis shorter
+    than the brick (the box is padded there).  'flip' in `augment` draws the three flip bits of op (ImageFlip mirrors
+    its samples), 'rot90' the in-plane transpose, bit 3 -- with the flips that makes every in-plane quarter turn, the
+    exact members of ImageRotate's range -- and needs a brick that is square in the plane; augment=() leaves op 0.
+
+    One deviation from ImageSample.update (sequitr/pipeline.py): its randint(boundary, L - boundary) excludes the upper
+    end, so it never draws the last origin L - T, and it cannot sample an axis with L == T at all.  This function does
+    both."""
+    shape, brick = tuple(int(s) for s in vol_shape), tuple(int(s) for s in brick)
+    if len(shape) != 3 or len(brick) != 3 or min(shape + brick) < 1:
+        raise ValueError('vol_shape and brick are (Z, X, Y) triples of positive sizes, got %r and %r' % (vol_shape, brick))
+    volumes, count = int(volumes), int(count)
+    if volumes < 1 or count < 1:
+        raise ValueError('need at least one volume and one sample, got %d and %d' % (volumes, count))
+    augment = (augment,) if isinstance(augment, str) else tuple(augment)
+    unknown = [a for a in augment if a not in ('flip', 'rot90')]
+    if unknown:
+        raise ValueError("augment holds 'flip' and / or 'rot90', got %r" % (unknown,))
+    if 'rot90' in augment and brick[1] != brick[2]:
+        raise ValueError("'rot90' needs a brick that is square in the plane, got %d x %d" % (brick[1], brick[2]))
+    plan = np.zeros((count, 5), np.int32)
+    plan[:, 0] = rng.integers(0, volumes, count)
+    for a in range(3):
+        plan[:, 1 + a] = rng.integers(0, max(shape[a] - brick[a], 0) + 1, count)
+    if 'flip' in augment:
+        plan[:, 4] |= rng.integers(0, 8, count).astype(np.int32)
+    if 'rot90' in augment:
+        plan[:, 4] |= (rng.integers(0, 2, count) * OP_TRANSPOSE).astype(np.int32)
+    return plan
+
+
+class VolumeSampler(object):
+    """Augmented training bricks cut on the GPU out of volumes, labels and weight maps that stay in HBM -- the training
+    counterpart of VolumeTiler (include/sequitr_hip.h "Volume sampler").  vol_shape / brick are in the array's (Z, X, Y)
+    order; `plan` is a (count, 5) int32 tensor in GPU memory (sample_plan's rows, or a slice of them).  The same plan
+    given to images(), copy() and onehot() cuts image, weights and labels at the same places under the same symmetry."""
+
+    def __init__(self, vol_shape, brick, device=None):
+        self.shape, self.brick = tuple(int(s) for s in vol_shape), tuple(int(s) for s in brick)
+        if len(self.shape) != 3 or len(self.brick) != 3 or min(self.shape + self.brick) < 1:
+            raise ValueError('vol_shape and brick are (Z, X, Y) triples of positive sizes, got %r and %r' % (vol_shape, brick))
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise _lib.SequitrHipError('VolumeSampler runs on the HIP back end only')
+        self.square = self.brick[1] == self.brick[2]            # bit 3 of op is only ever sent for such bricks
+
+    def _check(self, t, what, dtypes, tail=()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SequitrHipError('%s must be a tensor in GPU memory (no CPU fallback exists)' % what)
+        if t.dtype not in dtypes or t.dim() != 4 + len(tail) or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous (V,Z,X,Y%s) %s tensor' % (
+                what, ''.join(',%s' % c for c in tail), ' / '.join(str(d).replace('torch.', '') for d in dtypes)))
+        if tuple(t.shape[1:4]) != self.shape or t.shape[0] < 1:
+            raise ValueError('%s are %s, sampler was built for %s' % (what, tuple(t.shape[1:4]), self.shape))
+
+    def _plan(self, plan):
+        if not isinstance(plan, torch.Tensor) or not plan.is_cuda:
+            raise _lib.SequitrHipError('plan must be a tensor in GPU memory (no CPU fallback exists)')
+        if plan.dtype != torch.int32 or plan.dim() != 2 or plan.shape[1] != 5 or not plan.is_contiguous():
+            raise ValueError('plan must be a contiguous (count, 5) int32 tensor, got %s %s' % (plan.dtype, tuple(plan.shape)))
+        count = int(plan.shape[0])
+        if not 1 <= count <= 65535:
+            raise ValueError('a plan of %d rows is not one launch (1 .. 65535 rows)' % count)
+        return count
+
+    def _out(self, out, count, tail, dtype):
+        shape = (count,) + self.brick + tuple(tail)
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise _lib.SequitrHipError('out must be a tensor in GPU memory (no CPU fallback exists)')
+        if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError('out must be a contiguous %s tensor of %s, got %s %s' % (dtype, shape, out.dtype, tuple(out.shape)))
+        return out
+
+    def _dims(self, V, count):
+        return (int(V),) + self.shape + self.brick + (count, int(self.square), torch.cuda.current_stream().cuda_stream)
+
+    def images(self, vols, plan, normalise=True, stats=None, out=None):
+        """(count, BZ, BX, BY, 1) float32 bricks of the raw (V, Z, X, Y) uint8 / uint16 / float32 volumes, ImageNorm applied
+        per volume when `normalise` (with `stats` = volume_stats(vols) when the caller already has them); 0.0 where a box
+        leaves its volume.  A row with op 0 at a VolumeTiler's brick origin is that tiler's brick, bit for bit."""
+        self._check(vols, 'volumes', tuple(PIX))
+        count = self._plan(plan)
+        V = vols.shape[0]
+        mean, std = (stats if stats is not None else volume_stats(vols)) if normalise else (None, None)
+        if normalise and not all(t.is_cuda and t.dtype == torch.float32 and t.numel() == V and t.is_contiguous()
+                                 for t in (mean, std)):
+            raise ValueError('stats must be the (mean, std) float32 tensors of these %d volumes in GPU memory' % V)
+        out = self._out(out, count, (1,), torch.float32)
+        _lib.check(_lib.load().sq_volume_sample_f32(vols.data_ptr(), PIX[vols.dtype], mean.data_ptr() if normalise else None,
+                                                    std.data_ptr() if normalise else None, plan.data_ptr(), out.data_ptr(),
+                                                    *self._dims(V, count)), 'sq_volume_sample_f32')
+        return out
+
+    def copy(self, src, plan, out=None):
+        """bricks of `src` (V, Z, X, Y[, C]), voxels moved verbatim: (count, BZ, BX, BY[, C]) of src's dtype, zero bytes
+        where a box leaves its volume.  A voxel (the trailing axis included) is 1, 2, 3, 4 or 8 bytes: a float32 weight map
+        (V, Z, X, Y, 1), one-hot uint8 labels (V, Z, X, Y, C)."""
+        if not isinstance(src, torch.Tensor) or not src.is_cuda:
+            raise _lib.SequitrHipError('src must be a tensor in GPU memory (no CPU fallback exists)')
+        if src.dim() not in (4, 5) or not src.is_contiguous():
+            raise ValueError('src must be a contiguous (V,Z,X,Y[,C]) tensor, got %s' % (tuple(src.shape),))
+        if tuple(src.shape[1:4]) != self.shape or src.shape[0] < 1:
+            raise ValueError('src are %s, sampler was built for %s' % (tuple(src.shape[1:4]), self.shape))
+        tail = tuple(src.shape[4:])
+        nbytes = src.element_size() * (int(tail[0]) if tail else 1)
+        if nbytes not in (1, 2, 3, 4, 8):
+            raise ValueError('a voxel of %d bytes cannot be copied (1, 2, 3, 4 or 8 bytes)' % nbytes)
+        count = self._plan(plan)
+        out = self._out(out, count, tail, src.dtype)
+        _lib.check(_lib.load().sq_volume_sample_copy(src.data_ptr(), nbytes, plan.data_ptr(), out.data_ptr(),
+                                                     *self._dims(src.shape[0], count)), 'sq_volume_sample_copy')
+        return out
+
+    def onehot(self, labels, C, plan, out=None):
+        """(count, BZ, BX, BY, C) uint8 one-hot bricks of the class-index labels (V, Z, X, Y) uint8: out[..., c] = (label
+        == c); a label >= C, and a voxel where the box leaves its volume, is all zero.  C is 1 .. 16."""
+        self._check(labels, 'labels', (torch.uint8,))
+        C = int(C)
+        if not 1 <= C <= 16:
+            raise ValueError('%d classes are not 1 .. 16' % C)
+        count = self._plan(plan)
+        out = self._out(out, count, (C,), torch.uint8)
+        _lib.check(_lib.load().sq_volume_sample_onehot_u8(labels.data_ptr(), C, plan.data_ptr(), out.data_ptr(),
+                                                          *self._dims(labels.shape[0], count)), 'sq_volume_sample_onehot_u8')
+        return out
 
 
 class TileStreamer(object):

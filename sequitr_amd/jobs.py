@@ -596,6 +596,146 @@ def SERVER_train(params, options):
     return info
 
 
+def _train_volume_bricks(params, options):
+    """SERVER_train_volume with params['brick']: stacks of any size stay raw in HBM, every step's batch of augmented
+    bricks is cut there (frontend.sample_plan, VolumeSampler)."""
+    import torch
+    from . import utils
+    from .frontend import NP_TORCH, VolumeSampler, sample_plan, volume_bricks, volume_stats
+    from .networks.unet import UNet3DTrain
+    from .train import UNetTrainer
+
+    wm_kind = params.get('weightmap', 'uniform')
+    wm_w0, wm_sigma, wm_spacing = float(params.get('w0', 10.)), float(params.get('sigma', 5.)), float(params.get('spacing', 1.))
+    if len(tuple(params['brick'])) != 3:
+        raise ValueError("params['brick'] must be (X, Y, Z), got %r" % (params['brick'],))
+    bx, by, bz = (int(s) for s in params['brick'])
+    x = np.load(params['images'], mmap_mode='r', allow_pickle=False)
+    if x.ndim == 5 and x.shape[4] == 1:
+        x = x[..., 0]
+    if x.ndim != 4 or int(params.get('num_inputs', 1)) != 1:
+        raise ValueError("params['brick'] trains on single-channel (N, slices, width, height) stacks only, got shape %s" % (x.shape,))
+    if np.dtype(x.dtype) not in NP_TORCH:
+        raise TypeError("with params['brick'] the images must be uint8, uint16 or float32, got %s" % x.dtype)
+    N, Z, X, Y = (int(s) for s in x.shape)
+    augment = params.get('augment')
+    augment = (('flip', 'rot90') if bx == by else ('flip',)) if augment is None else \
+        ((augment,) if isinstance(augment, str) else tuple(augment))
+    seed = int(params.get('seed', 0))
+    rng = np.random.default_rng(seed)
+    sample_plan((Z, X, Y), (bz, bx, by), N, 1, np.random.default_rng(0), augment)     # refuses a bad `augment` before any upload
+    samples = params.get('samples_per_epoch')
+    samples = N * volume_bricks((Z, X, Y), (bz, bx, by), 0).per_volume if samples is None else int(samples)
+    if samples < 1:
+        raise ValueError('samples_per_epoch must be positive, got %d' % samples)
+
+    cfg_keys = ('name', 'num_outputs', 'num_epochs', 'learning_rate', 'warm_start', 'dropout')
+    cfg = {k: params[k] for k in cfg_keys if k in params}
+    cfg['shape'], cfg['num_inputs'] = (bx, by, bz), 1          # net.config records the brick: SERVER_segment_volume's `brick`
+    config = utils.NetConfiguration.from_params(cfg)
+    n_out = int(config.num_outputs)
+    labels = np.load(params['labels'], mmap_mode='r', allow_pickle=False)
+    if labels.ndim == 5:
+        labels = labels[..., :n_out]
+    if labels.ndim not in (4, 5) or tuple(labels.shape[:4]) != (N, Z, X, Y):
+        raise ValueError('labels %s do not match the images %s' % (labels.shape, x.shape))
+
+    device = _resolve_device(params, options)
+    torch.cuda.set_device(torch.device(device))
+    dev = torch.device(device)
+
+    def upload(arr, np_dtype, tail=()):
+        """host array or memmap -> HBM as it is, one volume at a time (no whole-stack host copy)"""
+        t = torch.empty((N, Z, X, Y) + tuple(tail), dtype=NP_TORCH[np.dtype(np_dtype)], device=dev)
+        for i in range(N):
+            t[i].copy_(torch.from_numpy(np.ascontiguousarray(arr[i], dtype=np_dtype)).reshape(t[i].shape))
+        return t
+
+    x_dev = upload(x, x.dtype)
+    index_labels = labels.ndim == 4                             # class indices stay at one byte per voxel
+    y_dev = upload(labels, np.uint8, () if index_labels else (n_out,))
+    if params.get('weights'):
+        w_dev = upload(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((N, Z, X, Y)), np.float32, (1,))
+    elif wm_kind == 'edt':
+        # once, on the whole volumes: crop and symmetry commute with the map (the spacing is along z, which no op mixes
+        # with x or y)
+        from .weightmap import device_weightmaps3d
+        fg = y_dev if index_labels else y_dev[..., 1:].sum(-1)
+        if N * Z * X * Y < (1 << 31):
+            w_dev = device_weightmaps3d(fg, wm_w0, wm_sigma, wm_spacing)
+        else:
+            w_dev = torch.empty((N, Z, X, Y, 1), dtype=torch.float32, device=dev)
+            for i in range(N):
+                w_dev[i:i + 1] = device_weightmaps3d(fg[i:i + 1], wm_w0, wm_sigma, wm_spacing)
+        del fg
+    else:
+        w_dev = torch.ones((N, Z, X, Y, 1), dtype=torch.float32, device=dev)    # resident, so padding still gets weight 0
+    normalise = bool(params.get('normalise', True))
+    stats = volume_stats(x_dev) if normalise else None          # ImageNorm of each WHOLE volume, as segment_volumes applies it
+
+    net_p = _net_params(params, device)
+    net_p['shape'] = (bx, by, bz)
+    net_p['num_inputs'], net_p['num_outputs'] = 1, n_out
+    net_p['dropout'] = float(params.get('dropout', 0.4))
+    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'),
+                          net_cls=UNet3DTrain)
+    config.learning_rate = trainer.lr
+    config.warmup_steps = trainer.warmup_steps
+    if config.warm_start:
+        latest = config.warm_start_from()
+        if latest:
+            trainer.load_state_dict(utils.load_model_weights(latest))
+            logger.info('Warm start from {0:s}'.format(latest))
+
+    batch = max(1, min(int(params.get('batch_size', 1)), samples))
+    steps_per_epoch = samples // batch
+    epochs = int(params.get('num_epochs', config.num_epochs))
+    max_steps = options.get('max_steps')
+    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    sampler = VolumeSampler((Z, X, Y), (bz, bx, by), dev)
+    bufs = (torch.empty((batch, bz, bx, by, 1), dtype=torch.float32, device=dev),
+            torch.empty((batch, bz, bx, by, n_out), dtype=torch.uint8, device=dev),
+            torch.empty((batch, bz, bx, by, 1), dtype=torch.float32, device=dev))
+    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    done = 0
+    t_start = t_steady = time.time()
+    for epoch in range(epochs):
+        if done >= total_steps:
+            break
+        plan = torch.from_numpy(sample_plan((Z, X, Y), (bz, bx, by), N, samples, rng, augment)).to(dev)   # ONE upload per epoch
+        for s in range(steps_per_epoch):
+            if done >= total_steps:
+                break
+            rows = plan[s * batch:(s + 1) * batch]
+            sampler.images(x_dev, rows, normalise=normalise, stats=stats, out=bufs[0])
+            if index_labels:
+                sampler.onehot(y_dev, n_out, rows, out=bufs[1])
+            else:
+                sampler.copy(y_dev, rows, out=bufs[1])
+            sampler.copy(w_dev, rows, out=bufs[2])
+            loss_log[done].copy_(trainer.step(*bufs))
+            done += 1
+            if done == 1:                                      # the first step carries the first-launch costs
+                torch.cuda.synchronize()
+                t_steady = time.time()
+    torch.cuda.synchronize()
+    t_end = time.time()
+    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
+    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
+            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady) * 1e3 / (done - 1) if done > 1 else None,
+            'steady_steps': max(done - 1, 0), 'batch_size': batch, 'volumes': N, 'shape': [Z, X, Y],
+            'brick': [bx, by, bz], 'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed,
+            'normalise': normalise, 'graph': False, 'dtype': 'f32', 'warmup_steps': trainer.warmup_steps,
+            'learning_rate': trainer.lr, 'world': 1, 'device': device}
+    if wm_kind == 'edt' and not params.get('weights'):
+        info.update(weightmap='edt', w0=wm_w0, sigma=wm_sigma, spacing=wm_spacing)
+    info['model_dir'] = utils.save_model(trainer.state_dict(), config)
+    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
+        json.dump(dict(info, losses=losses), f, indent=2)
+    logger.info('Trained {steps} steps on bricks of volumes, loss {first_loss} -> {last_loss}, saved {model_dir}'.format(**info))
+    return info
+
+
 def SERVER_train_volume(params, options):
     """Train the volumetric U-Net (UNet3DTrain, f32) on a stack of volumes with the weighted softmax cross-entropy.
 
@@ -612,6 +752,19 @@ def SERVER_train_volume(params, options):
     Single process, eager steps: the volumes, labels and weights are uploaded once, a batch is an index_select.  Writes
     ``weights.npz`` + ``net.config`` into the next numbered folder of MODELDIR/<name>/ and ``train.json`` (losses,
     ms_per_step) into params['output'].  The model loads strictly into UNet3D (SERVER_segment_volume's ``model``).
+
+    With params['brick'] = (X, Y, Z), the network's `shape` convention, the job trains on stacks of any size: the network is
+    built at the brick shape, `images` is a raw (N, slices, width, height) uint8 / uint16 / float32 single-channel stack
+    that is uploaded as it is and stays raw in HBM, class-index labels stay at one byte per voxel, the weight map (from
+    `weights`, 'edt' computed once on the whole volumes, or 'uniform' = ones) is resident, and every step's batch of bricks
+    is cut on the GPU at random origins under a random exact symmetry (frontend.sample_plan, VolumeSampler): ImageSample,
+    ImageFlip and the quarter turns of ImageRotate, with ImageNorm (params['normalise'], default True) from the statistics
+    of each whole volume, as SERVER_segment_volume applies it.  Where a brick leaves a volume shorter than it, the image is
+    0 and the weight 0.  params: augment (a subset of ('flip', 'rot90'); default both, 'flip' alone when the brick is not
+    square in the plane), samples_per_epoch (default: the number of bricks that tile the stack), seed (the plan's and the
+    network's).  Each epoch's plan is drawn on the host and uploaded once.  ``train.json`` gains ``brick``, ``augment``,
+    ``samples_per_epoch``, ``seed``; net.config's ``shape`` is the brick, so the model loads into SERVER_segment_volume
+    with the same ``brick``.
     """
     import torch
     from . import utils
@@ -623,6 +776,8 @@ def SERVER_train_volume(params, options):
     wm_kind = params.get('weightmap', 'uniform')
     if wm_kind not in ('uniform', 'edt'):
         raise ValueError("weightmap must be 'uniform' or 'edt', got %r" % (wm_kind,))
+    if params.get('brick') is not None:
+        return _train_volume_bricks(params, options)
     wm_w0, wm_sigma, wm_spacing = float(params.get('w0', 10.)), float(params.get('sigma', 5.)), float(params.get('spacing', 1.))
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
