@@ -881,6 +881,43 @@ int sq_stitch_masks_u8(const uint8_t *tile_masks, const int32_t *ymap, const int
                        int W, int TR, int TC, int TS, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Frame cleaning: the pipes the reference applies to raw microscope frames in front of ImageNorm, per whole frame,
+ * in the order ImageOutliers -> ImageBGSubtract -> ImageNorm (sequitr_amd/frontend.py: FrameClean, FrameTiler).
+ *   sq_frame_outliers_f32 : ImageOutliers (sequitr/pipeline.py:266-295: median_filter(image, sigma), then
+ *                           image[|image - med| > threshold] = med).  frames (F,H,W) SQ_PIX_* -> out (F,H,W) f32,
+ *                           BIT-EXACT: x = the pixel as float32; med = the element of rank size*size/2 (0-based,
+ *                           ascending) of the size x size window at offsets -(size/2) .. size-1-(size/2) along both
+ *                           axes, indices outside the frame mirrored with the edge pixel repeated (i < 0 -> -i-1,
+ *                           i >= L -> 2L-1-i: scipy's mode='reflect'); out = |x - med| > threshold ? med : x in
+ *                           float32.  For size 2 the window is the pixel with its upper and left neighbours and med
+ *                           the third smallest of the four.  size is 2 .. 5 and min(H, W) >= size (one reflection).
+ *   sq_frame_bgfit_f64    : ImageBGSubtract's fit (sequitr/pipeline.py:360-401: least squares of 1, u, v, u^2, uv, v^2
+ *                           over all pixels, u the column, v the row), in fp64 and in centred, scaled coordinates
+ *                               s = (u - (W-1)/2) / ((W-1)/2),  t = (v - (H-1)/2) / ((H-1)/2)   (both in [-1, 1]):
+ *                           coef (F,6) float64 with  bg(u, v) = c0 + c1 s + c2 t + c3 s^2 + c4 s t + c5 t^2.
+ *                           It is the reference's surface (the same polynomial space); the reference inverts A^T A in
+ *                           raw pixel coordinates, whose condition number grows as L^8.  Partial sums per strip of rows
+ *                           go to the workspace (sq_frame_bgfit_workspace bytes) and are added in a fixed order: results
+ *                           are the same bits on every run, and frame f's do not depend on F.  H, W >= 3, H*W <= 2^24.
+ *   sq_frame_bg_stats_f64 : float64 mean and standard deviation (np.std's definition) of the residual
+ *                           r = (double)x - bg(u, v) per frame; same workspace, same fixed-order reduction.
+ *   sq_frames_to_tiles_bg : sq_frames_to_tiles' geometry on the residual (sequitr/pipeline.py:402-405, then :350-356):
+ *                           (float)((r - mean[f]) / (1e-99 + stdv[f])) evaluated in fp64, or (float)r when
+ *                           mean == stdv == NULL.  The reference's result after ImageBGSubtract is float64; this is
+ *                           where the chain's one rounding to the network's float32 happens.
+ * F <= 65535 (a grid dimension).
+ * ---------------------------------------------------------------------------------------- */
+int sq_frame_outliers_f32(const void *frames, int dtype, float *out, int F, int H, int W, int size, float threshold,
+                          void *stream);
+int64_t sq_frame_bgfit_workspace(int F, int H, int W);
+int sq_frame_bgfit_f64(const float *frames, double *coef, void *workspace, int F, int H, int W, void *stream);
+int sq_frame_bg_stats_f64(const float *frames, const double *coef, double *mean, double *stdv, void *workspace, int F,
+                          int H, int W, void *stream);
+int sq_frames_to_tiles_bg(const float *frames, const double *coef, const double *mean, const double *stdv,
+                          const int32_t *oy, const int32_t *ox, float *tiles, int F, int H, int W, int TR, int TC, int TS,
+                          void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Volume front end: raw single-channel volumes (V, Z, X, Y) in HBM -> ImageNorm per volume -> network bricks, and
  * the brick-shaped network output back into full-volume arrays (sequitr_amd/frontend.py: volume_bricks, VolumeTiler).
  * A volume has KZ x KX x KY bricks of (BZ, BX, BY) voxels, numbered (v, kz, kx, ky) row-major.  `geom` is one int32

@@ -9,6 +9,10 @@ Tiling (build-defined: the reference only ever crops fixed-size tiles, pipeline.
 length L, tiles of size T start at 0, T-2m, 2(T-2m), ... and the last one at L-T; every pixel is owned by the
 tile in which it lies at least `m` (margin) pixels from the tile border, except at the frame border.
 
+In front of ImageNorm the reference's ImageOutliers (hot pixels, pipeline.py:266-295) and ImageBGSubtract (uneven
+illumination, pipeline.py:360-405) run on the device too, per whole frame before tiling (FrameClean, FrameTiler.outliers /
+background / tiles(clean=), segment_frames(clean=); include/sequitr_hip.h "Frame cleaning").
+
 Volumes take the same path in three dimensions (VolumeTiler, segment_volumes): a brick is a box of the network's
 input shape, the rule above holds along each axis, and an axis shorter than the brick is padded with the
 normalised mean, 0.
@@ -17,6 +21,7 @@ Training on volumes goes the other way round (sample_plan, VolumeSampler): the r
 stay in HBM and every step's batch of bricks is cut there at random origins under a random exact symmetry -- the
 reference's ImageSample, ImageFlip and the quarter turns of ImageRotate (sequitr/pipeline.py) in front of UNet3DTrain.
 """
+import json
 import os
 import time
 
@@ -94,6 +99,88 @@ def volume_bricks(vol_shape, brick, margin):
     return BrickGeometry(vol_shape, brick, margin)
 
 
+class FrameClean(object):
+    """What is done to a whole raw frame on the GPU in front of ImageNorm (include/sequitr_hip.h "Frame cleaning"), a plain
+    value: `outliers` is None or (size, threshold) of ImageOutliers (the pipe calls its window size `sigma`,
+    sequitr/pipeline.py:266-295), `bgsubtract` whether ImageBGSubtract follows.  The order is the only one the device
+    has: ImageOutliers -> ImageBGSubtract -> ImageNorm."""
+
+    PIPES = ('ImageOutliers', 'ImageBGSubtract', 'ImageNorm')
+
+    def __init__(self, outliers=None, bgsubtract=False):
+        if outliers is not None:
+            size, threshold = outliers
+            if isinstance(size, bool) or int(size) != size or not 2 <= int(size) <= 5:
+                raise ValueError('ImageOutliers: the window (sigma) is 2, 3, 4 or 5 on the device, got %r' % (size,))
+            outliers = (int(size), float(threshold))
+        self.outliers = outliers
+        self.bgsubtract = bool(bgsubtract)
+
+    def __eq__(self, other):
+        return isinstance(other, FrameClean) and (self.outliers, self.bgsubtract) == (other.outliers, other.bgsubtract)
+
+    def __hash__(self):
+        return hash((self.outliers, self.bgsubtract))
+
+    def __repr__(self):
+        return 'FrameClean(outliers=%r, bgsubtract=%r)' % (self.outliers, self.bgsubtract)
+
+    def __bool__(self):
+        return self.outliers is not None or self.bgsubtract
+
+    def pipes(self, normalise=True):
+        """the chain as SERVER_segment_frames records it: [{pipe name: its arguments}, ...]"""
+        chain = []
+        if self.outliers is not None:
+            chain.append({'ImageOutliers': {'sigma': self.outliers[0], 'threshold': self.outliers[1]}})
+        if self.bgsubtract:
+            chain.append({'ImageBGSubtract': {}})
+        if normalise:
+            chain.append({'ImageNorm': {}})
+        return chain
+
+    @classmethod
+    def from_pipeline(cls, pipeline):
+        """(clean or None, normalise) of an ImagePipeline, or of the path of the JSON ImagePipeline.save wrote.  Accepted
+        are exactly the subsequences of [ImageOutliers, ImageBGSubtract, ImageNorm] in that order; any other pipe, order
+        or duplicate, or an ImageOutliers.sigma outside 2 .. 5, raises ValueError naming the pipe (no CPU fallback)."""
+        from . import pipeline as pl
+        if isinstance(pipeline, str):
+            with open(pipeline, 'r') as f:
+                names = list(json.load(f, object_pairs_hook=lambda pairs: pairs)[0][1])
+            counts = {}
+            for name, _ in names:                               # a JSON object may repeat a key; load() keeps the last
+                counts[name] = counts.get(name, 0) + 1
+                if counts[name] > 1:
+                    raise ValueError('%s appears more than once in %s' % (name, pipeline))
+            pipeline = pl.ImagePipeline.load(pipeline)
+        if not isinstance(pipeline, pl.ImagePipeline):
+            raise TypeError('pipeline must be an ImagePipeline or the path of its JSON, got %r' % (pipeline,))
+        outliers, bgsubtract, normalise, stage = None, False, False, -1
+        for pipe in pipeline.pipeline:
+            name = pipe.__class__.__name__
+            if type(pipe) not in (pl.ImageOutliers, pl.ImageBGSubtract, pl.ImageNorm):
+                raise ValueError('%s does not run on whole frames on the GPU (only %s do, in that order)'
+                                 % (name, ', '.join(cls.PIPES)))
+            at = cls.PIPES.index(name)
+            if at == stage:
+                raise ValueError('%s appears more than once' % name)
+            if at < stage:
+                raise ValueError('%s comes after %s: the device order is %s' % (name, cls.PIPES[stage], ' -> '.join(cls.PIPES)))
+            stage = at
+            if at == 0:
+                try:
+                    outliers = cls(outliers=(pipe.sigma, pipe.threshold)).outliers
+                except (TypeError, ValueError) as e:
+                    raise ValueError('ImageOutliers(sigma=%r, threshold=%r): %s' % (pipe.sigma, pipe.threshold, e))
+            elif at == 1:
+                bgsubtract = True
+            else:
+                normalise = True
+        clean = cls(outliers, bgsubtract)
+        return (clean if clean else None), normalise
+
+
 class FrameTiler(object):
     """Geometry + device kernels for frames of one (H, W) shape."""
 
@@ -122,7 +209,7 @@ class FrameTiler(object):
         if tuple(frames.shape[1:]) != (self.H, self.W):
             raise ValueError('frames are %s, tiler was built for %s' % (tuple(frames.shape[1:]), (self.H, self.W)))
 
-    def stats(self, frames):
+    def stats(self, frames, scratch=None):
         """per-frame float32 (mean, std) exactly as np.mean / np.std of the float32 frame."""
         self._check_frames(frames)
         F = frames.shape[0]
@@ -130,18 +217,156 @@ class FrameTiler(object):
         nbytes = lib.sq_frame_stats_workspace(F, self.H, self.W)
         if nbytes < 0:
             raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
-        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-        mean = torch.empty(F, dtype=torch.float32, device=self.device)
-        std = torch.empty(F, dtype=torch.float32, device=self.device)
+        if scratch is not None:
+            ws, mean, std = scratch['stats_ws'], scratch['mean'][:F], scratch['std'][:F]
+        else:
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            mean = torch.empty(F, dtype=torch.float32, device=self.device)
+            std = torch.empty(F, dtype=torch.float32, device=self.device)
         _lib.check(lib.sq_frame_stats(frames.data_ptr(), PIX[frames.dtype], mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
                                       F, self.H, self.W, torch.cuda.current_stream().cuda_stream), 'sq_frame_stats')
         return mean, std
 
-    def tiles(self, frames, normalise=True):
-        """(F*TR*TC, T, T, 1) float32 tiles, ImageNorm applied per frame when `normalise`."""
+    def clean_scratch(self, F, clean, normalise=True):
+        """The tensors tiles(..., clean=clean) needs for up to F frames, so that a caller that streams batches (segment_frames)
+        allocates them once: the cleaned float32 frames and, per chain, the fit's coefficients, statistics and workspaces."""
+        if not clean:
+            return None
+        F, d, lib = int(F), self.device, _lib.load()
+        s = {'frames': F, 'f32': torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)}
+        if clean.bgsubtract:
+            nbytes = lib.sq_frame_bgfit_workspace(F, self.H, self.W)
+            if nbytes < 0:
+                raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
+                                 '%d x %d' % (F, self.H, self.W))
+            s['bg_ws'] = torch.empty(nbytes // 8, dtype=torch.float64, device=d)
+            s['coef'] = torch.empty((F, 6), dtype=torch.float64, device=d)
+            s['mean64'], s['std64'] = (torch.empty(F, dtype=torch.float64, device=d) for _ in range(2))
+        elif normalise:
+            nbytes = lib.sq_frame_stats_workspace(F, self.H, self.W)
+            if nbytes < 0:
+                raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
+            s['stats_ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=d)
+            s['mean'], s['std'] = (torch.empty(F, dtype=torch.float32, device=d) for _ in range(2))
+        return s
+
+    def _f32_out(self, F, out):
+        if out is None:
+            return torch.empty((F, self.H, self.W), dtype=torch.float32, device=self.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and tuple(out.shape) == (F, self.H, self.W)):
+            raise ValueError('out must be a contiguous (%d,%d,%d) float32 tensor in GPU memory' % (F, self.H, self.W))
+        return out
+
+    def _check_f32(self, frames):
         self._check_frames(frames)
+        if frames.dtype != torch.float32:
+            raise ValueError('the background fit reads float32 frames (outliers() or to_f32() make them), got %s' % frames.dtype)
+
+    def outliers(self, frames, size, threshold, out=None):
+        """ImageOutliers(sigma=size, threshold) of every raw frame: (F,H,W) float32, bit-exact with the host pipe."""
+        self._check_frames(frames)
+        size = FrameClean(outliers=(size, threshold)).outliers[0]
+        if min(self.H, self.W) < size:
+            raise ValueError('a window of %d does not fit frames of %d x %d' % (size, self.H, self.W))
         F = frames.shape[0]
-        mean, std = self.stats(frames) if normalise else (None, None)
+        out = self._f32_out(F, out)
+        _lib.check(_lib.load().sq_frame_outliers_f32(frames.data_ptr(), PIX[frames.dtype], out.data_ptr(), F, self.H, self.W,
+                                                     size, float(threshold), torch.cuda.current_stream().cuda_stream),
+                   'sq_frame_outliers_f32')
+        return out
+
+    def to_f32(self, frames, out=None):
+        """the raw frames cast to float32 (what ImagePipe.__call__ does first): float32 frames are returned as they are,
+        integer ones go through the volume front end's cast, every frame one brick of a one-slice volume"""
+        self._check_frames(frames)
+        if frames.dtype == torch.float32:
+            return frames
+        F = frames.shape[0]
+        out = self._f32_out(F, out)
+        if not hasattr(self, '_whole'):
+            self._whole = torch.tensor([0, 0, 0, 0, 0, 0, 1, self.H, self.W], dtype=torch.int32).to(self.device)
+        for lo in range(0, F, 65535):
+            n = min(65535, F - lo)
+            _lib.check(_lib.load().sq_volume_to_bricks(frames[lo:].data_ptr(), PIX[frames.dtype], None, None,
+                                                       self._whole.data_ptr(), out[lo:].data_ptr(), n, 1, self.H, self.W,
+                                                       1, 1, 1, 1, self.H, self.W, 0, n,
+                                                       torch.cuda.current_stream().cuda_stream), 'sq_volume_to_bricks')
+        return out
+
+    def _bg_workspace(self, F, scratch):
+        if scratch is not None:
+            return scratch['bg_ws']
+        nbytes = _lib.load().sq_frame_bgfit_workspace(F, self.H, self.W)
+        if nbytes < 0:
+            raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
+                             '%d x %d' % (F, self.H, self.W))
+        return torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+
+    def background(self, frames_f32, scratch=None):
+        """ImageBGSubtract's least-squares surface of every float32 frame: coef (F,6) float64 with
+        bg(u, v) = c0 + c1 s + c2 t + c3 s^2 + c4 s t + c5 t^2, s = (u - (W-1)/2) / ((W-1)/2) for column u and
+        t = (v - (H-1)/2) / ((H-1)/2) for row v (include/sequitr_hip.h "Frame cleaning")."""
+        self._check_f32(frames_f32)
+        F = frames_f32.shape[0]
+        ws = self._bg_workspace(F, scratch)
+        coef = scratch['coef'][:F] if scratch is not None else torch.empty((F, 6), dtype=torch.float64, device=self.device)
+        _lib.check(_lib.load().sq_frame_bgfit_f64(frames_f32.data_ptr(), coef.data_ptr(), ws.data_ptr(), F, self.H, self.W,
+                                                  torch.cuda.current_stream().cuda_stream), 'sq_frame_bgfit_f64')
+        return coef
+
+    def background_stats(self, frames_f32, coef, scratch=None):
+        """per-frame float64 (mean, std) of the residual frame - bg(coef), np.std's definition"""
+        self._check_f32(frames_f32)
+        F = frames_f32.shape[0]
+        self._check_coef(coef, F)
+        ws = self._bg_workspace(F, scratch)
+        if scratch is not None:
+            mean, std = scratch['mean64'][:F], scratch['std64'][:F]
+        else:
+            mean, std = (torch.empty(F, dtype=torch.float64, device=self.device) for _ in range(2))
+        _lib.check(_lib.load().sq_frame_bg_stats_f64(frames_f32.data_ptr(), coef.data_ptr(), mean.data_ptr(), std.data_ptr(),
+                                                     ws.data_ptr(), F, self.H, self.W,
+                                                     torch.cuda.current_stream().cuda_stream), 'sq_frame_bg_stats_f64')
+        return mean, std
+
+    def _check_coef(self, coef, F):
+        if not (isinstance(coef, torch.Tensor) and coef.is_cuda and coef.dtype == torch.float64 and coef.is_contiguous()
+                and tuple(coef.shape) == (F, 6)):
+            raise ValueError('coef must be the contiguous (%d,6) float64 tensor background() returned' % F)
+
+    def _tiles_clean(self, frames, normalise, clean, scratch):
+        """tiles() behind a FrameClean: the cleaned float32 frames are written once, every later kernel reads them"""
+        F = frames.shape[0]
+        if scratch is not None and scratch['frames'] < F:
+            raise ValueError('scratch was made for %d frames, got %d' % (scratch['frames'], F))
+        f32 = scratch['f32'][:F] if scratch is not None else None
+        if clean.outliers is not None:
+            x = self.outliers(frames, clean.outliers[0], clean.outliers[1], out=f32)
+        else:
+            x = self.to_f32(frames, out=f32)
+        if not clean.bgsubtract:                                # ImageNorm of the cleaned frames: the kernels of the plain path
+            return self.tiles(x, normalise=normalise, scratch=scratch)
+        coef = self.background(x, scratch=scratch)
+        mean, std = self.background_stats(x, coef, scratch=scratch) if normalise else (None, None)
+        out = torch.empty((F * self.TR * self.TC, self.T, self.T, 1), dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().sq_frames_to_tiles_bg(x.data_ptr(), coef.data_ptr(), mean.data_ptr() if normalise else None,
+                                                     std.data_ptr() if normalise else None, self._oy.data_ptr(),
+                                                     self._ox.data_ptr(), out.data_ptr(), F, self.H, self.W, self.TR, self.TC,
+                                                     self.T, torch.cuda.current_stream().cuda_stream), 'sq_frames_to_tiles_bg')
+        return out
+
+    def tiles(self, frames, normalise=True, clean=None, scratch=None):
+        """(F*TR*TC, T, T, 1) float32 tiles, ImageNorm applied per frame when `normalise`; with `clean` (a FrameClean) the
+        frames go through ImageOutliers and / or ImageBGSubtract first, per whole frame (`scratch`: clean_scratch(), for
+        callers that come back batch after batch)."""
+        self._check_frames(frames)
+        if clean:
+            if not isinstance(clean, FrameClean):
+                raise TypeError('clean must be a FrameClean, got %r' % (clean,))
+            return self._tiles_clean(frames, normalise, clean, scratch)
+        F = frames.shape[0]
+        mean, std = self.stats(frames, scratch if scratch and 'stats_ws' in scratch else None) if normalise else (None, None)
         out = torch.empty((F * self.TR * self.TC, self.T, self.T, 1), dtype=torch.float32, device=self.device)
         lib = _lib.load()
         _lib.check(lib.sq_frames_to_tiles(frames.data_ptr(), PIX[frames.dtype],
@@ -179,11 +404,13 @@ def _pinned(tag, shape, dtype):
     return buf
 
 
-def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None):
+def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None):
     """Segment a stack of raw frames (numpy array / memmap / OctopusData, (F,H,W) uint8|uint16|float32).
     Raw frames are staged through two pinned buffers and uploaded on a side stream while the previous batch is
     normalised, tiled, segmented (net.predict) and stitched; returns the (F,H,W) uint8 masks (host), or
-    streams each batch's device masks to on_masks(first_frame, masks) and returns None."""
+    streams each batch's device masks to on_masks(first_frame, masks) and returns None.  `clean` (a FrameClean) puts
+    ImageOutliers and / or ImageBGSubtract in front of ImageNorm, per whole frame, on the same stream: nothing on the host
+    waits between a batch's upload and its net.predict."""
     from .dataio.octopus import OctopusData
     if isinstance(frames, OctopusData):
         get = frames.block
@@ -202,6 +429,9 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     B = int(frames_per_batch)
     pinned = [_pinned('in%d' % i, (B, H, W), tdt) for i in range(2)]
     staged = [torch.empty((B, H, W), dtype=tdt, device=dev) for _ in range(2)]
+    if clean is not None and not isinstance(clean, FrameClean):
+        raise TypeError('clean must be a FrameClean or None, got %r' % (clean,))
+    scratch = tiler.clean_scratch(B, clean, normalise)          # once per call; the batches share it on the compute stream
     copy_stream = torch.cuda.Stream(device=dev)
     ready = [torch.cuda.Event(), torch.cuda.Event()]            # upload of buffer i finished
     freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[i]
@@ -237,8 +467,11 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         cur = torch.cuda.current_stream(dev)
         cur.wait_event(ready[k])
         n = counts[b]
-        tiles = tiler.tiles(staged[k][:n], normalise=normalise)
-        freed[k].record(cur)
+        if scratch is None:
+            tiles = tiler.tiles(staged[k][:n], normalise=normalise)
+        else:
+            tiles = tiler.tiles(staged[k][:n], normalise=normalise, clean=clean, scratch=scratch)
+        freed[k].record(cur)                                   # after the last kernel that reads staged[k]
         masks = tiler.stitch(net.predict(tiles))
         if on_masks is not None:
             on_masks(b * B, masks)

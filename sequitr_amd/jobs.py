@@ -347,15 +347,22 @@ def SERVER_segment_frames(params, options):
     (sequitr/dataio/octopus.py), a .npy of (F,H,W) uint8/uint16/float32 frames, or an ndarray.  Raw frames
     cross PCIe; ImageNorm, tiling, the U-Net and stitching run on the GPU (sequitr_amd/frontend.py).  Writes
     ``mask.npy`` (F,H,W) uint8, ``segment.json`` and, with options['centroids'], the centroid file.
-    params: shape (tile, default (512,512)), margin, frames_per_batch, model / filters / ... as SERVER_segment."""
+    params: shape (tile, default (512,512)), margin, frames_per_batch, model / filters / ... as SERVER_segment;
+    pipeline: the JSON ImagePipeline.save wrote (or an ImagePipeline).  It runs on the GPU per whole frame and may hold
+    any subsequence of ImageOutliers, ImageBGSubtract, ImageNorm in that order (frontend.FrameClean.from_pipeline; anything
+    else raises before a frame is read -- there is no host fallback); segment.json records it under 'pipeline'.  Without
+    it the frames are normalised with ImageNorm alone."""
     import torch
     from .networks.unet import UNet2D
     from . import utils
-    from .frontend import segment_frames
+    from .frontend import FrameClean, segment_frames
     from .dataio import OctopusData
 
     device = _resolve_device(params, options)
     out_dir = params['output']
+    clean, normalise = None, True
+    if params.get('pipeline') is not None:
+        clean, normalise = FrameClean.from_pipeline(params['pipeline'])
     src = params.get('input')
     if isinstance(src, str) and not src.endswith('.npy'):
         frames = OctopusData(src, timeout=params.get('timeout', 60))
@@ -391,7 +398,8 @@ def SERVER_segment_frames(params, options):
     # without centroids the masks come back through segment_frames' own double-buffered download (batch i-1 drains
     # while batch i runs); with them every batch is visited on the device first
     out = segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)),
-                         frames_per_batch=int(params.get('frames_per_batch', 4)), on_masks=sink if want_centroids else None)
+                         frames_per_batch=int(params.get('frames_per_batch', 4)), on_masks=sink if want_centroids else None,
+                         normalise=normalise, clean=clean)
     if not want_centroids:
         masks = out
     torch.cuda.synchronize()
@@ -399,6 +407,8 @@ def SERVER_segment_frames(params, options):
     np.save(os.path.join(out_dir, 'mask.npy'), masks)
     info = {'frames': int(F), 'shape': [int(H), int(W)], 'tile': tile, 'seconds': dt,
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
+    if params.get('pipeline') is not None:
+        info['pipeline'] = (clean or FrameClean()).pipes(normalise)
     if options.get('centroids'):
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:

@@ -1,0 +1,140 @@
+"""Case frames and numpy restatements for frame cleaning on the GPU (include/sequitr_hip.h "Frame cleaning").
+
+The definitions of record are the host classes of sequitr_amd/pipeline.py, pinned to the reference's own output by
+tests/test_pipeline.py.  Restated here, and checked against them in tests/test_frame_clean_cpu.py:
+  * the rank filter of ImageOutliers, written out index by index (no scipy);
+  * the background fit as least squares in centred, scaled coordinates, refined in np.longdouble -- the oracle of the
+    device fit.  The host pipe inverts A^T A in raw pixel coordinates; it is the same surface up to its own rounding.
+"""
+import functools
+import os
+
+import numpy as np
+
+from sequitr_amd import pipeline
+
+GOLDEN = np.load(os.path.join(os.path.dirname(__file__), "golden", "pipeline_golden.npz"))
+
+# (F, H, W), dtype.  The last: a width that is no multiple of 4 or of any tile, one row past a 32-row tile, and a row
+# wide enough for more than one block.
+CASES = [((1, 7, 5), np.uint8), ((2, 48, 40), np.float32), ((3, 37, 53), np.uint16), ((2, 96, 80), np.float32),
+         ((1, 150, 210), np.uint16), ((1, 257, 1031), np.uint16)]
+CASE_IDS = ["%dx%dx%d-%s" % (s + (np.dtype(d).name,)) for s, d in CASES]
+SIZES = (2, 3, 4, 5)
+
+
+def _hot_positions(H, W, rng):
+    """corners, the middle of each edge, a horizontal and a vertical pair, and about 1 % of the pixels at random"""
+    pos = {(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (0, W // 2), (H - 1, W // 2), (H // 2, 0), (H // 2, W - 1),
+           (H // 3, W // 3), (H // 3, W // 3 + 1), (2 * H // 3, W // 2), (2 * H // 3 + 1, W // 2)}
+    n = (H * W) // 100
+    pos |= set(zip(rng.integers(0, H, n).tolist(), rng.integers(0, W, n).tolist()))
+    ys, xs = zip(*sorted(pos))
+    return np.asarray(ys), np.asarray(xs)
+
+
+@functools.lru_cache(maxsize=None)
+def frames(case):
+    """the frames of CASES[case]: a smooth quadratic ramp plus noise, hot pixels far above any threshold used; no NaN,
+    no negative zero.  Frame 0 of the (2, 48, 40) float32 case is the golden file's img_in.  Read only."""
+    (F, H, W), dtype = CASES[case]
+    rng = np.random.default_rng(100 + case)
+    v, u = np.mgrid[0:H, 0:W].astype(np.float64)
+    s, t = u / max(W - 1, 1) - 0.5, v / max(H - 1, 1) - 0.5
+    level, noise, hot = (60., 3., 150.) if dtype == np.uint8 else (1500., 12., 4000.)
+    out = np.empty((F, H, W), dtype)
+    for f in range(F):
+        a = rng.uniform(-0.4, 0.4, 5)
+        img = level * (1 + a[0] * s + a[1] * t + a[2] * s * s + a[3] * s * t + a[4] * t * t) + noise * rng.standard_normal((H, W))
+        ys, xs = _hot_positions(H, W, rng)
+        img[ys, xs] += hot * rng.uniform(0.8, 1.0, len(ys))
+        out[f] = np.rint(img) if dtype != np.float32 else img
+    if dtype == np.float32 and (H, W) == GOLDEN["img_in"].shape:
+        out[0] = GOLDEN["img_in"]
+    out[out == 0] = 0                                           # -0.0 -> +0.0
+    out.setflags(write=False)
+    return out
+
+
+def as_float32(frame):
+    """what a pipe sees of a raw 2-D frame: ImagePipe.__call__'s cast (and OctopusData's before it)"""
+    return np.array(frame, dtype="float").astype("float32")
+
+
+def _reflect(i, L):
+    i = np.where(i < 0, -i - 1, i)
+    return np.where(i >= L, 2 * L - 1 - i, i)
+
+
+def median_restated(x, size):
+    """the element of rank size*size // 2 (0-based, ascending) of the size x size window at offsets -(size // 2) ..
+    size - 1 - (size // 2) along both axes, indices outside the frame mirrored with the edge pixel repeated"""
+    H, W = x.shape
+    assert min(H, W) >= size
+    offs = np.arange(size) - size // 2
+    stack = [x[_reflect(np.arange(H) + dy, H)][:, _reflect(np.arange(W) + dx, W)] for dy in offs for dx in offs]
+    return np.sort(np.stack(stack, -1), axis=-1)[..., size * size // 2]
+
+
+def outliers_restated(frame, size, threshold):
+    x = as_float32(frame)
+    med = median_restated(x, size)
+    return np.where(np.abs(x - med) > np.float32(threshold), med, x).astype(np.float32)
+
+
+def outliers_host(frame, size, threshold):
+    """pipeline.ImageOutliers on one raw frame: (H, W) float32"""
+    return pipeline.ImageOutliers(size, threshold)(np.array(frame))[..., 0]
+
+
+def scaled_axes(H, W):
+    """the centred, scaled coordinates of the header: s per column, t per row, both in [-1, 1]"""
+    cu, cv = (W - 1) / 2., (H - 1) / 2.
+    return (np.arange(W, dtype=np.float64) - cu) / cu, (np.arange(H, dtype=np.float64) - cv) / cv
+
+
+def basis_surface(coef, H, W):
+    """bg(u, v) = c0 + c1 s + c2 t + c3 s^2 + c4 s t + c5 t^2 in numpy float64, from a (6,) coefficient vector"""
+    s, t = scaled_axes(H, W)
+    s, t = s[None, :], t[:, None]
+    c = np.asarray(coef, np.float64)
+    return c[0] + c[1] * s + c[2] * t + c[3] * s * s + c[4] * s * t + c[5] * t * t
+
+
+def oracle_fit(x):
+    """least squares of the six basis functions over all pixels of x (any float dtype) in centred, scaled coordinates,
+    solved in float64 and refined in np.longdouble: (surface (H, W) float64, coefficients (6,) float64)"""
+    H, W = x.shape
+    s, t = scaled_axes(H, W)
+    s, t = np.broadcast_to(s[None, :], (H, W)).ravel(), np.broadcast_to(t[:, None], (H, W)).ravel()
+    A = np.stack([np.ones(H * W), s, t, s * s, s * t, t * t], 1)
+    Al, b = A.astype(np.longdouble), np.asarray(x, np.longdouble).ravel()
+    k = np.zeros(6, np.longdouble)
+    for _ in range(3):                                          # each pass solves for what the last one left over
+        k = k + np.linalg.lstsq(A, (b - Al.dot(k)).astype(np.float64), rcond=None)[0]
+    return np.asarray(Al.dot(k), np.float64).reshape(H, W), np.asarray(k, np.float64)
+
+
+def delta(x):
+    """the bound on a surface error: 2^-32 of the frame's largest magnitude -- 2^7 below the float32 half-ulp of that
+    pixel, about 2^20 above fp64 rounding"""
+    return 2.0 ** -32 * float(np.max(np.abs(np.asarray(x, np.float64))))
+
+
+def oracle_chain(frame, outliers=None, bgsubtract=False, normalise=True):
+    """one raw frame through the chain: (z (H, W) float64 before the rounding to float32, std that divided it or 1.0,
+    delta of the frame the fit saw or 0.0).  Outliers and a lone ImageNorm act in float32 as the host pipes do."""
+    x = outliers_host(frame, *outliers) if outliers is not None else as_float32(frame)
+    d = 0.0
+    if bgsubtract:
+        d = delta(x)
+        x = x.astype(np.float64) - oracle_fit(x)[0]
+    std = 1.0
+    if normalise:
+        std = np.std(x)
+        x = (x - np.mean(x)) / (1e-99 + std)
+    return np.asarray(x, np.float64), float(std), d
+
+
+def ulp32(z):
+    return np.spacing(np.abs(z).astype(np.float32)).astype(np.float64)
