@@ -981,6 +981,52 @@ int sq_volume_sample_copy(const void *src, int elem_bytes, const int32_t *plan, 
 int sq_volume_sample_onehot_u8(const uint8_t *labels, int C, const int32_t *plan, uint8_t *out, int V, int Z, int X, int Y,
                                int BZ, int BX, int BY, int count, int allow_transpose, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tile sampler: the planar twin of the volume sampler, and the one interpolating op of the pipeline -- the reference's
+ * tr_augment (sequitr/networks/unet.py:348-401: per element one random angle, image and weight map rotated bilinearly,
+ * labels by nearest neighbour, 1 - rotate(ones, NEAREST) added to the weights, a random crop of the network's shape,
+ * one-hot labels; sequitr_amd/frontend.py: tile_sample_plan, TileSampler).  Raw frames (F, H, W) SQ_PIX_*, class-index
+ * labels (F, H, W) uint8 and weight maps (F, H, W) f32 stay in HBM.  A sample is two rows in HBM:
+ *     plan[k] = [f, oy, ox, 0]  int32 (the fourth entry is reserved and ignored),
+ *     coef[k] = [a0, a1, a2, b0, b1, b2]  float32.
+ * TensorFlow's parity is unpinned; this text is the contract.  It restates TF 1.x's angles_to_projective_transforms and
+ * ImageProjectiveTransform.  For pixel (i, j) of sample k, with tiles of (TH, TW) and frames (F, H, W):
+ *
+ *     x = float32(ox + j);  y = float32(oy + i)
+ *     sx = (a0*x + a1*y) + a2;   sy = (b0*x + b1*y) + b2     # float32, every * and + rounded on its own, no FMA
+ *     read_T(r, c) = T[f, r, c] if 0 <= f < F and 0 <= r < H and 0 <= c < W else 0
+ *     bilinear(T):  x0 = floor(sx), y0 = floor(sy), x1 = x0 + 1, y1 = y0 + 1
+ *         top = (x1 - sx) * read_T(y0, x0) + (sx - x0) * read_T(y0, x1)
+ *         bot = (x1 - sx) * read_T(y1, x0) + (sx - x0) * read_T(y1, x1)
+ *         val = (y1 - sy) * top + (sy - y0) * bot
+ *     nearest:  r = roundf(sy), c = roundf(sx)  (half away from zero);  inside = (r, c) in the frame and 0 <= f < F
+ *     image  [k,i,j,0] = bilinear(normalised frame)
+ *     onehot [k,i,j,q] = (read_labels(r, c) == q)                            # label 0 outside; label >= C: all zero
+ *     weights[k,i,j,0] = bilinear(weight map) + (inside ? 0.0f : 1.0f)
+ *
+ * Normalised frame: a frame pixel read for the image is (float(v) - mean[f]) / std[f], sq_frames_to_tiles' expression with
+ * sq_frame_stats' statistics of the whole frame, or the plain cast when mean == std == NULL; a corner outside the frame
+ * reads 0.0f, the frame's mean.  ox + j and oy + i are exact integer sums, rounded once to float32.  A pixel whose sx or
+ * sy is NaN, or at or beyond +-2^23, reads fill everywhere: image 0, label 0, weight 1.  No load ever leaves the arrays:
+ * plan and coef are data, and the kernel trusts none of it.  The kernel knows nothing about angles; it takes any affine
+ * rows (tile_sample_plan writes a rotation about the frame's centre, optionally composed with mirrors of the tile).
+ *   sq_tile_sample_affine : out_image (count, TH, TW) f32, out_onehot (count, TH, TW, C) uint8, out_weights
+ *                           (count, TH, TW) f32, one launch.  Each of the pairs (frames, out_image), (labels, out_onehot),
+ *                           (weights, out_weights) may be NULL together, which skips that output; any other NULL, a
+ *                           half-NULL pair, C outside 1 .. 16, count outside 1 .. 65535, a non-positive size or
+ *                           H*W > 2^24 is refused before any launch.
+ * A block owns a 32 x 32 patch of one tile, so that its source footprint is compact at any angle, and gathers the four
+ * corners of every pixel directly.  With SQ_ROTATE_LDS=1 (read per launch) it stages the bounding box of the patch's
+ * footprint (the four corner coordinates, plus the bilinear apron) into LDS with loads that run along the frame's rows,
+ * and interpolates from there; a block whose box exceeds 48 x 48 pixels (a zooming or shearing row) still gathers
+ * directly.  SQ_ROTATE_LDS=0 selects the direct gather everywhere.  Unset is the direct gather, the faster form as
+ * measured (tools/tile_sampler_bench.py); both give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+int sq_tile_sample_affine(const void *frames, int dtype, const float *mean, const float *stdv, const uint8_t *labels,
+                          const float *weights, const int32_t *plan, const float *coef, float *out_image,
+                          uint8_t *out_onehot, float *out_weights, int F, int H, int W, int TH, int TW, int C, int count,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

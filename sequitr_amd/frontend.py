@@ -20,6 +20,10 @@ normalised mean, 0.
 Training on volumes goes the other way round (sample_plan, VolumeSampler): the raw volumes, their labels and weight maps
 stay in HBM and every step's batch of bricks is cut there at random origins under a random exact symmetry -- the
 reference's ImageSample, ImageFlip and the quarter turns of ImageRotate (sequitr/pipeline.py) in front of UNet3DTrain.
+
+Training on whole frames is the planar twin (tile_sample_plan, TileSampler): raw frames, class-index labels and weight
+maps stay in HBM and every step's batch of tiles is sampled there under a random rotation, bilinear for image and weights,
+nearest for the labels -- the reference's tr_augment (sequitr/networks/unet.py:348-401) in front of SERVER_train's step.
 """
 import json
 import os
@@ -818,6 +822,156 @@ class VolumeSampler(object):
         _lib.check(_lib.load().sq_volume_sample_onehot_u8(labels.data_ptr(), C, plan.data_ptr(), out.data_ptr(),
                                                           *self._dims(labels.shape[0], count)), 'sq_volume_sample_onehot_u8')
         return out
+
+
+def covering_tiles(frame_shape, tile):
+    """how many margin-0 tiles cover one (H, W) frame (axis_tiles' rule; one along an axis shorter than the tile)"""
+    return int(np.prod([len(axis_tiles(L, T, 0)[0]) if T <= L else 1 for L, T in zip(frame_shape, tile)]))
+
+
+def tile_sample_plan(frame_shape, tile, frames, count, rng, augment=('rotate',), theta=None):
+    """The rows of a tile sampler launch (include/sequitr_hip.h "Tile sampler"), host only: (plan (count, 4) int32 rows
+    [f, oy, ox, 0], coef (count, 6) float32 rows [a0, a1, a2, b0, b1, b2]).  frame_shape is (H, W), tile (TH, TW), `frames`
+    the number of frames, `rng` a numpy.random.Generator.  f is uniform over the frames; an origin is uniform over
+    [0, L - T] inclusive along its axis, and 0 along an axis shorter than the tile (sample_plan's stated deviation from the
+    reference's exclusive maxval).  theta is uniform in [0, 2 pi) under 'rotate', else 0; an explicit `theta` array (count
+    values) overrides it.  The coefficients are TF 1.x's angles_to_projective_transforms, a rotation about the frame's
+    centre, computed in float64 and rounded once to float32:
+
+        c = cos theta, s = sin theta
+        a = (c, -s, ((W-1) - (c (W-1) - s (H-1))) / 2)
+        b = (s,  c, ((H-1) - (s (W-1) + c (H-1))) / 2)
+
+    'flip' draws ImageFlip's two mirror bits and composes j -> TW-1-j and / or i -> TH-1-i into the row in float64, before
+    the rounding.  The default ('rotate',) is exactly tr_augment (sequitr/networks/unet.py:348-401)."""
+    shape, tile = tuple(int(s) for s in frame_shape), tuple(int(s) for s in tile)
+    if len(shape) != 2 or len(tile) != 2 or min(shape + tile) < 1:
+        raise ValueError('frame_shape and tile are (H, W) pairs of positive sizes, got %r and %r' % (frame_shape, tile))
+    frames, count = int(frames), int(count)
+    if frames < 1 or count < 1:
+        raise ValueError('need at least one frame and one sample, got %d and %d' % (frames, count))
+    augment = (augment,) if isinstance(augment, str) else tuple(augment)
+    unknown = [a for a in augment if a not in ('rotate', 'flip')]
+    if unknown:
+        raise ValueError("augment holds 'rotate' and / or 'flip', got %r" % (unknown,))
+    (H, W), (TH, TW) = shape, tile
+    plan = np.zeros((count, 4), np.int32)
+    plan[:, 0] = rng.integers(0, frames, count)
+    plan[:, 1] = rng.integers(0, max(H - TH, 0) + 1, count)
+    plan[:, 2] = rng.integers(0, max(W - TW, 0) + 1, count)
+    drawn = rng.uniform(0., 2. * np.pi, count) if 'rotate' in augment else np.zeros(count)
+    if theta is not None:
+        drawn = np.asarray(theta, np.float64).reshape(-1)
+        if drawn.shape != (count,):
+            raise ValueError('theta must hold one angle per sample (%d), got %d' % (count, drawn.size))
+    c, s = np.cos(drawn), np.sin(drawn)
+    coef = np.empty((count, 6), np.float64)
+    coef[:, 0], coef[:, 1], coef[:, 2] = c, -s, ((W - 1) - (c * (W - 1) - s * (H - 1))) / 2.
+    coef[:, 3], coef[:, 4], coef[:, 5] = s, c, ((H - 1) - (s * (W - 1) + c * (H - 1))) / 2.
+    if 'flip' in augment:
+        bits = rng.integers(0, 4, count)
+        oy, ox = plan[:, 1].astype(np.float64), plan[:, 2].astype(np.float64)
+        mx, my = (bits & 1) != 0, (bits & 2) != 0
+        # x = ox + j becomes ox + TW-1-j = (2 ox + TW-1) - x, and y likewise
+        for col, m, pivot in ((0, mx, 2. * ox + (TW - 1)), (1, my, 2. * oy + (TH - 1))):
+            for base in (0, 3):
+                coef[:, base + 2] = np.where(m, coef[:, base + 2] + coef[:, base + col] * pivot, coef[:, base + 2])
+                coef[:, base + col] = np.where(m, -coef[:, base + col], coef[:, base + col])
+    return plan, coef.astype(np.float32)
+
+
+class TileSampler(object):
+    """Rotated training tiles cut on the GPU out of whole frames, labels and weight maps that stay in HBM -- the planar twin
+    of VolumeSampler and the device form of the reference's tr_augment (include/sequitr_hip.h "Tile sampler").  `plan` and
+    `coef` are tile_sample_plan's rows (or a slice of them) in GPU memory; one launch fills all three outputs."""
+
+    def __init__(self, frame_shape, tile, device=None):
+        self.shape, self.tile = tuple(int(s) for s in frame_shape), tuple(int(s) for s in tile)
+        if len(self.shape) != 2 or len(self.tile) != 2 or min(self.shape + self.tile) < 1:
+            raise ValueError('frame_shape and tile are (H, W) pairs of positive sizes, got %r and %r' % (frame_shape, tile))
+        if self.shape[0] * self.shape[1] > 1 << 24:
+            raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % self.shape)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise _lib.SequitrHipError('TileSampler runs on the HIP back end only')
+        self._tiler = None
+
+    def stats(self, frames):
+        """per-frame float32 (mean, std) of the whole frames: FrameTiler.stats"""
+        if self._tiler is None:
+            self._tiler = FrameTiler(self.shape, min(self.shape), 0, device=self.device)
+        return self._tiler.stats(frames)
+
+    def _check(self, t, what, dtypes, channel=False):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SequitrHipError('%s must be a tensor in GPU memory (no CPU fallback exists)' % what)
+        dims = (3, 4) if channel else (3,)
+        if t.dtype not in dtypes or t.dim() not in dims or not t.is_contiguous() or (t.dim() == 4 and t.shape[3] != 1):
+            raise ValueError('%s must be a contiguous (F,H,W%s) %s tensor' % (
+                what, '[,1]' if channel else '', ' / '.join(str(d).replace('torch.', '') for d in dtypes)))
+        if tuple(t.shape[1:3]) != self.shape or t.shape[0] < 1:
+            raise ValueError('%s are %s, sampler was built for %s' % (what, tuple(t.shape[1:3]), self.shape))
+        return int(t.shape[0])
+
+    def _rows(self, t, what, width, dtype):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.SequitrHipError('%s must be a tensor in GPU memory (no CPU fallback exists)' % what)
+        if t.dtype != dtype or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous (count, %d) %s tensor, got %s %s' % (what, width, dtype, t.dtype, tuple(t.shape)))
+        return int(t.shape[0])
+
+    def _out(self, out, count, tail, dtype):
+        shape = (count,) + self.tile + (tail,)
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise _lib.SequitrHipError('out must hold tensors in GPU memory (no CPU fallback exists)')
+        if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError('out must be a contiguous %s tensor of %s, got %s %s' % (dtype, shape, out.dtype, tuple(out.shape)))
+        return out
+
+    def sample(self, frames, labels, weights, plan, coef, C, normalise=True, stats=None, out=None):
+        """(image (count, TH, TW, 1) float32, onehot (count, TH, TW, C) uint8, weights (count, TH, TW, 1) float32) of the raw
+        (F, H, W) uint8 / uint16 / float32 frames, the class-index uint8 labels and the float32 weight maps (F, H, W[, 1]).
+        Any of the three sources may be None, and its output is then None.  ImageNorm is applied per whole frame when
+        `normalise` (with `stats` = self.stats(frames) when the caller already has them).  `out` takes the three
+        preallocated tensors (None for a source that is None)."""
+        count = self._rows(plan, 'plan', 4, torch.int32)
+        if self._rows(coef, 'coef', 6, torch.float32) != count:
+            raise ValueError('plan has %d rows, coef %d' % (count, coef.shape[0]))
+        if not 1 <= count <= 65535:
+            raise ValueError('a plan of %d rows is not one launch (1 .. 65535 rows)' % count)
+        C = int(C)
+        if not 1 <= C <= 16:
+            raise ValueError('%d classes are not 1 .. 16' % C)
+        if frames is None and labels is None and weights is None:
+            raise ValueError('give at least one of frames, labels and weights')
+        F = [self._check(t, what, dt, ch) for t, what, dt, ch in (
+            (frames, 'frames', tuple(PIX), False), (labels, 'labels', (torch.uint8,), False),
+            (weights, 'weights', (torch.float32,), True)) if t is not None]
+        if len(set(F)) != 1:
+            raise ValueError('frames, labels and weights must hold the same number of frames, got %r' % (F,))
+        F = F[0]
+        if out is None:
+            out = (None, None, None)
+        if len(out) != 3:
+            raise ValueError('out takes the three tensors (image, onehot, weights)')
+        mean = std = None
+        if frames is not None and normalise:
+            mean, std = stats if stats is not None else self.stats(frames)
+            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == F
+                       and t.is_contiguous() for t in (mean, std)):
+                raise ValueError('stats must be the (mean, std) float32 tensors of these %d frames in GPU memory' % F)
+        o_img = self._out(out[0], count, 1, torch.float32) if frames is not None else None
+        o_hot = self._out(out[1], count, C, torch.uint8) if labels is not None else None
+        o_wts = self._out(out[2], count, 1, torch.float32) if weights is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(_lib.load().sq_tile_sample_affine(ptr(frames), PIX[frames.dtype] if frames is not None else 0, ptr(mean),
+                                                     ptr(std), ptr(labels), ptr(weights), plan.data_ptr(), coef.data_ptr(),
+                                                     ptr(o_img), ptr(o_hot), ptr(o_wts), F, self.shape[0], self.shape[1],
+                                                     self.tile[0], self.tile[1], C, count,
+                                                     torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine')
+        return o_img, o_hot, o_wts
 
 
 class TileStreamer(object):

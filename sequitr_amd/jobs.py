@@ -438,6 +438,140 @@ def _onehot(labels, num_outputs):
     return np.stack([(labels == c) for c in range(num_outputs)], -1).astype(np.uint8)
 
 
+def _train_frame_tiles(params, options):
+    """SERVER_train with params['tile']: whole raw frames of any size, their class-index labels and weight maps stay in
+    HBM, and every step's batch of rotated tiles is cut there by one kernel (frontend.tile_sample_plan, TileSampler) --
+    the reference's tr_augment (sequitr/networks/unet.py:348-401) in front of the captured step."""
+    world = int(os.environ.get('WORLD_SIZE', 1))
+    if world > 1:
+        raise RuntimeError("params['tile'] samples frames in a single process: WORLD_SIZE is %d (data-parallel frame "
+                           "sampling is not built)" % world)
+    from .frontend import NP_TORCH, covering_tiles, tile_sample_plan
+    tile = tuple(params['tile'])
+    if len(tile) != 2:
+        raise ValueError("params['tile'] must be (TH, TW), got %r" % (params['tile'],))
+    th, tw = (int(s) for s in tile)
+    x = np.load(params['images'], mmap_mode='r', allow_pickle=False)
+    if x.ndim == 4 and x.shape[3] == 1:
+        x = x[..., 0]
+    if x.ndim != 3 or int(params.get('num_inputs', 1)) != 1:
+        raise ValueError("params['tile'] trains on single-channel (F, H, W) frame stacks only, got shape %s" % (x.shape,))
+    if np.dtype(x.dtype) not in NP_TORCH:
+        raise TypeError("with params['tile'] the images must be raw uint8, uint16 or float32 frames, got %s" % x.dtype)
+    F, H, W = (int(s) for s in x.shape)
+    labels = np.load(params['labels'], mmap_mode='r', allow_pickle=False)
+    if labels.ndim != 3:
+        raise ValueError("with params['tile'] the labels are (F, H, W) class indices, one byte per pixel; one-hot labels "
+                         "of shape %s are not taken" % (labels.shape,))
+    if tuple(labels.shape) != (F, H, W):
+        raise ValueError('labels %s do not match the images %s' % (labels.shape, x.shape))
+    augment = params.get('augment')
+    augment = ('rotate',) if augment is None else ((augment,) if isinstance(augment, str) else tuple(augment))
+    seed = int(params.get('seed', 0))
+    rng = np.random.default_rng(seed)
+    tile_sample_plan((H, W), (th, tw), F, 1, np.random.default_rng(0), augment)      # refuses a bad `augment` before any upload
+    samples = params.get('samples_per_epoch')
+    samples = F * covering_tiles((H, W), (th, tw)) if samples is None else int(samples)
+    if samples < 1:
+        raise ValueError('samples_per_epoch must be positive, got %d' % samples)
+
+    import torch
+    from . import utils
+    from .frontend import TileSampler
+    from .train import UNetTrainer
+    from .weightmap import device_weightmaps
+
+    cfg_keys = ('name', 'num_outputs', 'num_epochs', 'learning_rate', 'warm_start', 'dropout')
+    cfg = {k: params[k] for k in cfg_keys if k in params}
+    cfg['shape'], cfg['num_inputs'] = (th, tw), 1              # net.config records the tile: the shape the model segments at
+    config = utils.NetConfiguration.from_params(cfg)
+    n_out = int(config.num_outputs)
+    device = _resolve_device(params, options)
+    torch.cuda.set_device(torch.device(device))
+    dev = torch.device(device)
+
+    def upload(arr, np_dtype):
+        """host array or memmap -> HBM as it is, one frame at a time (no whole-stack host copy)"""
+        t = torch.empty((F, H, W), dtype=NP_TORCH[np.dtype(np_dtype)], device=dev)
+        for i in range(F):
+            t[i].copy_(torch.from_numpy(np.array(arr[i], dtype=np_dtype, order='C')))   # a copy: arr is a read-only memmap
+        return t
+
+    x_dev = upload(x, x.dtype)
+    y_dev = upload(labels, np.uint8)
+    if params.get('weights'):
+        w_dev = upload(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((F, H, W)), np.float32)
+    else:
+        # once, on the whole frames; the rotation then interpolates the map, as the reference rotates its precomputed TIFFs
+        w_dev = device_weightmaps(y_dev, params.get('w0', 10.), params.get('sigma', 5.))
+    sampler = TileSampler((H, W), (th, tw), dev)
+    normalise = bool(params.get('normalise', True))
+    stats = sampler.stats(x_dev) if normalise else None         # ImageNorm of each WHOLE frame, as segment_frames applies it
+
+    net_p = _net_params(params, device)
+    net_p['shape'] = (th, tw)
+    net_p['num_inputs'], net_p['num_outputs'] = 1, n_out
+    net_p['dropout'] = float(params.get('dropout', 0.4))
+    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'))
+    config.learning_rate = trainer.lr
+    config.warmup_steps = trainer.warmup_steps
+    if config.warm_start:
+        latest = config.warm_start_from()
+        if latest:
+            trainer.load_state_dict(utils.load_model_weights(latest))
+            logger.info('Warm start from {0:s}'.format(latest))
+
+    batch = max(1, min(int(params.get('batch_size', 16)), samples))
+    steps_per_epoch = samples // batch
+    epochs = int(params.get('num_epochs', config.num_epochs))
+    max_steps = options.get('max_steps')
+    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    bufs = [torch.empty((batch, th, tw, 1), dtype=torch.float32, device=dev),
+            torch.empty((batch, th, tw, n_out), dtype=torch.uint8, device=dev),
+            torch.empty((batch, th, tw, 1), dtype=torch.float32, device=dev)]
+    use_graph = bool(options.get('graph', True))
+    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    done, steady_from = 0, 0
+    t_start = t_steady = time.time()
+    for epoch in range(epochs):
+        if done >= total_steps:
+            break
+        plan, coef = (torch.from_numpy(a).to(dev) for a in tile_sample_plan((H, W), (th, tw), F, samples, rng, augment))
+        for s in range(steps_per_epoch):                       # ONE plan upload per epoch; a step takes a slice of it
+            if done >= total_steps:
+                break
+            sl = slice(s * batch, (s + 1) * batch)
+            sampler.sample(x_dev, y_dev, w_dev, plan[sl], coef[sl], n_out, normalise=normalise, stats=stats, out=bufs)
+            if use_graph and done == 0:
+                # as SERVER_train's tile path: the first step is eager, then the step is captured and the sampler writes
+                # straight into the capture's static input buffers
+                trainer.capture(*bufs, warmup=1)
+                bufs[:] = trainer.static_inputs
+                loss_log[0].copy_(trainer.last_loss)
+            else:
+                loss_log[done].copy_(trainer.step(*bufs))
+            done += 1
+            if done == 1:                                      # the first step carries the first-launch costs
+                torch.cuda.synchronize()
+                t_steady, steady_from = time.time(), 1
+    torch.cuda.synchronize()
+    t_end = time.time()
+    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
+    steady = done - steady_from
+    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
+            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady) * 1e3 / steady if steady > 0 else None,
+            'steady_steps': steady, 'batch_size': batch, 'frames': F, 'frame_shape': [H, W], 'tile': [th, tw],
+            'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed, 'normalise': normalise,
+            'graph': use_graph, 'dtype': str(net_p.get('dtype', 'f32')), 'warmup_steps': trainer.warmup_steps,
+            'learning_rate': trainer.lr, 'world': 1, 'device': device}
+    info['model_dir'] = utils.save_model(trainer.state_dict(), config)
+    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
+        json.dump(dict(info, losses=losses), f, indent=2)
+    logger.info('Trained {steps} steps on rotated tiles of whole frames, loss {first_loss} -> {last_loss}, saved '
+                '{model_dir}'.format(**info))
+    return info
+
+
 def SERVER_train(params, options):
     """Train the U-Net on a stack of tiles with the weight-map-weighted softmax cross-entropy.
 
@@ -459,7 +593,18 @@ def SERVER_train(params, options):
     (WORLD_SIZE > 1) the tiles shard across ranks and gradients are all-reduced over RCCL once per step, between
     the two graphs.  Rank 0 saves ``weights.npz`` + ``net.config`` into the next numbered folder of MODELDIR/<name>/
     (sequitr/utils.py:143-223 layout) and ``train.json`` (losses, ms_per_step) into params['output'].
+
+    With params['tile'] = (TH, TW) the job trains on whole frames instead (_train_frame_tiles): images is a raw (F, H, W)
+    uint8 / uint16 / float32 stack of any frame size, labels (F, H, W) class indices (one-hot labels are refused), weights
+    (F, H, W) or, when absent, the EDT maps of the whole frames.  All three stay in HBM and every step's batch is sampled
+    there by one kernel under a random rotation, the reference's tr_augment (sequitr/networks/unet.py:348-401): params
+    augment (default ('rotate',); 'flip' adds mirrors, () only crops), samples_per_epoch (default: the number of margin-0
+    tiles that cover the stack), seed, normalise (ImageNorm of each whole frame, default True).  The network is built at
+    the tile shape and net.config records it, so the model loads into SERVER_segment_frames / SERVER_segment unchanged;
+    train.json gains tile, augment, samples_per_epoch, seed and frame_shape.  Single process only: WORLD_SIZE > 1 raises.
     """
+    if params.get('tile') is not None:
+        return _train_frame_tiles(params, options)
     import torch
     from . import utils
     from .parallel import epoch_schedule
