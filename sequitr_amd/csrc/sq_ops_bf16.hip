@@ -346,7 +346,10 @@ __global__ __launch_bounds__(256) void convT_bf16_kernel(const __bf16 *__restric
             (bf16x4){(__bf16)(acc[cb][0] + bv.x), (__bf16)(acc[cb][1] + bv.y), (__bf16)(acc[cb][2] + bv.z),
                      (__bf16)(acc[cb][3] + bv.w)};
     __syncthreads();
-    // rows (2a+b)*Cout + o: for one a, (b, o) is contiguous in the output over min(64, 2*Cout) rows of this block
+    // rows (2a+b)*Cout + o: the block's 64 rows are read back as runs of RB = min(64, 2*Cout) rows.  Where 2*Cout divides
+    // 64 or is a multiple of it, a run is one a with (b, o) contiguous in the output.  Otherwise (Cout 48: the 64 rows
+    // straddle two sub-pixel classes) a run is not, and nothing relies on it: the class ab and the channel o are recomputed
+    // from the global row for every 8-channel piece, and a piece never straddles a class because Cout % 8 == 0.
     const int RB = 2 * Cout < 64 ? 2 * Cout : 64, R8 = RB >> 3;
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
