@@ -1027,6 +1027,52 @@ int sq_tile_sample_affine(const void *frames, int dtype, const float *mean, cons
                           uint8_t *out_onehot, float *out_weights, int F, int H, int W, int TH, int TW, int C, int count,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GAN sampler: the progressive GAN's real images, the third sampler -- the reference's input pipeline in front of its
+ * discriminator (sequitr/networks/gan.py:347-407 and :682-684: every image normalised per channel by its own moments,
+ * tf.nn.moments(img, axes=[0,1]) and batch_normalization(..., 1e-8); shuffled; a random crop; two random mirrors; a
+ * bilinear tf.image.resize_images(..., align_corners=True) to the current level's size; sequitr_amd/frontend.py:
+ * gan_sample_plan, GanSampler).  Raw image stacks (N, H, W, C), channels interleaved, C in 1 .. 4, stay in HBM.
+ * TensorFlow's parity is unpinned; this text is the contract.
+ *   sq_gan_image_stats : per-(image, channel) moments of SQ_PIX_U8 or SQ_PIX_U16 images, H*W <= 2^24.  The sums are EXACT
+ *                        integers, S1 = sum v and S2 = sum v^2 over the n = H*W pixels in uint64, accumulated with integer
+ *                        adds and integer atomics: the result does not depend on any order and is the same bits on every
+ *                        run.  A finishing step computes in float64, no FMA contraction,
+ *                            mean = S1 / n;   var = max(S2 / n - mean * mean, 0);   inv = 1 / sqrt(var + 1e-8)
+ *                        (S1, S2 and n converted to float64, round to nearest even) and stores float32(mean) and
+ *                        float32(inv) as (N, C) arrays.  The clamp matters: a nearly constant uint16 image can round the
+ *                        difference below zero.  workspace: sq_gan_image_stats_workspace bytes, 8-byte aligned, cleared
+ *                        by the call.  SQ_PIX_F32 is refused here: float32 pixels are sampled with the caller's own
+ *                        statistics or with none.
+ *   sq_gan_sample_f32  : out (count, SH, SW, C) f32 from a SAMPLE PLAN, an int32 array (count, 4) in HBM with rows
+ *                        plan[k] = [n, oy, ox, bits]: the image, the origin of a (CH, CW) crop, bit 0 mirrors the crop along
+ *                        x, bit 1 along y (higher bits are ignored).  One launch.  For output pixel (i, j) and channel c:
+ *
+ *     sy = SH > 1 ? float32(CH-1) / float32(SH-1) : 0.0f      (sx likewise from CW, SW)
+ *     py = float32(i) * sy;  y0 = floor(py);  y1 = min(ceil(py), CH-1);  ly = py - y0     (x likewise)
+ *     crop(r, q) = src(oy + (bits&2 ? CH-1-r : r), ox + (bits&1 ? CW-1-q : q))
+ *     src(Y, X)  = (float32(v[n,Y,X,c]) - mean[n,c]) * inv[n,c]   if 0<=n<N, 0<=Y<H, 0<=X<W   else 0.0f
+ *                  (plain cast when mean == inv == NULL)
+ *     tl = crop(y0, x0), tr = crop(y0, x1), bl = crop(y1, x0), br = crop(y1, x1)
+ *     top = tl + (tr - tl) * lx;  bot = bl + (br - bl) * lx;  out = top + (bot - top) * ly
+ *
+ * Every *, + and - is rounded on its own in float32, no FMA.  This restates TF 1.x ResizeBilinear with align_corners=True
+ * applied to the flipped crop of the normalised image: crop -> flips -> resize is the reference's order.  With SH == CH and
+ * SW == CW the lerps are 0 and the output is the normalised crop bit for bit.  The plan is data: no load leaves the arrays,
+ * and a row or a corner that points outside -- n outside 0 .. N-1, a negative origin, a crop larger than the image -- reads
+ * 0.0f, the image's mean.  mean and inv are (N, C) f32, sq_gan_image_stats' or the caller's own.
+ * Refused before any launch: a NULL images, plan or out, a half-NULL (mean, inv) pair, C outside 1 .. 4, count outside
+ * 1 .. 65535, a non-positive size, H*W > 2^24, a crop axis above 2^24, SH*SW > 2^24, count*SH*SW >= 2^31.  A pixel's C
+ * channels are one load and its C floats one store where C is 1, 2 or 4, so images, out, mean and inv must be aligned to
+ * C of their elements there (to one element for C = 3).
+ * One thread per output pixel over the flat (k, i, j) index, stores along j; the kernel is launch- and gather-bound.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_gan_image_stats_workspace(int N, int C);
+int sq_gan_image_stats(const void *images, int dtype, float *mean, float *inv, void *workspace, int N, int H, int W, int C,
+                       void *stream);
+int sq_gan_sample_f32(const void *images, int dtype, const float *mean, const float *inv, const int32_t *plan, float *out,
+                      int N, int H, int W, int C, int CH, int CW, int SH, int SW, int count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,9 @@ SIGNATURES = {
     "sq_volume_sample_copy": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "sq_volume_sample_onehot_u8": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "sq_tile_sample_affine": (c_int, [c_void_p, c_int] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
+    "sq_gan_image_stats_workspace": (c_int64, [c_int, c_int]),
+    "sq_gan_image_stats": (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
+    "sq_gan_sample_f32": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "sq_dense_workspace_f32": (c_int64, [c_int, c_int, c_int]),
     "sq_dense_fwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "sq_convT_conv3x3_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

@@ -24,6 +24,11 @@ reference's ImageSample, ImageFlip and the quarter turns of ImageRotate (sequitr
 Training on whole frames is the planar twin (tile_sample_plan, TileSampler): raw frames, class-index labels and weight
 maps stay in HBM and every step's batch of tiles is sampled there under a random rotation, bilinear for image and weights,
 nearest for the labels -- the reference's tr_augment (sequitr/networks/unet.py:348-401) in front of SERVER_train's step.
+
+The progressive GAN's real images are the third sampler (gan_sample_plan, GanSampler): raw multi-channel image stacks stay
+in HBM, every image is normalised per channel by its own moments, and one launch per step writes the batch at the current
+level's size -- a random crop, two random mirrors and a bilinear resize with align_corners=True, the reference's input
+pipeline (sequitr/networks/gan.py:347-407, :682-684).
 """
 import json
 import os
@@ -972,6 +977,127 @@ class TileSampler(object):
                                                      self.tile[0], self.tile[1], C, count,
                                                      torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine')
         return o_img, o_hot, o_wts
+
+
+FLIP_X, FLIP_Y = 1, 2                                           # the mirror bits of a GAN sample plan's `bits`
+
+
+def gan_sample_plan(image_shape, crop, images, count, rng, augment=('flip',), shuffle=True):
+    """The rows of a GAN sampler launch (include/sequitr_hip.h "GAN sampler"), host only: (count, 4) int32 rows
+    [n, oy, ox, bits].  image_shape is (H, W), crop (CH, CW), `images` the number of images, `rng` a
+    numpy.random.Generator.  The image index walks successive epochs, each a fresh rng.permutation(images) drawn when the
+    previous one is used up (the reference shuffles its dataset); with shuffle=False it walks k % images and draws nothing.
+    An origin is uniform over [0, L - T] inclusive along its axis -- tf.image.random_crop's range -- and 0 along an axis
+    shorter than the crop (the crop reads fill there).  `bits` is uniform over 0 .. 3 under 'flip' (bit 0 mirrors x, bit 1
+    y: the reference's two random mirrors), otherwise 0.  The draws are, in this order: the permutations, the count row
+    origins, the count column origins, the count mirror values."""
+    shape, crop = tuple(int(s) for s in image_shape), tuple(int(s) for s in crop)
+    if len(shape) != 2 or len(crop) != 2 or min(shape + crop) < 1:
+        raise ValueError('image_shape and crop are (H, W) pairs of positive sizes, got %r and %r' % (image_shape, crop))
+    images, count = int(images), int(count)
+    if images < 1 or count < 1:
+        raise ValueError('need at least one image and one sample, got %d and %d' % (images, count))
+    augment = (augment,) if isinstance(augment, str) else tuple(augment)
+    unknown = [a for a in augment if a != 'flip']
+    if unknown:
+        raise ValueError("augment holds 'flip' or nothing, got %r" % (unknown,))
+    plan = np.zeros((count, 4), np.int32)
+    if shuffle:
+        epochs = [rng.permutation(images) for _ in range((count + images - 1) // images)]
+        plan[:, 0] = np.concatenate(epochs)[:count]
+    else:
+        plan[:, 0] = np.arange(count) % images
+    plan[:, 1] = rng.integers(0, max(shape[0] - crop[0], 0) + 1, count)
+    plan[:, 2] = rng.integers(0, max(shape[1] - crop[1], 0) + 1, count)
+    if 'flip' in augment:
+        plan[:, 3] = rng.integers(0, 4, count)
+    return plan
+
+
+class GanSampler(object):
+    """The progressive GAN's real images cut on the GPU out of raw (N, H, W, C) image stacks that stay in HBM: per-channel
+    normalisation by each image's own moments, crop, mirrors and the bilinear resize to the level's size in one launch
+    (include/sequitr_hip.h "GAN sampler").  `plan` is gan_sample_plan's rows (or a slice of them) in GPU memory."""
+
+    def __init__(self, image_shape, channels, crop, device=None):
+        self.shape, self.crop = tuple(int(s) for s in image_shape), tuple(int(s) for s in crop)
+        if len(self.shape) != 2 or len(self.crop) != 2 or min(self.shape + self.crop) < 1:
+            raise ValueError('image_shape and crop are (H, W) pairs of positive sizes, got %r and %r' % (image_shape, crop))
+        if self.shape[0] * self.shape[1] > 1 << 24:
+            raise ValueError('images of %d x %d pixels exceed 2^24 pixels' % self.shape)
+        self.channels = int(channels)
+        if not 1 <= self.channels <= 4:
+            raise ValueError('%d channels are not 1 .. 4' % self.channels)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise _lib.SequitrHipError('GanSampler runs on the HIP back end only')
+
+    def _check(self, images, dtypes):
+        if not isinstance(images, torch.Tensor) or not images.is_cuda:
+            raise _lib.SequitrHipError('images must be a tensor in GPU memory (no CPU fallback exists)')
+        if images.dtype not in dtypes or images.dim() != 4 or not images.is_contiguous():
+            raise ValueError('images must be a contiguous (N,H,W,C) %s tensor' % (
+                ' / '.join(str(d).replace('torch.', '') for d in dtypes)))
+        if tuple(images.shape[1:]) != self.shape + (self.channels,) or images.shape[0] < 1:
+            raise ValueError('images are %s, sampler was built for %s' % (tuple(images.shape[1:]), self.shape + (self.channels,)))
+        return int(images.shape[0])
+
+    def stats(self, images):
+        """per-(image, channel) float32 (mean, inv) of uint8 / uint16 images, (N, C) each: inv = 1 / sqrt(var + 1e-8) from
+        exact integer sums, the same bits on every run"""
+        N = self._check(images, (torch.uint8, torch.uint16))
+        lib = _lib.load()
+        mean = torch.empty((N, self.channels), dtype=torch.float32, device=self.device)
+        inv = torch.empty_like(mean)
+        work = torch.empty(max(int(lib.sq_gan_image_stats_workspace(N, self.channels)), 8) // 8, dtype=torch.int64,
+                           device=self.device)
+        _lib.check(lib.sq_gan_image_stats(images.data_ptr(), PIX[images.dtype], mean.data_ptr(), inv.data_ptr(),
+                                          work.data_ptr(), N, self.shape[0], self.shape[1], self.channels,
+                                          torch.cuda.current_stream().cuda_stream), 'sq_gan_image_stats')
+        return mean, inv
+
+    def sample(self, images, plan, size, normalise=True, stats=None, out=None):
+        """(count, SH, SW, C) float32: every plan row's crop of the raw (N, H, W, C) uint8 / uint16 / float32 images,
+        mirrored and resized bilinearly (align_corners=True) to size = (SH, SW).  The images are normalised per channel
+        when `normalise`, with `stats` = (mean, inv) when the caller already has them and self.stats(images) otherwise;
+        float32 images have no statistics kernel, so they need `stats` or normalise=False.  Where a crop leaves its image
+        it reads 0.0.  `out` takes a preallocated tensor."""
+        N = self._check(images, tuple(PIX))
+        if not isinstance(plan, torch.Tensor) or not plan.is_cuda:
+            raise _lib.SequitrHipError('plan must be a tensor in GPU memory (no CPU fallback exists)')
+        if plan.dtype != torch.int32 or plan.dim() != 2 or plan.shape[1] != 4 or not plan.is_contiguous():
+            raise ValueError('plan must be a contiguous (count, 4) int32 tensor, got %s %s' % (plan.dtype, tuple(plan.shape)))
+        count = int(plan.shape[0])
+        if not 1 <= count <= 65535:
+            raise ValueError('a plan of %d rows is not one launch (1 .. 65535 rows)' % count)
+        try:
+            size = tuple(int(s) for s in size)
+        except TypeError:
+            size = ()
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError('size is an (SH, SW) pair of positive sizes, got %r' % (size,))
+        mean = inv = None
+        if normalise:
+            if stats is None and images.dtype == torch.float32:
+                raise ValueError('float32 images are normalised with the caller\'s stats=(mean, inv) only (or normalise=False)')
+            mean, inv = stats if stats is not None else self.stats(images)
+            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                       and tuple(t.shape) == (N, self.channels) for t in (mean, inv)):
+                raise ValueError('stats must be the (mean, inv) float32 (%d, %d) tensors of these images in GPU memory'
+                                 % (N, self.channels))
+        shape = (count,) + size + (self.channels,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda:
+            raise _lib.SequitrHipError('out must be a tensor in GPU memory (no CPU fallback exists)')
+        elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError('out must be a contiguous float32 tensor of %s, got %s %s' % (shape, out.dtype, tuple(out.shape)))
+        _lib.check(_lib.load().sq_gan_sample_f32(images.data_ptr(), PIX[images.dtype], mean.data_ptr() if normalise else None,
+                                                 inv.data_ptr() if normalise else None, plan.data_ptr(), out.data_ptr(), N,
+                                                 self.shape[0], self.shape[1], self.channels, self.crop[0], self.crop[1],
+                                                 size[0], size[1], count, torch.cuda.current_stream().cuda_stream),
+                   'sq_gan_sample_f32')
+        return out
 
 
 class TileStreamer(object):

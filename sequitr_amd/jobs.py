@@ -1018,3 +1018,69 @@ def SERVER_train_volume(params, options):
         json.dump(dict(info, losses=losses), f, indent=2)
     logger.info('Trained {steps} steps on volumes, loss {first_loss} -> {last_loss}, saved {model_dir}'.format(**info))
     return info
+
+
+GAN_KEYS = ('num_outputs', 'batch_size', 'repeat_batch', 'num_levels', 'num_epochs_per_level', 'start_size', 'learning_rate',
+            'seed', 'dtype', 'batch_d', 'hbm_budget')
+
+
+def SERVER_train_gan(params, options):
+    """Train the progressive WGAN-GP (networks.gan.GenerativeAdverserialNetwork) on a stack of real images that stays in HBM.
+
+    params: training_data (.npy (N, H, W, C) raw uint8 / uint16 stack, C equal to num_outputs), output (the folder the
+    per-level checkpoints ``model_(HxW).npz``, ``export/`` and ``train.json`` go to), crop ((CH, CW), default (512, 512)
+    clipped to the image: every step's batch is one GanSampler launch -- per-channel normalisation by each image's own
+    moments, a random crop, two random mirrors, the bilinear resize to the level's size; the reference's input pipeline,
+    sequitr/networks/gan.py:347-407), and the network's keys: num_outputs, batch_size, repeat_batch, num_levels,
+    num_epochs_per_level, start_size, learning_rate, seed, dtype ('f32' | 'bf16' | 'mixed'), batch_d, hbm_budget.
+    options: gpu, max_steps (the most steps per fade / stabilisation phase: train(max_steps_per_phase=)), graph (default
+    True: the iterations replay as hipGraphs).
+
+    Single process.  After the last level the highest checkpoint is exported with convert_checkpoint_to_model().  Returns
+    (and writes to ``train.json``) levels, sizes, steps, d_loss and g_loss of the last discriminator step, graph, dtype,
+    crop, images, seconds, export_dir."""
+    import torch
+    from .networks import gan
+
+    if int(os.environ.get('WORLD_SIZE', 1)) > 1:
+        raise RuntimeError('SERVER_train_gan runs in a single process')
+    fn = params.get('training_data')
+    if not (isinstance(fn, str) and fn.endswith('.npy')):
+        raise ValueError("params['training_data'] must be a .npy stack (N, H, W, C), got %r" % (fn,))
+    if not params.get('output'):
+        raise ValueError("params['output'] must name the folder for the checkpoints")
+    x = np.load(fn, mmap_mode='r', allow_pickle=False)
+    if x.ndim != 4:
+        raise ValueError('training_data must be (N, H, W, C), got shape %s' % (x.shape,))
+    N, H, W, C = (int(v) for v in x.shape)
+    n_out = int(params.get('num_outputs', 2))
+    if C != n_out:
+        raise ValueError('training_data has %d channels, the network (num_outputs) %d' % (C, n_out))
+    crop = tuple(int(c) for c in params.get('crop', (512, 512)))
+    if len(crop) != 2 or min(crop) < 1:
+        raise ValueError("params['crop'] must be a (CH, CW) pair of positive sizes, got %r" % (params.get('crop'),))
+    crop = (min(crop[0], H), min(crop[1], W))
+    del x
+
+    device = _resolve_device(params, options)
+    torch.cuda.set_device(torch.device(device))
+    p = {k: params[k] for k in GAN_KEYS if k in params}
+    p.update(training_data=fn, crop=crop, device=device, output=params['output'], num_outputs=n_out,
+             graph=bool(options.get('graph', True)))
+    t_start = time.time()
+    net = gan.GenerativeAdverserialNetwork(p, gan.TRAIN)
+    net.build()
+    net.train(max_steps_per_phase=options.get('max_steps'))
+    torch.cuda.synchronize()
+    seconds = time.time() - t_start
+    d_loss, g_loss = net.last_losses
+    export_dir = net.convert_checkpoint_to_model()
+    info = {'levels': int(net.num_levels), 'sizes': [list(net.get_size(n)) for n in range(net.num_levels)],
+            'steps': int(net.global_step), 'd_loss': d_loss, 'g_loss': g_loss, 'graph': bool(net.use_graph),
+            'dtype': str(net.dtype), 'crop': list(crop), 'images': N, 'image_shape': [H, W, C], 'batch_size': int(net.batch_size),
+            'seed': int(net.seed), 'seconds': seconds, 'device': device, 'export_dir': export_dir}
+    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
+        json.dump(info, f, indent=2)
+    logger.info('Trained the GAN for {steps} iterations over {levels} levels, losses D {d_loss:.4f} G {g_loss:.4f}, '
+                'exported {export_dir}'.format(**info))
+    return info

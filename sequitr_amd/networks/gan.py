@@ -253,7 +253,12 @@ class GenerativeAdverserialNetwork(object):
     convolutions; 'bf16': BASELINE config 5 -- bf16-multiply / f32-accumulate convolutions AND bf16 storage of every
     feature map and feature-map gradient, f32 parameters / images / losses; 'mixed': the bf16 multiplies behind f32 tensors),
     graph (default False: True replays the solver steps as hipGraphs), batch_d (default True: the discriminator sees
-    the generated and the real minibatch as one stacked batch, each with its own minibatch statistic)."""
+    the generated and the real minibatch as one stacked batch, each with its own minibatch statistic), crop ((CH, CW);
+    with training_data in TRAIN mode: the raw uint8 / uint16 stack is uploaded once and stays in HBM, every image is
+    normalised per channel by its own moments, and each step's batch is one GanSampler launch -- a random crop of that
+    size, two random mirrors and the bilinear resize to the level's size, the reference's input pipeline, gan.py:347-407;
+    absent: the host path, images picked in order and resized by nearest neighbour), hbm_budget (bytes the resident stack
+    may take, default 32 GiB)."""
 
     def __init__(self, params, mode=None, discriminator_fn=discriminator_network,
                  generator_fn=generator_network):
@@ -304,6 +309,11 @@ class GenerativeAdverserialNetwork(object):
                 raise IOError('training_data must be a .npy stack (TFRecord IO is out of scope): %r' % (fn,))
             self.dataset = np.load(fn, mmap_mode='r', allow_pickle=False)
             self.num_batches_per_epoch = max(1, int(len(self.dataset) / self.batch_size))
+        self.crop = params.get('crop', None)
+        self._sampler = None                                    # crop: the stack in HBM, its statistics, the phase's plan rows
+        self._plan_rows, self._plan_first = None, 0
+        if self.dataset is not None and self.crop is not None:
+            self._upload_dataset(int(params.get('hbm_budget', 32 << 30)))
 
         self.restore = False
         self.networks = []
@@ -806,8 +816,56 @@ class GenerativeAdverserialNetwork(object):
         return torch.randn((self.batch_size, 1, 1, 512), generator=self._torch_rng, dtype=torch.float32,
                            device=self.device)
 
+    def _upload_dataset(self, budget):
+        """params['crop']: the .npy stack goes to HBM once, as it is, and its per-(image, channel) statistics are computed
+        once (frontend.GanSampler)"""
+        from ..frontend import NP_TORCH, GanSampler
+        x = self.dataset
+        crop = tuple(int(c) for c in self.crop) if np.ndim(self.crop) == 1 else ()
+        if len(crop) != 2 or min(crop) < 1:
+            raise ValueError('crop must be a (CH, CW) pair of positive sizes, got %r' % (self.crop,))
+        if x.ndim != 4 or np.dtype(x.dtype) not in (np.dtype('uint8'), np.dtype('uint16')):
+            raise ValueError('with crop the training data must be a raw (N, H, W, C) uint8 or uint16 stack, got %s %s'
+                             % (x.dtype, x.shape))
+        N, H, W, C = (int(v) for v in x.shape)
+        if C != self.num_channels:
+            raise ValueError('the training data has %d channels, the network (num_outputs) %d' % (C, self.num_channels))
+        nbytes = N * H * W * C * x.dtype.itemsize
+        if nbytes > budget:
+            raise MemoryError('the training stack (%d images of %d x %d x %d %s, %d bytes) does not fit hbm_budget = %d bytes'
+                              % (N, H, W, C, x.dtype, nbytes, budget))
+        self.crop = crop
+        self._sampler = GanSampler((H, W), C, crop, device=self.device)
+        self._images = torch.empty((N, H, W, C), dtype=NP_TORCH[np.dtype(x.dtype)], device=self.device)
+        for i in range(N):                                      # one image at a time: no whole-stack host copy
+            self._images[i].copy_(torch.from_numpy(np.array(x[i])))
+        with torch.cuda.device(self.device):
+            self._stats = self._sampler.stats(self._images)
+        rank = 0
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            rank = dist.get_rank(self.group)
+        self._plan_rng = np.random.default_rng([int(self.seed), int(rank)])
+
+    def _draw_plan(self, first_step, steps):
+        """one phase's sample plan: steps * batch_size rows drawn on the host from the (seed, rank) generator and uploaded
+        once; step first_step + s takes rows s * batch_size onwards"""
+        from ..frontend import gan_sample_plan
+        rows = gan_sample_plan(self._sampler.shape, self.crop, self._images.shape[0], max(int(steps), 1) * self.batch_size,
+                               self._plan_rng)
+        self._plan_rows, self._plan_first = torch.from_numpy(rows).to(self.device), int(first_step)
+
     def _next_real_batch(self, step):
         size = self.current_size
+        if self._sampler is not None:
+            # train() draws a plan per phase; a step outside it (a caller of its own) starts a plan of one level's iterations
+            s = step - self._plan_first
+            if self._plan_rows is None or not 0 <= s * self.batch_size < self._plan_rows.shape[0]:
+                self._draw_plan(step, self.num_iterations_this_level)
+                s = 0
+            rows = self._plan_rows[s * self.batch_size:(s + 1) * self.batch_size]
+            with torch.cuda.device(self.device):
+                return self._sampler.sample(self._images, rows, size, stats=self._stats)
         if self.dataset is None:
             g = torch.Generator(device=self.device)
             g.manual_seed(self.seed * 7919 + step)
@@ -856,6 +914,8 @@ class GenerativeAdverserialNetwork(object):
             if max_steps_per_phase:
                 iters = min(iters, max_steps_per_phase)
             for phase in ('fade', 'stabilisation'):
+                if self._sampler is not None:
+                    self._draw_plan(step_id, iters)             # the phase's rows: one host draw, one upload
                 for step in range(iters):
                     fade = float(step + 1) / iters if phase == 'fade' else 1.0
                     z, x = self.build_latent(), self._next_real_batch(step_id)
@@ -936,6 +996,9 @@ def main(argv=None):
     p.add_argument('--train', action='store_true', help='Train the model if this flag is present')
     p.add_argument('--restore', action='store_true', help='Continue training a model')
     p.add_argument('--training_data', default=None, help='.npy stack (N,H,W,C); synthetic tiles when absent')
+    p.add_argument('--crop', type=int, nargs=2, default=None, metavar=('CH', 'CW'),
+                   help='keep the raw uint8 / uint16 stack in GPU memory and sample every batch there: random CH x CW crops, '
+                        'mirrors, bilinear resize to the level (the reference crops 512 512)')
     p.add_argument('--samples', type=int, default=512, help='images to export when predicting')
     args = p.parse_args(argv)
 
@@ -945,6 +1008,8 @@ def main(argv=None):
     config.batch_size = args.batch_size
     config.training_data = args.training_data
     params = config.to_params()
+    if args.crop is not None:
+        params['crop'] = tuple(args.crop)
     if args.train:
         gan = GenerativeAdverserialNetwork(params, TRAIN)
         gan.restore = args.restore
