@@ -1073,6 +1073,51 @@ int sq_gan_image_stats(const void *images, int dtype, float *mean, float *inv, v
 int sq_gan_sample_f32(const void *images, int dtype, const float *mean, const float *inv, const int32_t *plan, float *out,
                       int N, int H, int W, int C, int CH, int CW, int SH, int SW, int count, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scoring: confusion counts of predictions against labels, both in HBM -- the counterpart of the reference's
+ * sequitr/confusion.py, which hands host arrays to scikit-learn (sequitr_amd/confusion.py: confusion_counts,
+ * ConfusionMeter, scores).  One streaming pass; every quantity is an integer count, so this text is exact.
+ *   sq_confusion : `items` rows of `n` pixels or voxels each (a row is a tile, a whole frame or a whole volume; n is an
+ *                  int64, up to 2^44).  For pixel p of item i, with C classes:
+ *
+ *     pc = SQ_PRED_MASK       : pred  uint8 (items, n),     pc = pred[i, p]
+ *          SQ_PRED_LOGITS_F32 : pred  float32 (items, n, C), best = 0; for c = 1 .. C-1: if (z[c] > z[best]) best = c; pc = best
+ *     tc = SQ_TRUTH_INDEX     : truth uint8 (items, n),     tc = truth[i, p]
+ *          SQ_TRUTH_ONEHOT    : truth uint8 (items, n, C),  tc = the lowest c with truth[i, p, c] != 0; none: no class
+ *     tc < C and pc < C  ?  counts[i, tc, pc] += 1  :  ignored[i] += 1
+ *
+ *                  The logits rule is sq_argmax_u8's loop: ties go to the lowest index, a NaN never wins a comparison (a row
+ *                  that starts with NaN is class 0), and -0 == +0; for every input pc is the class sq_argmax_u8 writes, and no
+ *                  mask is materialised.  An all-zero one-hot row is what the trainer's label format holds for labels >= C.
+ *                  counts is int64 (items, C, C), row = truth, column = prediction (scikit-learn's convention); ignored is
+ *                  int64 (items): the pixels whose truth has no class or is >= C and the mask pixels >= C.  Those touch no
+ *                  counts cell, so counts[i].sum() + ignored[i] grows by exactly n per call.  The call ADDS to both arrays:
+ *                  the caller zeroes them, and the batches of a stream accumulate into the same rows.  Integer adds only
+ *                  (LDS and global atomics): the result depends on no order and is the same bits on every run.
+ *                  Refused before any launch: a NULL pointer, an unknown kind, C outside 1 .. 16, a negative items or n,
+ *                  counts or ignored not aligned to 8 bytes, logits not aligned to 4.  items == 0 or n == 0 is a no-op that
+ *                  returns 0.  pred (masks) and truth may start at ANY byte address and n may be odd: see below.
+ *   sq_confusion_chunk : the pixels of one item a block counts before it flushes, for this (items, n): 16384, doubled while
+ *                  the call would have more than 2^22 chunks, at most 2^30.  0 for an empty call.
+ * A block owns one chunk of one item -- it never straddles two -- and counts it into an LDS histogram of C*C + 1 bins of
+ * 32-bit counters, 32 counters per bin so that the lanes of an LDS lane group always sit on different banks; it then issues
+ * at most C*C + 1 global 64-bit atomic adds.  There is no global atomic per pixel.  Overflow bound: a block's counters see
+ * at most one chunk <= 2^30 pixels between two flushes, below the 2^32 a counter holds.  Chunks beyond 65536 blocks are a
+ * grid-stride loop, so any `items` is one launch.
+ * Alignment: masks against index labels read 16 pixels per lane.  A block takes the pixels up to the first 16-byte boundary
+ * of its pred range one per thread, then 16-byte vectors (pred aligned; truth aligned too when both bases are congruent mod
+ * 16, otherwise the same load at an unaligned address), then the tail one per thread.  The other pairs walk one pixel per
+ * lane and read its C floats or C bytes as the widest vector that divides a pixel and that every row base is aligned to.
+ * No load leaves [base, base + items * n * bytes per pixel).
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_PRED_MASK 0
+#define SQ_PRED_LOGITS_F32 1
+#define SQ_TRUTH_INDEX 0
+#define SQ_TRUTH_ONEHOT 1
+int64_t sq_confusion_chunk(int64_t items, int64_t n);
+int sq_confusion(const void *pred, int pred_kind, const uint8_t *truth, int truth_kind, int64_t *counts, int64_t *ignored,
+                 int64_t items, int64_t n, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

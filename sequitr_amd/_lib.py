@@ -88,6 +88,8 @@ SIGNATURES = {
     "sq_gan_image_stats_workspace": (c_int64, [c_int, c_int]),
     "sq_gan_image_stats": (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "sq_gan_sample_f32": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
+    "sq_confusion_chunk": (c_int64, [c_int64, c_int64]),
+    "sq_confusion": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "sq_dense_workspace_f32": (c_int64, [c_int, c_int, c_int]),
     "sq_dense_fwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "sq_convT_conv3x3_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

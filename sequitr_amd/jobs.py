@@ -194,12 +194,12 @@ def _load_net_weights(net, params):
     logger.info('Loaded weights from {0:s}'.format(model_dir))
 
 
-def _segment_volume_bricks(params, options):
-    """SERVER_segment_volume with params['brick']: volumes of any size, raw, brick by brick (frontend.segment_volumes)."""
+def _brick_volumes(params, options):
+    """What the brick jobs check before any voxel is read or any GPU work starts: (device, volumes (N, Z, X, Y) raw,
+    brick (bz, bx, by), margin in (Z, X, Y) order, geometry)"""
     from .frontend import NP_TORCH, volume_bricks
 
     device = _resolve_device(params, options)
-    out_dir = params['output']
     x = _load_volumes(params)
     if x.shape[4] != 1 or int(params.get('num_inputs', 1)) != 1:
         raise ValueError("params['brick'] segments single-channel volumes only, got %d channels" % x.shape[4])
@@ -216,6 +216,14 @@ def _segment_volume_bricks(params, options):
             raise ValueError("params['margin'] must be an int or (X, Y, Z), got %r" % (margin,))
         margin = (int(margin[2]), int(margin[0]), int(margin[1]))
     geometry = volume_bricks((Z, X, Y), (bz, bx, by), margin)  # raises on a margin too large for the brick
+    return device, x, (bz, bx, by), margin, geometry
+
+
+def _segment_volume_bricks(params, options):
+    """SERVER_segment_volume with params['brick']: volumes of any size, raw, brick by brick (frontend.segment_volumes)."""
+    device, x, (bz, bx, by), margin, geometry = _brick_volumes(params, options)
+    out_dir = params['output']
+    N, Z, X, Y = (int(s) for s in x.shape)
 
     import torch
     from .networks.unet import UNet3D
@@ -342,6 +350,20 @@ def SERVER_segment_volume(params, options):
     return info
 
 
+def _open_frames(params):
+    """params['input'] of the frame jobs -> (frames, F, H, W): an Octopus stream, a .npy memmap or an ndarray; no pixel is
+    read here"""
+    src = params.get('input')
+    if isinstance(src, str) and not src.endswith('.npy'):
+        from .dataio import OctopusData
+        frames = OctopusData(src, timeout=params.get('timeout', 60))
+        F, (H, W) = len(frames), frames.framesize
+    else:
+        frames = np.load(src, mmap_mode='r', allow_pickle=False) if isinstance(src, str) else np.asarray(src)
+        F, H, W = frames.shape
+    return frames, int(F), int(H), int(W)
+
+
 def SERVER_segment_frames(params, options):
     """Segment whole camera frames (larger than the network tile): params['input'] = an Octopus stream stem
     (sequitr/dataio/octopus.py), a .npy of (F,H,W) uint8/uint16/float32 frames, or an ndarray.  Raw frames
@@ -356,20 +378,13 @@ def SERVER_segment_frames(params, options):
     from .networks.unet import UNet2D
     from . import utils
     from .frontend import FrameClean, segment_frames
-    from .dataio import OctopusData
 
     device = _resolve_device(params, options)
     out_dir = params['output']
     clean, normalise = None, True
     if params.get('pipeline') is not None:
         clean, normalise = FrameClean.from_pipeline(params['pipeline'])
-    src = params.get('input')
-    if isinstance(src, str) and not src.endswith('.npy'):
-        frames = OctopusData(src, timeout=params.get('timeout', 60))
-        F, (H, W) = len(frames), frames.framesize
-    else:
-        frames = np.load(src, mmap_mode='r', allow_pickle=False) if isinstance(src, str) else np.asarray(src)
-        F, H, W = frames.shape
+    frames, F, H, W = _open_frames(params)
     net_p = _net_params(params, device)
     net_p.setdefault('shape', (512, 512))
     tile = int(net_p['shape'][0])
@@ -421,6 +436,178 @@ def SERVER_segment_frames(params, options):
     return info
 
 
+def _load_labels(src, key='labels'):
+    """class-index labels: a .npy path (opened as a memmap) or an ndarray, uint8"""
+    if isinstance(src, str) and src.endswith('.npy'):
+        labels = np.load(src, mmap_mode='r', allow_pickle=False)
+    elif isinstance(src, np.ndarray):
+        labels = src
+    else:
+        raise ValueError("params[%r] must be a .npy path or an ndarray of uint8 class indices" % key)
+    if labels.dtype != np.uint8:
+        raise TypeError("params[%r] must be uint8 class indices, got %s" % (key, labels.dtype))
+    return labels
+
+
+class _LabelFeed(object):
+    """uint8 labels (N, ...) on their way to the device: the whole stack once when it fits in `resident_bytes`, otherwise
+    the rows a batch needs, through two pinned buffers, on the stream the masks are produced on"""
+
+    def __init__(self, labels, device, rows_per_batch, resident_bytes):
+        import torch
+        from .frontend import _pinned
+        self.labels, self.all = labels, None
+        if labels.nbytes <= resident_bytes:
+            self.all = torch.empty(tuple(labels.shape), dtype=torch.uint8, device=device)
+            for i in range(labels.shape[0]):                    # row by row: no whole-stack host copy of a memmap
+                self.all[i].copy_(torch.from_numpy(np.array(labels[i], dtype=np.uint8, order='C')))
+            return
+        shape = (int(rows_per_batch),) + tuple(labels.shape[1:])
+        self.pinned = [_pinned('labels%d' % i, shape, torch.uint8) for i in range(2)]
+        self.staged = [torch.empty(shape, dtype=torch.uint8, device=device) for _ in range(2)]
+        self.sent = [torch.cuda.Event(), torch.cuda.Event()]
+        self.turn = 0
+
+    def get(self, first, n):
+        """labels[first:first + n] in HBM; a staged batch stays valid until the second get() after it"""
+        if self.all is not None:
+            return self.all[first:first + n]
+        k, self.turn = self.turn, 1 - self.turn
+        self.sent[k].synchronize()                              # the previous upload out of this pinned buffer is done
+        self.pinned[k][:n].numpy()[...] = self.labels[first:first + n]
+        self.staged[k][:n].copy_(self.pinned[k][:n], non_blocking=True)
+        self.sent[k].record()
+        return self.staged[k][:n]
+
+
+def _evaluation_record(counts, ignored):
+    """the part of evaluate.json that follows from the per-item counts (F, C, C) and ignored (F), host int64"""
+    from .confusion import json_ready, scores
+    total = counts.sum(0)
+    return {'confusion': total.tolist(), 'ignored': int(ignored.sum()), 'scores': json_ready(scores(total)),
+            'per_frame': [dict(json_ready(scores(c)), ignored=int(g)) for c, g in zip(counts, ignored)]}
+
+
+def _evaluate_volume_bricks(params, options):
+    """SERVER_evaluate with params['brick']: volumes brick by brick, each stitched mask scored where segment_volumes
+    leaves it"""
+    labels = _load_labels(params.get('labels'))
+    device, x, (bz, bx, by), margin, geometry = _brick_volumes(params, options)
+    N, Z, X, Y = (int(s) for s in x.shape)
+    if tuple(labels.shape) != (N, Z, X, Y):
+        raise ValueError('labels %s do not match the volumes %s' % (tuple(labels.shape), (N, Z, X, Y)))
+    out_dir = params['output']
+
+    import torch
+    from . import ops
+    from .networks.unet import UNet3D
+    from .frontend import segment_volumes
+    torch.cuda.set_device(torch.device(device))
+    net_p = _net_params(params, device)
+    net_p['shape'], net_p['num_inputs'] = (bx, by, bz), 1
+    t_setup = time.time()
+    net = UNet3D(net_p, 'infer')
+    _load_net_weights(net, params)
+    C = int(net.n_outputs)
+    batch = int(params.get('bricks_per_batch', 8))
+    net.predict(torch.zeros((min(batch, geometry.per_volume), bz, bx, by, 1), device=device))   # first-launch costs
+    feed = _LabelFeed(labels, device, 1, float(options.get('resident_label_gib', 4)) * 2 ** 30)
+    counts = torch.zeros((N, C, C), dtype=torch.int64, device=device)
+    ignored = torch.zeros((N,), dtype=torch.int64, device=device)
+    masks = np.zeros((N, Z, X, Y), np.uint8) if options.get('masks') else None
+    torch.cuda.synchronize()
+
+    def sink(i, m):                                            # m (1, Z, X, Y) in HBM
+        ops.confusion_(counts[i:i + 1], ignored[i:i + 1], m, feed.get(i, 1), C)
+        if masks is not None:
+            masks[i] = m[0].cpu().numpy()
+
+    t0 = time.time()
+    segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch, normalise=bool(params.get('normalise', True)),
+                    on_masks=sink)
+    counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
+    dt = time.time() - t0
+    np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
+    if masks is not None:
+        np.save(os.path.join(out_dir, 'mask.npy'), masks)
+    info = {'volumes': N, 'shape': [Z, X, Y], 'num_classes': C, 'seconds': dt, 'setup_seconds': t0 - t_setup,
+            'mpixels_per_s': float(N * Z * X * Y / max(dt, 1e-9) / 1e6), 'device': device, 'brick': [bx, by, bz],
+            'margin': [geometry.margin[1], geometry.margin[2], geometry.margin[0]],
+            'bricks_per_volume': int(geometry.per_volume)}
+    info.update(_evaluation_record(counts_h, ignored_h))
+    with open(os.path.join(out_dir, 'evaluate.json'), 'w') as f:
+        json.dump(info, f, indent=2)
+    logger.info('Scored {volumes} volumes in {seconds:.3f}s on {device}'.format(**info))
+    return info
+
+
+def SERVER_evaluate(params, options):
+    """Score a saved model on labelled data: segments as SERVER_segment_frames does (the same params: input, shape,
+    margin, frames_per_batch, pipeline, model ...) or, with params['brick'], as SERVER_segment_volume does, and counts
+    every stitched mask against params['labels'] -- a .npy (or ndarray) of uint8 class indices, (F, H, W) or
+    (V, Z, X, Y) -- while the mask is in HBM (sq_confusion): what comes back per frame is C x C integers, not the mask.
+    Labels >= num_outputs (255 is the usual "unlabelled") are counted as ``ignored`` and enter no cell.
+
+    Writes ``confusion.npy``, int64 (F, C, C) with row = truth and column = prediction, and ``evaluate.json``: the total
+    matrix ``confusion``, ``ignored``, ``scores`` (iou, dice, precision, recall and support per class, accuracy, mean_iou;
+    a class absent from both sides scores null), ``per_frame`` with the same per frame, ``seconds``, ``mpixels_per_s``
+    and the ``pipeline`` record as segment.json has it.  ``mask.npy`` is written only with options['masks'].  The labels
+    follow the frames to the device batch by batch; a stack up to options['resident_label_gib'] (default 4) is uploaded
+    once instead.  A label shape that does not match the frames raises before any frame is read."""
+    if params.get('brick') is not None:
+        return _evaluate_volume_bricks(params, options)
+    labels = _load_labels(params.get('labels'))
+    frames, F, H, W = _open_frames(params)
+    if tuple(labels.shape) != (F, H, W):
+        raise ValueError('labels %s do not match the frames %s' % (tuple(labels.shape), (F, H, W)))
+    from .frontend import FrameClean, segment_frames
+    clean, normalise = None, True
+    if params.get('pipeline') is not None:
+        clean, normalise = FrameClean.from_pipeline(params['pipeline'])
+
+    import torch
+    from . import ops
+    from .networks.unet import UNet2D
+    device = _resolve_device(params, options)
+    torch.cuda.set_device(torch.device(device))
+    out_dir = params['output']
+    net_p = _net_params(params, device)
+    net_p.setdefault('shape', (512, 512))
+    tile = int(net_p['shape'][0])
+    net = UNet2D(net_p, 'infer')
+    _load_net_weights(net, params)
+    C = int(net.n_outputs)
+    B = int(params.get('frames_per_batch', 4))
+    feed = _LabelFeed(labels, device, B, float(options.get('resident_label_gib', 4)) * 2 ** 30)
+    counts = torch.zeros((F, C, C), dtype=torch.int64, device=device)
+    ignored = torch.zeros((F,), dtype=torch.int64, device=device)
+    masks = np.empty((F, H, W), np.uint8) if options.get('masks') else None
+
+    def sink(first, m):                                        # m (n, H, W) in HBM: one row of counts per frame
+        n = m.shape[0]
+        ops.confusion_(counts[first:first + n], ignored[first:first + n], m, feed.get(first, n), C)
+        if masks is not None:
+            masks[first:first + n] = m.cpu().numpy()
+
+    t0 = time.time()
+    segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)), frames_per_batch=B, on_masks=sink,
+                   normalise=normalise, clean=clean)
+    counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
+    dt = time.time() - t0
+    np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
+    if masks is not None:
+        np.save(os.path.join(out_dir, 'mask.npy'), masks)
+    info = {'frames': F, 'shape': [H, W], 'tile': tile, 'num_classes': C, 'seconds': dt,
+            'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
+    if params.get('pipeline') is not None:
+        info['pipeline'] = (clean or FrameClean()).pipes(normalise)
+    info.update(_evaluation_record(counts_h, ignored_h))
+    with open(os.path.join(out_dir, 'evaluate.json'), 'w') as f:
+        json.dump(info, f, indent=2)
+    logger.info('Scored {frames} frames in {seconds:.3f}s on {device}'.format(**info))
+    return info
+
+
 def SERVER_test(params, options):
     """Plumbing check (the reference's commented-out SERVER_test, worker.py:300-302):
     writes the params it was called with into the output folder."""
@@ -436,6 +623,69 @@ def _onehot(labels, num_outputs):
     if labels.ndim == 4:
         return np.ascontiguousarray(labels[..., :num_outputs], dtype=np.uint8)
     return np.stack([(labels == c) for c in range(num_outputs)], -1).astype(np.uint8)
+
+
+def _validation_keys(params):
+    """(wanted, validate_every): the val_* keys come as a pair; validate_every counts epochs, None = after the last step only"""
+    have = [k for k in ('val_images', 'val_labels') if params.get(k) is not None]
+    if len(have) == 1:
+        raise ValueError("params['val_images'] and params['val_labels'] go together, got only %r" % have[0])
+    every = params.get('validate_every')
+    if every is not None and int(every) < 1:
+        raise ValueError('validate_every counts epochs and must be positive, got %r' % (every,))
+    if have and int(os.environ.get('WORLD_SIZE', 1)) > 1:
+        raise RuntimeError("validation (params['val_images'] / ['val_labels']) runs in a single process: WORLD_SIZE is %s "
+                           "(rank 0 validating alone while the others wait is not built)" % os.environ.get('WORLD_SIZE'))
+    return bool(have), (None if every is None else int(every))
+
+
+class _Validator(object):
+    """Held-out scoring between training steps, outside the captured graphs.  The net is the inference net the segment
+    jobs build for a saved model (UNet2D, mode 'infer': no dropout, the fused f32 kernels), and its variables ARE the
+    trainer's: views of the flat parameter bucket plus the trainer's non-trainable state, re-bound on the device before
+    every run, so a validation sees the weights of the step before it without a copy.  Nothing the training step reads
+    is written: the dropout salt, the samplers' random streams and the trainer's workspace arena are not touched."""
+
+    def __init__(self, trainer, net_p, run, steps_per_epoch, every, total_steps):
+        from .confusion import ConfusionMeter
+        from .networks.unet import UNet2D
+        self.trainer, self.run = trainer, run
+        self.net = UNet2D(dict(net_p), 'infer')
+        self.meter = ConfusionMeter(self.net.n_outputs, self.net.device)
+        self.steps_per_epoch, self.every, self.total_steps = int(steps_per_epoch), every, int(total_steps)
+        self.log, self.seconds = [], 0.0
+
+    def _bind(self):
+        tr, net = self.trainer, self.net
+        for k in tr.pbucket.names:
+            net._vars[k] = tr.pbucket.view(k).detach()
+        for k, v in tr.net._vars.items():                       # BN moving statistics
+            if k not in tr.pbucket.shapes:
+                net._vars[k] = v.detach()
+        net._loaded, net._creatable = True, set()
+
+    def after_step(self, done):
+        """called with the number of optimiser steps done; validates at the end of every `every`-th epoch and after
+        the last step"""
+        import torch
+        from .confusion import json_ready
+        last = done == self.total_steps
+        due = self.every is not None and done % (self.every * self.steps_per_epoch) == 0
+        if not (last or due):
+            return
+        torch.cuda.synchronize()
+        t0 = time.time()
+        self._bind()
+        self.meter.reset()
+        with torch.no_grad():
+            self.run(self.net, self.meter)
+        counts = self.meter.counts()                            # the one download, and the synchronisation
+        dt = time.time() - t0
+        self.seconds += dt
+        s = json_ready(self.meter.scores())
+        self.log.append({'step': int(done), 'epoch': int(-(-done // self.steps_per_epoch)), 'confusion': counts.tolist(),
+                         'ignored': self.meter.ignored(), 'iou': s['iou'], 'dice': s['dice'], 'accuracy': s['accuracy'],
+                         'mean_iou': s['mean_iou'], 'seconds': dt})
 
 
 def _train_frame_tiles(params, options):
@@ -474,6 +724,20 @@ def _train_frame_tiles(params, options):
     samples = F * covering_tiles((H, W), (th, tw)) if samples is None else int(samples)
     if samples < 1:
         raise ValueError('samples_per_epoch must be positive, got %d' % samples)
+    want_val, validate_every = _validation_keys(params)
+    if want_val:                                               # whole raw frames and (F, H, W) labels, as the training pair
+        vx = np.load(params['val_images'], mmap_mode='r', allow_pickle=False)
+        if vx.ndim == 4 and vx.shape[3] == 1:
+            vx = vx[..., 0]
+        if vx.ndim != 3 or np.dtype(vx.dtype) not in NP_TORCH:
+            raise ValueError("with params['tile'] val_images are raw (F, H, W) uint8, uint16 or float32 frames, got %s %s"
+                             % (vx.dtype, vx.shape))
+        vlab = _load_labels(params['val_labels'], 'val_labels')
+        if tuple(vlab.shape) != tuple(vx.shape):
+            raise ValueError('val_labels %s do not match val_images %s' % (vlab.shape, vx.shape))
+        if th != tw:
+            raise ValueError('validation segments whole frames with square tiles (frontend.segment_frames), got tile %r'
+                             % (tile,))
 
     import torch
     from . import utils
@@ -531,6 +795,17 @@ def _train_frame_tiles(params, options):
             torch.empty((batch, th, tw, 1), dtype=torch.float32, device=dev)]
     use_graph = bool(options.get('graph', True))
     loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    validator = None
+    if want_val:
+        from .frontend import segment_frames
+        val_fpb = int(params.get('frames_per_batch', 4))
+        val_feed = _LabelFeed(vlab, dev, val_fpb, float('inf'))   # resident, like the training labels
+
+        def run_val(net, meter):                               # the frames as SERVER_segment_frames would segment them
+            segment_frames(net, vx, tile=th, margin=int(params.get('margin', 32)), frames_per_batch=val_fpb,
+                           on_masks=lambda first, m: meter.update(m, val_feed.get(first, m.shape[0])), normalise=normalise)
+
+        validator = _Validator(trainer, net_p, run_val, steps_per_epoch, validate_every, total_steps)
     done, steady_from = 0, 0
     t_start = t_steady = time.time()
     for epoch in range(epochs):
@@ -554,19 +829,23 @@ def _train_frame_tiles(params, options):
             if done == 1:                                      # the first step carries the first-launch costs
                 torch.cuda.synchronize()
                 t_steady, steady_from = time.time(), 1
+            if validator is not None:
+                validator.after_step(done)
     torch.cuda.synchronize()
     t_end = time.time()
     losses = [float(v) for v in loss_log[:done].cpu().numpy()]
     steady = done - steady_from
+    val_seconds = validator.seconds if validator is not None else 0.0      # all of it falls after t_steady
     info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
-            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady) * 1e3 / steady if steady > 0 else None,
+            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady - val_seconds) * 1e3 / steady if steady > 0 else None,
             'steady_steps': steady, 'batch_size': batch, 'frames': F, 'frame_shape': [H, W], 'tile': [th, tw],
             'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed, 'normalise': normalise,
             'graph': use_graph, 'dtype': str(net_p.get('dtype', 'f32')), 'warmup_steps': trainer.warmup_steps,
             'learning_rate': trainer.lr, 'world': 1, 'device': device}
     info['model_dir'] = utils.save_model(trainer.state_dict(), config)
+    extra = {'validation': validator.log} if validator is not None else {}
     with open(os.path.join(params['output'], 'train.json'), 'w') as f:
-        json.dump(dict(info, losses=losses), f, indent=2)
+        json.dump(dict(info, losses=losses, **extra), f, indent=2)
     logger.info('Trained {steps} steps on rotated tiles of whole frames, loss {first_loss} -> {last_loss}, saved '
                 '{model_dir}'.format(**info))
     return info
@@ -602,6 +881,17 @@ def SERVER_train(params, options):
     tiles that cover the stack), seed, normalise (ImageNorm of each whole frame, default True).  The network is built at
     the tile shape and net.config records it, so the model loads into SERVER_segment_frames / SERVER_segment unchanged;
     train.json gains tile, augment, samples_per_epoch, seed and frame_shape.  Single process only: WORLD_SIZE > 1 raises.
+
+    Held-out validation, in both paths: params val_images and val_labels, in the formats of images and labels of that path
+    (with `tile`: whole raw frames and (F, H, W) class indices, segmented as SERVER_segment_frames does with the job's
+    margin / frames_per_batch; otherwise tiles, scored val_batch at a time), and validate_every, counted in epochs
+    (default: only after the last step).  Validation runs between steps, outside the captured graphs, on the inference
+    net the segment jobs build for a saved model (UNet2D 'infer': the f32 kernels on the f32 master weights, whatever the
+    job's dtype), whose variables are views of the trainer's parameter bucket; the counting is confusion.ConfusionMeter on
+    the device.  Nothing the step reads is written, so the losses are bit-identical with and without the keys.  Labels
+    >= num_outputs (255 = unlabelled) are ignored.  train.json gains ``validation``: a list of {step, epoch, confusion
+    (row = truth, column = prediction), ignored, iou, dice, accuracy, mean_iou, seconds}; ms_per_step leaves the
+    validation time out.  Single process only: with WORLD_SIZE > 1 the keys raise.
     """
     if params.get('tile') is not None:
         return _train_frame_tiles(params, options)
@@ -611,6 +901,7 @@ def SERVER_train(params, options):
     from .weightmap import device_weightmaps
     from .train import UNetTrainer
 
+    want_val, validate_every = _validation_keys(params)
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
     world, rank = int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('RANK', 0))
@@ -694,6 +985,25 @@ def SERVER_train(params, options):
 
     use_graph = bool(options.get('graph', True))
     loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    validator = None
+    if want_val:                                               # tiles and labels in the formats of `images` and `labels`
+        vx = np.load(params['val_images'], mmap_mode='r', allow_pickle=False)
+        if vx.ndim == 3:
+            vx = vx[..., np.newaxis]
+        vlab = np.load(params['val_labels'], allow_pickle=False)
+        if tuple(vx.shape[1:]) != tuple(x.shape[1:]) or tuple(vlab.shape[:3]) != tuple(vx.shape[:3]):
+            raise ValueError('val_images %s / val_labels %s do not match tiles of %s'
+                             % (vx.shape, vlab.shape, tuple(x.shape[1:])))
+        vx_dev = torch.from_numpy(np.array(vx, dtype=np.float32, order='C')).to(dev)
+        vy = _onehot(vlab, config.num_outputs) if vlab.ndim == 4 else np.ascontiguousarray(vlab, dtype=np.uint8)
+        vy_dev = torch.from_numpy(vy).to(dev)
+        val_batch = int(params.get('val_batch', 32))
+
+        def run_val(net, meter):                               # the tiles as SERVER_segment would segment them
+            for i in range(0, vx_dev.shape[0], val_batch):
+                meter.update(net.predict(vx_dev[i:i + val_batch]).contiguous(), vy_dev[i:i + val_batch])
+
+        validator = _Validator(trainer, net_p, run_val, steps_per_epoch, validate_every, total_steps)
     losses, done = [], 0
     t_start = t_steady = time.time()
     steady_from = 0
@@ -720,12 +1030,15 @@ def SERVER_train(params, options):
             else:
                 loss_log[done].copy_(trainer.step(*bufs))
             done += 1
+            if validator is not None:
+                validator.after_step(done)
         losses.extend(float(v) for v in loss_log[first:done].cpu().numpy())      # ONE read-back per epoch
     torch.cuda.synchronize()
     t_end = time.time()
     steady = done - steady_from
+    val_seconds = validator.seconds if validator is not None else 0.0      # all of it falls after t_steady
     info = {'steps': done, 'first_loss': losses[0], 'last_loss': losses[-1], 'seconds': t_end - t_start,
-            'ms_per_step': (t_end - t_steady) * 1e3 / steady if steady > 0 else None,
+            'ms_per_step': (t_end - t_steady - val_seconds) * 1e3 / steady if steady > 0 else None,
             'steady_steps': steady, 'batch_size': batch, 'tiles': n_items, 'resident': bool(resident),
             'graph': use_graph, 'dtype': str(net_p.get('dtype', 'f32')), 'warmup_steps': trainer.warmup_steps,
             'learning_rate': trainer.lr, 'world': world, 'device': device}
@@ -745,8 +1058,9 @@ def SERVER_train(params, options):
                 [float(v) for v in lo.cpu()], [float(v) for v in hi.cpu()]))
     if rank == 0:
         info['model_dir'] = utils.save_model(trainer.state_dict(), config)
+        extra = {'validation': validator.log} if validator is not None else {}
         with open(os.path.join(params['output'], 'train.json'), 'w') as f:
-            json.dump(dict(info, losses=losses), f, indent=2)
+            json.dump(dict(info, losses=losses, **extra), f, indent=2)
         logger.info('Trained {steps} steps, loss {first_loss:.4f} -> {last_loss:.4f}, saved {model_dir}'.format(**info))
     return info
 

@@ -496,6 +496,57 @@ def argmax_u8(logits):
     return mask
 
 
+PRED_MASK, PRED_LOGITS_F32 = 0, 1                               # SQ_PRED_*
+TRUTH_INDEX, TRUTH_ONEHOT = 0, 1                                # SQ_TRUTH_*
+
+
+def confusion_chunk(items, n):
+    """pixels of one item that a block of sq_confusion counts before it flushes (sq_confusion_chunk)"""
+    return int(_lib.load().sq_confusion_chunk(int(items), int(n)))
+
+
+def confusion_(counts, ignored, pred, truth, num_classes):
+    """ADDS the confusion counts of `pred` against `truth` to counts int64 (items, C, C) and ignored int64 (items)
+    (sq_confusion; row = truth, column = prediction).  pred: uint8 masks (items, ...) or float32 logits (items, ..., C);
+    truth: uint8 class indices of the mask's shape, or one-hot uint8 with a trailing C.  The kinds follow from dtype and
+    shape; tensors may be views at any byte offset as long as they are contiguous.  No synchronisation."""
+    C = int(num_classes)
+    _chk(counts, "counts", dtype=torch.int64, ndim=3), _chk(ignored, "ignored", dtype=torch.int64, ndim=1)
+    _chk(truth, "truth", dtype=torch.uint8)
+    if not isinstance(pred, torch.Tensor):
+        raise TypeError("pred must be a torch.Tensor")
+    if pred.dtype == torch.uint8:
+        pk, space = PRED_MASK, tuple(_chk(pred, "pred", dtype=torch.uint8).shape)
+    else:
+        pk = PRED_LOGITS_F32
+        _chk(pred, "pred")
+        if pred.dim() < 2 or pred.shape[-1] != C:
+            raise ValueError("float32 logits must be (items, ..., %d), got %s" % (C, tuple(pred.shape)))
+        space = tuple(pred.shape[:-1])
+    if not space:
+        raise ValueError("pred needs a leading items axis")
+    if tuple(truth.shape) == space:
+        tk = TRUTH_INDEX
+    elif tuple(truth.shape) == space + (C,):
+        tk = TRUTH_ONEHOT
+    else:
+        raise ValueError("truth has shape %s; expected %s (class indices) or %s (one-hot)"
+                         % (tuple(truth.shape), space, space + (C,)))
+    items = space[0]
+    n = 1
+    for s in space[1:]:
+        n *= s
+    if tuple(counts.shape) != (items, C, C) or tuple(ignored.shape) != (items,):
+        raise ValueError("counts / ignored have shapes %s / %s, expected %s / %s"
+                         % (tuple(counts.shape), tuple(ignored.shape), (items, C, C), (items,)))
+    lib = _lib.load()
+    if (items == 0 or n == 0) and 1 <= C <= 16:
+        return counts, ignored                                  # an empty tensor has no address to pass
+    _lib.check(lib.sq_confusion(_ptr(pred), pk, _ptr(truth), tk, _ptr(counts), _ptr(ignored), items, n, C, _stream()),
+               "sq_confusion")
+    return counts, ignored
+
+
 def pixelnorm(x, eps=1e-8, out=None):
     if x.dtype == _BF16 and out is None:
         return _gb().pixelnorm(x, eps)
