@@ -588,6 +588,43 @@ int sq_volume_centroids_u8(const uint8_t *mask, int N, int D0, int D1, int D2, v
                            float *out, int32_t *keys, int max_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Object measurements: what CentroidWriter.write's docstring promises beyond the centroid ("if the original image
+ * data is provided, some image statistics are calculated", sequitr/utils.py:492-494).  Components, connectivity and
+ * numbering are those of the centroid path above: 4 neighbours in a plane, 6 in a volume, two pixels linked only when
+ * they carry the same class > 0, a component's root = its first pixel in raster order.
+ *   mask (N,planes,H,W) uint8 class labels on the device, planes = 1 for planar masks; fewer than 2^31 elements.
+ *   image: NULL, or the mask's shape in `dtype` = SQ_PIX_U8 / SQ_PIX_U16 / SQ_PIX_F32 (defined below, "Frame cleaning").
+ *   workspace: sq_objects_workspace bytes (-1: too large), 16-B aligned: 8 B per pixel + 88 B per max_out.
+ *   found (device int32): components before the size filter; when it exceeds max_out the rows are incomplete: re-run with
+ *     max_out >= found.  count (device int32): objects kept = rows written.
+ *   An object is kept iff min_area <= area <= max_area (inclusive; min_area >= 1; max_area <= 0: no upper bound).
+ *   rows_i (max_out,12) int64, in NO particular order:
+ *     [frame, class, key, area, lo_plane, lo_row, lo_col, hi_plane, hi_row, hi_col, isum, isumsq]
+ *     key = linear index of the object's first voxel within its frame: sorting by (frame, class, key) gives the reference's
+ *     order.  hi_* are exclusive (scipy.ndimage.find_objects slices).  isum / isumsq = the exact sum of x and of x*x under
+ *     the object for integer images, 0 otherwise.
+ *   rows_f (max_out,7) float64: [centre_plane, centre_row, centre_col, sum, sumsq, min, max]
+ *     centre = (c * sum of coordinate) / (c * area) in float64, c the class: scipy.ndimage.center_of_mass(out, labels, index).
+ *     sum / sumsq / min / max of the image under the object, 0 without an image.  Integer images: exact (sumsq rounded
+ *     once to float64).  float32 images: sum and sumsq are float64 atomic adds of exact terms, so their last bits depend
+ *     on arrival order; min / max are exact and leave NaN pixels out; a NaN pixel makes sum and sumsq NaN.
+ *   slots (max_out) int32: the workspace slot of each output row, what sq_objects_relabel's rank is indexed by.
+ * sq_objects_relabel reads the workspace the measure call on the same mask left behind: rank (n_slots) int32 with
+ * n_slots = that call's max_out; labels (int32, the mask's shape, or NULL) = rank[slot of the pixel's object], 0 on
+ * background; mask_out (uint8, or NULL) = mask where that rank is not 0, else 0.  Give rank 0 to dropped objects and the
+ * 1-based position within the frame to kept ones for scipy-style label images.
+ * Both return SQ_EINVAL with a message, before any launch, for null pointers, a bad dtype, min_area < 1, max_out < 1,
+ * 2^31 or more elements, a workspace that is not 16-B aligned, an n_slots / shape that does not match the measure
+ * call that filled the workspace, labels and mask_out both NULL.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_objects_workspace(int N, int planes, int H, int W, int max_out);
+int sq_objects_measure(const uint8_t *mask, int N, int planes, int H, int W, const void *image, int dtype,
+                       int64_t min_area, int64_t max_area, void *workspace, int32_t *count, int32_t *found,
+                       int64_t *rows_i, double *rows_f, int32_t *slots, int max_out, void *stream);
+int sq_objects_relabel(const uint8_t *mask, int N, int planes, int H, int W, const void *workspace,
+                       const int32_t *rank, int n_slots, int32_t *labels, uint8_t *mask_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * EDT weight maps (the step in front of the training hot path).
  * ImageWeightMap.pipe, sequitr/pipeline.py:475-479:
  *   d = distance_transform_edt(1 - image);  out = w0*(1-image)*exp(-(d*d)/(2 sigma^2 + 1e-99)) + image + 1

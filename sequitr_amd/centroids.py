@@ -67,8 +67,10 @@ def mask_centroids(mask, as_numpy=True):
 
 class CentroidWriter(object):
     """sequitr/utils.py:479-578.  ``write(segmented)`` takes the (N,H,W) segmentation (GPU uint8 tensor, or
-    a numpy array that is uploaded) and stores frames/frame_<i>/coords = (k,5) float32 per frame.  The
-    reference writes HDF5 through h5py; when h5py is not importable the same keys go into an ``.npz``."""
+    a numpy array that is uploaded) and stores frames/frame_<i>/coords = (k,5) float32 per frame; with the original
+    image data and / or a size range also the per-object area, bounding box and intensity statistics its docstring
+    promises (utils.py:492-494).  The reference writes HDF5 through h5py; when h5py is not importable the same keys go
+    into an ``.npz``."""
 
     def __init__(self, filename=None):
         if not isinstance(filename, str):
@@ -90,32 +92,67 @@ class CentroidWriter(object):
             self._hdf = h5py.File(self.filename, 'w')
             self._hdf.create_group('frames')
 
-    def write(self, segmented, device=None):
-        if isinstance(segmented, np.ndarray):
+    def write(self, segmented, device=None, image=None, min_area=1, max_area=None):
+        """Without the keywords: the centroids, as the reference writes them.  With `image` (the original image data, the
+        segmentation's shape, uint8 / uint16 / float32, tensor or numpy array) and / or a size range [min_area, max_area]
+        the objects are measured (sequitr_amd/objects.py) and next to ``coords`` every frame gets ``area`` int64 (k,),
+        ``bbox`` int64 (k,6) [lo_plane, lo_row, lo_col, hi_plane, hi_row, hi_col] with hi exclusive (ObjectTable.bbox)
+        and, with an image, ``intensity`` float64 (k,4) [mean, std, min, max]; objects outside the size range are left
+        out.  The table stays in ``self.objects``."""
+        measure = image is not None or int(min_area) != 1 or max_area is not None
+        dev = None
+        if isinstance(segmented, np.ndarray) or isinstance(image, np.ndarray):
             dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        if isinstance(segmented, np.ndarray):
             segmented = torch.from_numpy(np.ascontiguousarray(segmented, dtype=np.uint8)).to(dev)
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image)).to(segmented.device if dev is None else dev)
+        if image is not None and tuple(image.shape) != tuple(segmented.shape):
+            raise ValueError("image %s does not have the segmentation's shape %s" % (tuple(image.shape), tuple(segmented.shape)))
         if segmented.dim() == 4:
             im_type = "Volumetric"                               # default input is N,Z,X,Y (utils.py:519-521)
             segmented = segmented.transpose(1, 3).contiguous()
+            if image is not None:
+                image = image.transpose(1, 3).contiguous()
         elif segmented.dim() == 3:
             im_type = "Image"
         else:
             logger.error("Incorrect image data shape.")
             raise ValueError("Incorrect image data shape.")
-        frames = mask_centroids(segmented)
+        extras = None
+        if measure:
+            from .objects import measure_objects
+            self.objects = table = measure_objects(segmented, image=image, min_area=min_area, max_area=max_area)
+            frames = table.coords()
+            extras = [self._extras(t) for t in table.frames()]
+        else:
+            frames = mask_centroids(segmented)
         for i, coords in enumerate(frames):
             if i % 100 == 0:
                 logger.info('Written out {0:d} of {1:d} frames ({2:s})...'.format(i, len(frames), im_type))
-            self.add_frame(i, coords)
+            self.add_frame(i, coords, **(extras[i] if extras is not None else {}))
         return frames
 
-    def add_frame(self, i, coords):
-        """store one frame's (k,5) rows as frames/frame_<i>/coords (utils.py:569-578)"""
+    @staticmethod
+    def _extras(table):
+        """the datasets of one frame's ObjectTable that go next to coords"""
+        d = {'area': table.area, 'bbox': table.bbox}
+        if table.with_intensity:
+            d['intensity'] = table.intensity()
+        return d
+
+    def add_frame(self, i, coords, **datasets):
+        """store one frame's (k,5) rows as frames/frame_<i>/coords (utils.py:569-578), and any further per-object
+        datasets (area, bbox, intensity) next to them"""
         if self._hdf is not None:
             grp = self._hdf['frames'].create_group('frame_' + str(i))
             grp.create_dataset('coords', data=coords, dtype='float32')
+            for name, data in datasets.items():
+                grp.create_dataset(name, data=data)
         else:
             self._frames['frames/frame_' + str(i) + '/coords'] = coords
+            for name, data in datasets.items():
+                self._frames['frames/frame_' + str(i) + '/' + name] = data
 
     def close(self):
         if self._hdf is not None:

@@ -413,13 +413,18 @@ def _pinned(tag, shape, dtype):
     return buf
 
 
-def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None):
+def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None,
+                   on_batch=None):
     """Segment a stack of raw frames (numpy array / memmap / OctopusData, (F,H,W) uint8|uint16|float32).
     Raw frames are staged through two pinned buffers and uploaded on a side stream while the previous batch is
     normalised, tiled, segmented (net.predict) and stitched; returns the (F,H,W) uint8 masks (host), or
     streams each batch's device masks to on_masks(first_frame, masks) and returns None.  `clean` (a FrameClean) puts
     ImageOutliers and / or ImageBGSubtract in front of ImageNorm, per whole frame, on the same stream: nothing on the host
-    waits between a batch's upload and its net.predict."""
+    waits between a batch's upload and its net.predict.  on_batch(first_frame, raw_frames, masks) is on_masks with the
+    batch's raw device frames as well (a slice of a staging buffer, valid until the callback returns: the buffer is
+    released to the next upload after it); it also makes the function return None, and only one of the two may be given."""
+    if on_masks is not None and on_batch is not None:
+        raise ValueError('on_masks and on_batch are two forms of the same sink: pass one of them')
     from .dataio.octopus import OctopusData
     if isinstance(frames, OctopusData):
         get = frames.block
@@ -444,7 +449,7 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     copy_stream = torch.cuda.Stream(device=dev)
     ready = [torch.cuda.Event(), torch.cuda.Event()]            # upload of buffer i finished
     freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[i]
-    out = None if on_masks is not None else np.empty((F, H, W), np.uint8)
+    out = None if on_masks is not None or on_batch is not None else np.empty((F, H, W), np.uint8)
 
     def upload(k, first):
         n = min(B, F - first)
@@ -480,8 +485,13 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
             tiles = tiler.tiles(staged[k][:n], normalise=normalise)
         else:
             tiles = tiler.tiles(staged[k][:n], normalise=normalise, clean=clean, scratch=scratch)
-        freed[k].record(cur)                                   # after the last kernel that reads staged[k]
+        if on_batch is None:
+            freed[k].record(cur)                               # after the last kernel that reads staged[k]
         masks = tiler.stitch(net.predict(tiles))
+        if on_batch is not None:
+            on_batch(b * B, staged[k][:n], masks)
+            freed[k].record(cur)                               # the callback's kernels read staged[k] too
+            continue
         if on_masks is not None:
             on_masks(b * B, masks)
             continue

@@ -369,6 +369,12 @@ def SERVER_segment_frames(params, options):
     (sequitr/dataio/octopus.py), a .npy of (F,H,W) uint8/uint16/float32 frames, or an ndarray.  Raw frames
     cross PCIe; ImageNorm, tiling, the U-Net and stitching run on the GPU (sequitr_amd/frontend.py).  Writes
     ``mask.npy`` (F,H,W) uint8, ``segment.json`` and, with options['centroids'], the centroid file.
+    options['measure'] (implies centroids) measures every object per batch in HBM against the RAW frames -- the camera's
+    counts, before any cleaning (sequitr_amd/objects.py): the centroid file gains per frame ``area``, ``bbox`` and
+    ``intensity`` (mean, std, min, max) next to ``coords``, ``objects.npz`` holds ObjectTable.columns() of the whole
+    stack and segment.json an ``objects`` record; options['save_labels'] adds ``labels.npy`` (F,H,W) int32, each object's
+    1-based rank within its frame.  params['min_area'] / params['max_area'] (inclusive, in pixels) drop objects outside
+    the range from all of these, and ``mask.npy`` is then the mask without them.
     params: shape (tile, default (512,512)), margin, frames_per_batch, model / filters / ... as SERVER_segment;
     pipeline: the JSON ImagePipeline.save wrote (or an ImagePipeline).  It runs on the GPU per whole frame and may hold
     any subsequence of ImageOutliers, ImageBGSubtract, ImageNorm in that order (frontend.FrameClean.from_pipeline; anything
@@ -399,8 +405,15 @@ def SERVER_segment_frames(params, options):
     else:
         net.initialize()
     per_frame = {}
-    want_centroids = bool(options.get('centroids'))
+    want_measure = bool(options.get('measure'))
+    want_centroids = bool(options.get('centroids')) or want_measure
     masks = np.empty((F, H, W), np.uint8) if want_centroids else None
+    min_area, max_area = int(params.get('min_area') or 1), params.get('max_area')
+    bounded = min_area != 1 or max_area is not None
+    if bounded and not want_measure:
+        raise ValueError("params['min_area'] / params['max_area'] need options['measure']")
+    label_stack = np.empty((F, H, W), np.int32) if want_measure and options.get('save_labels') else None
+    tables, firsts = [], []
 
     def sink(first, m):                                        # centroids need the masks while they are in HBM
         from .centroids import mask_centroids
@@ -409,12 +422,23 @@ def SERVER_segment_frames(params, options):
             coords[:, 0] = first + k
             per_frame[first + k] = coords
 
+    def measure_sink(first, raw, m):                           # objects against the raw frames, both still in HBM
+        from .objects import measure_objects
+        t = measure_objects(m, image=raw, min_area=min_area, max_area=max_area, labels=label_stack is not None,
+                            filtered_mask=bounded)
+        masks[first:first + m.shape[0]] = (t.mask if bounded else m).cpu().numpy()
+        if label_stack is not None:
+            label_stack[first:first + m.shape[0]] = t.labels.cpu().numpy()
+        tables.append(t)
+        firsts.append(first)
+
     t0 = time.time()
     # without centroids the masks come back through segment_frames' own double-buffered download (batch i-1 drains
     # while batch i runs); with them every batch is visited on the device first
     out = segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)),
-                         frames_per_batch=int(params.get('frames_per_batch', 4)), on_masks=sink if want_centroids else None,
-                         normalise=normalise, clean=clean)
+                         frames_per_batch=int(params.get('frames_per_batch', 4)),
+                         on_masks=sink if want_centroids and not want_measure else None,
+                         on_batch=measure_sink if want_measure else None, normalise=normalise, clean=clean)
     if not want_centroids:
         masks = out
     torch.cuda.synchronize()
@@ -424,7 +448,20 @@ def SERVER_segment_frames(params, options):
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
     if params.get('pipeline') is not None:
         info['pipeline'] = (clean or FrameClean()).pipes(normalise)
-    if options.get('centroids'):
+    if want_measure:
+        from .centroids import CentroidWriter
+        from .objects import ObjectTable
+        table = ObjectTable.concatenate(tables, firsts, F)
+        with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
+            for k, (coords, t) in enumerate(zip(table.coords(), table.frames())):
+                cw.add_frame(k, coords, **cw._extras(t))
+        np.savez(os.path.join(out_dir, 'objects.npz'), **table.columns())
+        if label_stack is not None:
+            np.save(os.path.join(out_dir, 'labels.npy'), label_stack)
+        info['centroids'] = {'file': os.path.basename(cw.filename), 'objects': len(table)}
+        info['objects'] = {'count': len(table), 'found': int(table.found), 'min_area': min_area,
+                           'max_area': None if max_area is None else int(max_area), 'with_intensity': True}
+    elif want_centroids:
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
             for k in sorted(per_frame):
