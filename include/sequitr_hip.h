@@ -901,14 +901,42 @@ int sq_space_to_depth2x2x2_f32(const float *dy, float *g, int N, int D, int H, i
  * tile masks back to full-frame masks.
  *   sq_frame_stats     : per-frame float32 mean and std EXACTLY as numpy's np.mean / np.std of the float32
  *                        frame (8192-element chunks, pairwise blocks of 128 with 8 accumulators); H*W <= 2^24.
- *                        workspace: sq_frame_stats_workspace bytes.
+ *                        workspace: sq_frame_stats_workspace bytes.  frames need the alignment of their pixel type
+ *                        only (a channel's slice of multi-channel planes, below).
  *   sq_frames_to_tiles : tiles (F*TR*TC, TS, TS) f32, tile (f,ty,tx) = frame f at origin (oy[ty], ox[tx]),
  *                        value (x - mean[f]) / std[f], or the plain cast when mean == std == NULL.
  *   sq_stitch_masks_u8 : out (F,H,W): pixel (y,x) = tile_masks[(f, ymap[y]>>16, xmap[x]>>16)][ymap[y]&0xffff][xmap[x]&0xffff]
+ *
+ * Multi-channel frames (bright field + fluorescence, one stack per channel: sequitr/dataio/octopus.py:321-328) are
+ * CHANNEL-MAJOR PLANES on the device: channel c of frame f is a contiguous (H, W) plane at element offset
+ * c * chan_stride + f * H * W, chan_stride >= F * H * W elements (a partial batch [:, :n] of a (C, B, H, W) buffer has
+ * chan_stride = B * H * W).  Every per-frame entry above and under "Frame cleaning" then runs unchanged on a channel's
+ * slice; per-channel statistics are (C, F) arrays, index c * F + f.
+ *   sq_frames_to_tiles_mc : tiles (F*TR*TC, TS, TS, C) f32, interleaved, sq_frames_to_tiles' geometry, C = 1 .. 8, one
+ *                        launch.  chan_mode is a HOST array of C int32, read before the launch; channel c of a tile is
+ *                          SQ_CH_CAST    : (float)v
+ *                          SQ_CH_NORM    : ((float)v - mean32[c,f]) / std32[c,f] in float32 (sq_frames_to_tiles' value)
+ *                          SQ_CH_BG      : (float)r,  r = (double)x - bg(u, v) from coef[c,f,0..5] ("Frame cleaning")
+ *                          SQ_CH_BG_NORM : (float)((r - mean64[c,f]) / (1e-99 + std64[c,f])) in fp64 (sq_frames_to_tiles_bg's)
+ *                        with bg evaluated by rows as sq_frames_to_tiles_bg does, every multiply-add of the surface one
+ *                        fused operation:  t' = fma(t, fma(c5, t, c2), c0),  b = fma(c4, t, c1),
+ *                        bg = fma(s, fma(c3, s, b), t').  Channel c has the bits sq_frames_to_tiles / sq_frames_to_tiles_bg
+ *                        give on channel c's stack.  All channels are read in one pixel type `dtype`; the two background
+ *                        modes need SQ_PIX_F32 (the float32 frames sq_frame_outliers_f32 or a cast wrote) and H, W >= 3.
+ *                        A statistics pointer may be NULL only if no channel's mode reads it.  An unknown mode or pixel
+ *                        type, C outside 1 .. 8, chan_stride < F*H*W, a tile that does not fit, F*TR*TC*TS >= 2^31 and
+ *                        tiles not 16-byte aligned are refused before any launch.
+ * Where the reference is silent: its ImageOutliers and ImageNorm already work per channel of an (H, W, C) image
+ * (sequitr/pipeline.py:174-180), its ImageBGSubtract ravels (H, W, C) against H*W rows and fails for C > 1.  Here every
+ * channel gets its own fit: the single-channel contract applied per plane.
  * ---------------------------------------------------------------------------------------- */
 #define SQ_PIX_U8 0
 #define SQ_PIX_U16 1
 #define SQ_PIX_F32 2
+#define SQ_CH_CAST 0
+#define SQ_CH_NORM 1
+#define SQ_CH_BG 2
+#define SQ_CH_BG_NORM 3
 int64_t sq_frame_stats_workspace(int F, int H, int W);
 int sq_frame_stats(const void *frames, int dtype, float *mean, float *stdv, void *workspace, int F, int H, int W,
                    void *stream);
@@ -916,6 +944,10 @@ int sq_frames_to_tiles(const void *frames, int dtype, const float *mean, const f
                        const int32_t *ox, float *tiles, int F, int H, int W, int TR, int TC, int TS, void *stream);
 int sq_stitch_masks_u8(const uint8_t *tile_masks, const int32_t *ymap, const int32_t *xmap, uint8_t *out, int F, int H,
                        int W, int TR, int TC, int TS, void *stream);
+int sq_frames_to_tiles_mc(const void *frames, int dtype, int64_t chan_stride, const int32_t *chan_mode, const float *mean32,
+                          const float *std32, const double *coef, const double *mean64, const double *std64,
+                          const int32_t *oy, const int32_t *ox, float *tiles, int F, int H, int W, int C, int TR, int TC,
+                          int TS, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frame cleaning: the pipes the reference applies to raw microscope frames in front of ImageNorm, per whole frame,
@@ -1058,11 +1090,26 @@ int sq_volume_sample_onehot_u8(const uint8_t *labels, int C, const int32_t *plan
  * and interpolates from there; a block whose box exceeds 48 x 48 pixels (a zooming or shearing row) still gathers
  * directly.  SQ_ROTATE_LDS=0 selects the direct gather everywhere.  Unset is the direct gather, the faster form as
  * measured (tools/tile_sampler_bench.py); both give the same bits.
+ *   sq_tile_sample_affine_mc : sq_tile_sample_affine with CI image channels, 1 .. 8.  frames are channel-major planes
+ *                           ("Tile front end": channel c of frame f at c * chan_stride + f * H * W, chan_stride >= F*H*W),
+ *                           mean and stdv are (CI, F), out_image is (count, TH, TW, CI) interleaved.  sx, sy, the corner
+ *                           indices and the bilinear weights are computed once per pixel and applied to every channel
+ *                           with the same float32 expressions; labels, weights, plan, coef, the fill rules, the NaN and
+ *                           +-2^23 rule, "no load ever leaves the arrays" and SQ_ROTATE_LDS are the contract above, word
+ *                           for word (under SQ_ROTATE_LDS=1 the planes pass through the staging buffer one after the
+ *                           other and the image is stored one channel per pass, CI floats apart; only the default
+ *                           direct form was timed for this entry, tools/multichannel_bench.py).  Channel c has the bits sq_tile_sample_affine gives on channel c's stack, and with
+ *                           CI == 1 the call is sq_tile_sample_affine.  CI outside 1 .. 8 or chan_stride < F*H*W (with
+ *                           frames given) is refused before any launch, next to everything the entry above refuses.
  * ---------------------------------------------------------------------------------------- */
 int sq_tile_sample_affine(const void *frames, int dtype, const float *mean, const float *stdv, const uint8_t *labels,
                           const float *weights, const int32_t *plan, const float *coef, float *out_image,
                           uint8_t *out_onehot, float *out_weights, int F, int H, int W, int TH, int TW, int C, int count,
                           void *stream);
+int sq_tile_sample_affine_mc(const void *frames, int dtype, int64_t chan_stride, const float *mean, const float *stdv,
+                             const uint8_t *labels, const float *weights, const int32_t *plan, const float *coef,
+                             float *out_image, uint8_t *out_onehot, float *out_weights, int F, int H, int W, int CI, int TH,
+                             int TW, int C, int count, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAN sampler: the progressive GAN's real images, the third sampler -- the reference's input pipeline in front of its

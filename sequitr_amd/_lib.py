@@ -75,6 +75,7 @@ SIGNATURES = {
     "sq_frame_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "sq_frames_to_tiles": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
     "sq_stitch_masks_u8": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "sq_frames_to_tiles_mc": (c_int, [c_void_p, c_int, c_int64] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
     "sq_frame_outliers_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "sq_frame_bgfit_workspace": (c_int64, [c_int, c_int, c_int]),
     "sq_frame_bgfit_f64": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "sq_volume_sample_copy": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "sq_volume_sample_onehot_u8": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "sq_tile_sample_affine": (c_int, [c_void_p, c_int] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
+    "sq_tile_sample_affine_mc": (c_int, [c_void_p, c_int, c_int64] + [c_void_p] * 9 + [c_int] * 8 + [c_void_p]),
     "sq_gan_image_stats_workspace": (c_int64, [c_int, c_int]),
     "sq_gan_image_stats": (c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "sq_gan_sample_f32": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),

@@ -94,7 +94,10 @@ extern "C" int sq_frame_stats(const void *frames, int dtype, float *mean, float 
                               int W, void *stream) {
     SQ_REQUIRE(frames && mean && stdv && workspace, "sq_frame_stats: null pointer");
     SQ_REQUIRE(sq_frame_stats_workspace(F, H, W) > 0, "sq_frame_stats: need F, H, W > 0 and H*W <= 2^24");
-    SQ_REQUIRE_ALIGNED(frames);
+    // aligned to the pixel type: a channel's slice of multi-channel planes starts wherever c * chan_stride falls, as frame
+    // f > 0 of an odd-sized stack always did (the kernel reads element by element)
+    SQ_REQUIRE((uintptr_t)frames % (dtype == SQ_PIX_U16 ? 2 : dtype == SQ_PIX_F32 ? 4 : 1) == 0,
+               "sq_frame_stats: frames not aligned to their pixel type");
     hipStream_t st = (hipStream_t)stream;
     const int64_t npix = (int64_t)H * W;
     float *ws = reinterpret_cast<float *>(workspace);

@@ -40,6 +40,8 @@ import torch
 from . import _lib
 
 PIX = {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}
+CH_CAST, CH_NORM, CH_BG, CH_BG_NORM = 0, 1, 2, 3               # SQ_CH_*: a channel's mode in sq_frames_to_tiles_mc
+MAX_CHANNELS = 8
 NP_TORCH = {np.dtype('uint8'): torch.uint8, np.dtype('uint16'): torch.uint16, np.dtype('float32'): torch.float32}
 
 
@@ -190,12 +192,31 @@ class FrameClean(object):
         return (clean if clean else None), normalise
 
 
-class FrameTiler(object):
-    """Geometry + device kernels for frames of one (H, W) shape."""
+def channel_cleans(clean, channels):
+    """`clean` of tiles() / segment_frames() as one entry per channel: a FrameClean or None applies to every channel, a
+    sequence holds one FrameClean or None per channel"""
+    if clean is None or isinstance(clean, FrameClean):
+        return [clean if clean else None] * channels
+    if isinstance(clean, (list, tuple)):
+        if len(clean) != channels:
+            raise ValueError('clean holds %d entries for %d channels' % (len(clean), channels))
+        if all(c is None or isinstance(c, FrameClean) for c in clean):
+            return [c if c else None for c in clean]
+    raise TypeError('clean must be a FrameClean, None or a sequence of them, one per channel, got %r' % (clean,))
 
-    def __init__(self, frame_shape, tile=512, margin=32, device=None):
+
+class FrameTiler(object):
+    """Geometry + device kernels for frames of one (H, W) shape.  With channels > 1 the frames are channel-major planes,
+    a (C, F, H, W) tensor or the [:, :n] view of a contiguous (C, B, H, W) one (include/sequitr_hip.h "Tile front end"):
+    every per-frame kernel runs on each channel's slice, statistics come back as (C, F), and tiles() weaves the planes into
+    (F*TR*TC, T, T, C) in one launch."""
+
+    def __init__(self, frame_shape, tile=512, margin=32, device=None, channels=1):
         self.H, self.W = int(frame_shape[0]), int(frame_shape[1])
         self.T, self.margin = int(tile), int(margin)
+        self.channels = int(channels)
+        if not 1 <= self.channels <= MAX_CHANNELS:
+            raise ValueError('%d channels are not 1 .. %d' % (self.channels, MAX_CHANNELS))
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
         if self.device.type != 'cuda':
             raise _lib.SequitrHipError('FrameTiler runs on the HIP back end only')
@@ -205,12 +226,34 @@ class FrameTiler(object):
         d = self.device
         self._oy, self._ox = torch.from_numpy(self.oy).to(d), torch.from_numpy(self.ox).to(d)
         self._ymap, self._xmap = torch.from_numpy(self.ymap).to(d), torch.from_numpy(self.xmap).to(d)
+        if self.channels > 1:                                   # the per-frame kernels, on one channel's slice at a time
+            self._one = FrameTiler.__new__(FrameTiler)
+            self._one.__dict__.update(self.__dict__, channels=1)
 
     @property
     def tiles_per_frame(self):
         return self.TR * self.TC
 
+    def _check_planes(self, frames, dtypes=None):
+        """(C, F, H, W) channel-major planes: every (H, W) plane contiguous, frames of a channel back to back"""
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise _lib.SequitrHipError('frames must be a tensor in GPU memory (no CPU fallback exists)')
+        C, H, W = self.channels, self.H, self.W
+        if frames.dtype not in (dtypes or PIX) or frames.dim() != 4 or frames.shape[0] != C or frames.shape[1] < 1:
+            raise ValueError('frames must be a (%d,F,H,W) %s tensor of channel-major planes, got %s %s' % (
+                C, ' / '.join(str(d).replace('torch.', '') for d in (dtypes or PIX)), frames.dtype, tuple(frames.shape)))
+        if tuple(frames.shape[2:]) != (H, W):
+            raise ValueError('frames are %s, tiler was built for %s' % (tuple(frames.shape[2:]), (H, W)))
+        F = int(frames.shape[1])
+        st = frames.stride()
+        if (st[3], st[2]) != (1, W) or (F > 1 and st[1] != H * W) or st[0] < F * H * W:
+            raise ValueError('frames must be contiguous (C,F,H,W) planes or the [:, :n] view of a contiguous (C,B,H,W) buffer, '
+                             'got strides %r' % (st,))
+        return F
+
     def _check_frames(self, frames):
+        if self.channels > 1:
+            raise ValueError('this tiler was built for %d channels: pass (C,F,H,W) planes' % self.channels)
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise _lib.SequitrHipError('frames must be a tensor in GPU memory (no CPU fallback exists)')
         if frames.dtype not in PIX or frames.dim() != 3 or not frames.is_contiguous():
@@ -219,7 +262,9 @@ class FrameTiler(object):
             raise ValueError('frames are %s, tiler was built for %s' % (tuple(frames.shape[1:]), (self.H, self.W)))
 
     def stats(self, frames, scratch=None):
-        """per-frame float32 (mean, std) exactly as np.mean / np.std of the float32 frame."""
+        """per-frame float32 (mean, std) exactly as np.mean / np.std of the float32 frame; (C, F) each with channels > 1."""
+        if self.channels > 1:
+            return self._mc_stats(frames, scratch)
         self._check_frames(frames)
         F = frames.shape[0]
         lib = _lib.load()
@@ -239,6 +284,8 @@ class FrameTiler(object):
     def clean_scratch(self, F, clean, normalise=True):
         """The tensors tiles(..., clean=clean) needs for up to F frames, so that a caller that streams batches (segment_frames)
         allocates them once: the cleaned float32 frames and, per chain, the fit's coefficients, statistics and workspaces."""
+        if self.channels > 1:
+            return self._mc_scratch(F, channel_cleans(clean, self.channels), normalise)
         if not clean:
             return None
         F, d, lib = int(F), self.device, _lib.load()
@@ -273,7 +320,14 @@ class FrameTiler(object):
             raise ValueError('the background fit reads float32 frames (outliers() or to_f32() make them), got %s' % frames.dtype)
 
     def outliers(self, frames, size, threshold, out=None):
-        """ImageOutliers(sigma=size, threshold) of every raw frame: (F,H,W) float32, bit-exact with the host pipe."""
+        """ImageOutliers(sigma=size, threshold) of every raw frame: (F,H,W) float32, bit-exact with the host pipe
+        ((C,F,H,W) planes in, (C,F,H,W) out with channels > 1)."""
+        if self.channels > 1:
+            F = self._check_planes(frames)
+            out = self._mc_f32_out(F, out)
+            for c in range(self.channels):
+                self._one.outliers(frames[c], size, threshold, out=out[c])
+            return out
         self._check_frames(frames)
         size = FrameClean(outliers=(size, threshold)).outliers[0]
         if min(self.H, self.W) < size:
@@ -288,6 +342,14 @@ class FrameTiler(object):
     def to_f32(self, frames, out=None):
         """the raw frames cast to float32 (what ImagePipe.__call__ does first): float32 frames are returned as they are,
         integer ones go through the volume front end's cast, every frame one brick of a one-slice volume"""
+        if self.channels > 1:
+            F = self._check_planes(frames)
+            if frames.dtype == torch.float32:
+                return frames
+            out = self._mc_f32_out(F, out)
+            for c in range(self.channels):
+                self._one.to_f32(frames[c], out=out[c])
+            return out
         self._check_frames(frames)
         if frames.dtype == torch.float32:
             return frames
@@ -315,7 +377,16 @@ class FrameTiler(object):
     def background(self, frames_f32, scratch=None):
         """ImageBGSubtract's least-squares surface of every float32 frame: coef (F,6) float64 with
         bg(u, v) = c0 + c1 s + c2 t + c3 s^2 + c4 s t + c5 t^2, s = (u - (W-1)/2) / ((W-1)/2) for column u and
-        t = (v - (H-1)/2) / ((H-1)/2) for row v (include/sequitr_hip.h "Frame cleaning")."""
+        t = (v - (H-1)/2) / ((H-1)/2) for row v (include/sequitr_hip.h "Frame cleaning").  With channels > 1 every
+        channel of every frame gets its own fit, coef (C,F,6): the single-channel contract per plane (the reference's
+        ImageBGSubtract does not take more than one channel)."""
+        if self.channels > 1:
+            F = self._check_planes(frames_f32, (torch.float32,))
+            ws = self._bg_workspace(F, scratch)
+            coef = torch.empty((self.channels, F, 6), dtype=torch.float64, device=self.device)
+            for c in range(self.channels):
+                self._one.background(frames_f32[c], scratch={'bg_ws': ws, 'coef': coef[c]})
+            return coef
         self._check_f32(frames_f32)
         F = frames_f32.shape[0]
         ws = self._bg_workspace(F, scratch)
@@ -325,7 +396,18 @@ class FrameTiler(object):
         return coef
 
     def background_stats(self, frames_f32, coef, scratch=None):
-        """per-frame float64 (mean, std) of the residual frame - bg(coef), np.std's definition"""
+        """per-frame float64 (mean, std) of the residual frame - bg(coef), np.std's definition; (C, F) each with channels > 1"""
+        if self.channels > 1:
+            F = self._check_planes(frames_f32, (torch.float32,))
+            C = self.channels
+            if not (isinstance(coef, torch.Tensor) and coef.is_cuda and coef.dtype == torch.float64 and coef.is_contiguous()
+                    and tuple(coef.shape) == (C, F, 6)):
+                raise ValueError('coef must be the contiguous (%d,%d,6) float64 tensor background() returned' % (C, F))
+            ws = self._bg_workspace(F, scratch)
+            mean, std = (torch.empty((C, F), dtype=torch.float64, device=self.device) for _ in range(2))
+            for c in range(C):
+                self._one.background_stats(frames_f32[c], coef[c], scratch={'bg_ws': ws, 'mean64': mean[c], 'std64': std[c]})
+            return mean, std
         self._check_f32(frames_f32)
         F = frames_f32.shape[0]
         self._check_coef(coef, F)
@@ -368,7 +450,11 @@ class FrameTiler(object):
     def tiles(self, frames, normalise=True, clean=None, scratch=None):
         """(F*TR*TC, T, T, 1) float32 tiles, ImageNorm applied per frame when `normalise`; with `clean` (a FrameClean) the
         frames go through ImageOutliers and / or ImageBGSubtract first, per whole frame (`scratch`: clean_scratch(), for
-        callers that come back batch after batch)."""
+        callers that come back batch after batch).  With channels > 1: (C,F,H,W) planes in, (F*TR*TC, T, T, C) tiles out of
+        one sq_frames_to_tiles_mc launch, `clean` one FrameClean for all channels or a sequence of C (None: that channel is
+        not cleaned)."""
+        if self.channels > 1:
+            return self._mc_tiles(frames, normalise, clean, scratch)
         self._check_frames(frames)
         if clean:
             if not isinstance(clean, FrameClean):
@@ -383,6 +469,108 @@ class FrameTiler(object):
                                           self._oy.data_ptr(), self._ox.data_ptr(), out.data_ptr(), F, self.H, self.W,
                                           self.TR, self.TC, self.T, torch.cuda.current_stream().cuda_stream),
                    'sq_frames_to_tiles')
+        return out
+
+    # ---- channels > 1 -----------------------------------------------------------------------------------------------
+    def _mc_f32_out(self, F, out):
+        C = self.channels
+        if out is None:
+            return torch.empty((C, F, self.H, self.W), dtype=torch.float32, device=self.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
+                and tuple(out.shape) == (C, F, self.H, self.W)):
+            raise ValueError('out must be a (%d,%d,%d,%d) float32 tensor in GPU memory' % (C, F, self.H, self.W))
+        self._check_planes(out, (torch.float32,))
+        return out
+
+    def _mc_stats(self, frames, scratch=None):
+        F = self._check_planes(frames)
+        C = self.channels
+        nbytes = _lib.load().sq_frame_stats_workspace(F, self.H, self.W)
+        if nbytes < 0:
+            raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
+        if scratch is not None and 'stats_ws' in scratch:        # clean_scratch() made them when a channel's mode reads them
+            ws, mean, std = scratch['stats_ws'], self._rows(scratch['mean'], F), self._rows(scratch['std'], F)
+        else:
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            mean, std = (torch.empty((C, F), dtype=torch.float32, device=self.device) for _ in range(2))
+        for c in range(C):
+            self._one.stats(frames[c], scratch={'stats_ws': ws, 'mean': mean[c], 'std': std[c]})
+        return mean, std
+
+    def _rows(self, flat, F, tail=()):
+        """the (C, F) + tail array at the start of a flat scratch buffer made for more frames: index c * F + f"""
+        n = self.channels * F * int(np.prod(tail, dtype=np.int64))
+        return flat[:n].view((self.channels, F) + tuple(tail))
+
+    def _mc_scratch(self, F, cleans, normalise):
+        """clean_scratch for channel-major planes: one float32 copy of all channels when any is cleaned, and flat buffers
+        for whatever statistics the channels' modes read"""
+        F, C, d, lib = int(F), self.channels, self.device, _lib.load()
+        s = {'frames': F, 'cleans': tuple(cleans), 'normalise': bool(normalise)}
+        if any(cleans):
+            s['f32'] = torch.empty((C, F, self.H, self.W), dtype=torch.float32, device=d)
+        if any(c is not None and c.bgsubtract for c in cleans):
+            nbytes = lib.sq_frame_bgfit_workspace(F, self.H, self.W)
+            if nbytes < 0:
+                raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
+                                 '%d x %d' % (F, self.H, self.W))
+            s['bg_ws'] = torch.empty(nbytes // 8, dtype=torch.float64, device=d)
+            s['coef'] = torch.empty(C * F * 6, dtype=torch.float64, device=d)
+            if normalise:
+                s['mean64'], s['std64'] = (torch.empty(C * F, dtype=torch.float64, device=d) for _ in range(2))
+        if normalise and any(c is None or not c.bgsubtract for c in cleans):
+            nbytes = lib.sq_frame_stats_workspace(F, self.H, self.W)
+            if nbytes < 0:
+                raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
+            s['stats_ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=d)
+            s['mean'], s['std'] = (torch.empty(C * F, dtype=torch.float32, device=d) for _ in range(2))
+        return s
+
+    def _mc_tiles(self, frames, normalise, clean, scratch):
+        F = self._check_planes(frames)
+        C, one = self.channels, self._one
+        cleans = channel_cleans(clean, C)
+        if scratch is None:
+            scratch = self._mc_scratch(F, cleans, normalise)
+        elif scratch['frames'] < F or scratch['cleans'] != tuple(cleans) or scratch['normalise'] != bool(normalise):
+            raise ValueError('scratch was made by clean_scratch(%d, %r, %r): it does not serve %d frames under %r, %r'
+                             % (scratch['frames'], scratch['cleans'], scratch['normalise'], F, cleans, bool(normalise)))
+        src = frames
+        if any(cleans):                                         # one pixel type for the launch: float32, cleaned or cast
+            src = scratch['f32'][:, :F]
+            for c in range(C):
+                if cleans[c] is not None and cleans[c].outliers is not None:
+                    one.outliers(frames[c], cleans[c].outliers[0], cleans[c].outliers[1], out=src[c])
+                elif frames.dtype == torch.float32:
+                    src[c].copy_(frames[c])
+                else:
+                    one.to_f32(frames[c], out=src[c])
+        mean32 = std32 = coef = mean64 = std64 = None
+        if 'mean' in scratch:
+            mean32, std32 = self._rows(scratch['mean'], F), self._rows(scratch['std'], F)
+        if 'coef' in scratch:
+            coef = self._rows(scratch['coef'], F, (6,))
+        if 'mean64' in scratch:
+            mean64, std64 = self._rows(scratch['mean64'], F), self._rows(scratch['std64'], F)
+        modes = np.zeros(C, np.int32)
+        for c in range(C):
+            if cleans[c] is not None and cleans[c].bgsubtract:
+                sub = {'bg_ws': scratch['bg_ws'], 'coef': coef[c]}
+                one.background(src[c], scratch=sub)
+                if normalise:
+                    sub['mean64'], sub['std64'] = mean64[c], std64[c]
+                    one.background_stats(src[c], coef[c], scratch=sub)
+                modes[c] = CH_BG_NORM if normalise else CH_BG
+            elif normalise:
+                one.stats(src[c], scratch={'stats_ws': scratch['stats_ws'], 'mean': mean32[c], 'std': std32[c]})
+                modes[c] = CH_NORM
+        out = torch.empty((F * self.TR * self.TC, self.T, self.T, C), dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(_lib.load().sq_frames_to_tiles_mc(src.data_ptr(), PIX[src.dtype], src.stride(0), modes.ctypes.data,
+                                                     ptr(mean32), ptr(std32), ptr(coef), ptr(mean64), ptr(std64),
+                                                     self._oy.data_ptr(), self._ox.data_ptr(), out.data_ptr(), F, self.H,
+                                                     self.W, C, self.TR, self.TC, self.T,
+                                                     torch.cuda.current_stream().cuda_stream), 'sq_frames_to_tiles_mc')
         return out
 
     def stitch(self, tile_masks):
@@ -413,6 +601,43 @@ def _pinned(tag, shape, dtype):
     return buf
 
 
+def open_channels(frames):
+    """What segment_frames reads, without touching a pixel: (gets, (F, H, W), numpy dtype, C).  `frames` is an OctopusData
+    or an (F,H,W) array (C is None: the single-channel path), a list or tuple of C such sources of one dtype, shape and
+    length, or one interleaved (F,H,W,C) array.  gets[i](first, count) returns source i's frames."""
+    from .dataio.octopus import OctopusData
+
+    def one(src):
+        if isinstance(src, OctopusData):
+            return src.block, (len(src),) + tuple(int(v) for v in src.framesize), np.dtype('uint' + str(src.bit_depth))
+        if not hasattr(src, 'shape') or not hasattr(src, 'dtype'):
+            raise TypeError('a source of frames is an OctopusData or an array, got %r' % (type(src),))
+        return (lambda first, count: src[first:first + count]), tuple(int(v) for v in src.shape), np.dtype(src.dtype)
+
+    if isinstance(frames, (list, tuple)):
+        if not 1 <= len(frames) <= MAX_CHANNELS:
+            raise ValueError('%d channels are not 1 .. %d' % (len(frames), MAX_CHANNELS))
+        opened = [one(src) for src in frames]
+        shape, dtype = opened[0][1], opened[0][2]
+        if len(shape) != 3:
+            raise ValueError('every channel is an (F,H,W) stack, got shape %r' % (shape,))
+        for i, (_, sh, dt) in enumerate(opened):
+            if sh != shape or dt != dtype:
+                raise ValueError('channel %d is %s %r, channel 0 is %s %r: the channels of a stack share one length, shape '
+                                 'and pixel type' % (i, dt, sh, dtype, shape))
+        return [o[0] for o in opened], shape, dtype, len(opened)
+    get, shape, dtype = one(frames)
+    if len(shape) == 4:
+        if not 1 <= shape[3] <= MAX_CHANNELS:
+            raise ValueError('%d channels are not 1 .. %d' % (shape[3], MAX_CHANNELS))
+        if shape[3] == 1:
+            return [lambda first, count: get(first, count)[..., 0]], shape[:3], dtype, 1
+        return [get], shape[:3], dtype, shape[3]
+    if len(shape) != 3:
+        raise ValueError('frames are (F,H,W), (F,H,W,C) or a list of (F,H,W) stacks, got shape %r' % (shape,))
+    return [get], shape, dtype, None
+
+
 def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None,
                    on_batch=None):
     """Segment a stack of raw frames (numpy array / memmap / OctopusData, (F,H,W) uint8|uint16|float32).
@@ -422,30 +647,38 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     ImageOutliers and / or ImageBGSubtract in front of ImageNorm, per whole frame, on the same stream: nothing on the host
     waits between a batch's upload and its net.predict.  on_batch(first_frame, raw_frames, masks) is on_masks with the
     batch's raw device frames as well (a slice of a staging buffer, valid until the callback returns: the buffer is
-    released to the next upload after it); it also makes the function return None, and only one of the two may be given."""
+    released to the next upload after it); it also makes the function return None, and only one of the two may be given.
+
+    Multi-channel frames: `frames` may be a list or tuple of C sources of one dtype, shape and length (each an OctopusData
+    or an (F,H,W) array -- the Octopus layout, one stack per channel), or one interleaved (F,H,W,C) array, which is
+    de-interleaved while it is copied into the pinned buffer.  Staging is then (C,B,H,W) channel-major planes, on_batch
+    receives the raw (C,n,H,W) view, `clean` is one FrameClean for all channels or a sequence of C (None entries: no
+    cleaning), and net.n_inputs must equal C (checked before any upload).  The masks are (F,H,W) as ever."""
     if on_masks is not None and on_batch is not None:
         raise ValueError('on_masks and on_batch are two forms of the same sink: pass one of them')
-    from .dataio.octopus import OctopusData
-    if isinstance(frames, OctopusData):
-        get = frames.block
-        F, (H, W) = len(frames), frames.framesize
-        np_dtype = np.dtype('uint' + str(frames.bit_depth))
-    else:
-        arr = frames
-        F, H, W = arr.shape
-        np_dtype = np.dtype(arr.dtype)
-        get = lambda first, count: arr[first:first + count]
+    gets, (F, H, W), np_dtype, C = open_channels(frames)
     if np_dtype not in NP_TORCH:
         raise TypeError('frames must be uint8, uint16 or float32, got %s' % np_dtype)
+    if C is not None and int(net.n_inputs) != C:
+        raise ValueError('the network takes %d input channels, the frames have %d' % (int(net.n_inputs), C))
     tdt = NP_TORCH[np_dtype]
-    tiler = FrameTiler((H, W), tile, margin, device=net.device)
+    tiler = FrameTiler((H, W), tile, margin, device=net.device, channels=C or 1)
     dev = tiler.device
     B = int(frames_per_batch)
-    pinned = [_pinned('in%d' % i, (B, H, W), tdt) for i in range(2)]
-    staged = [torch.empty((B, H, W), dtype=tdt, device=dev) for _ in range(2)]
-    if clean is not None and not isinstance(clean, FrameClean):
-        raise TypeError('clean must be a FrameClean or None, got %r' % (clean,))
-    scratch = tiler.clean_scratch(B, clean, normalise)          # once per call; the batches share it on the compute stream
+    if C is None or C == 1:
+        lead, take = (), (lambda t, n: t[:n])
+        cleans = clean
+        if C == 1 and isinstance(clean, (list, tuple)):        # a list of one source may come with a list of one clean
+            cleans = channel_cleans(clean, 1)[0]
+        if cleans is not None and not isinstance(cleans, FrameClean):
+            raise TypeError('clean must be a FrameClean or None, got %r' % (clean,))
+    else:
+        lead, take = (C,), (lambda t, n: t[:, :n])
+        cleans = channel_cleans(clean, C)
+    pinned = [_pinned('in%d' % i, lead + (B, H, W), tdt) for i in range(2)]
+    staged = [torch.empty(lead + (B, H, W), dtype=tdt, device=dev) for _ in range(2)]
+    scratch = tiler.clean_scratch(B, cleans, normalise)         # once per call; the batches share it on the compute stream
+    clean = cleans
     copy_stream = torch.cuda.Stream(device=dev)
     ready = [torch.cuda.Event(), torch.cuda.Event()]            # upload of buffer i finished
     freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[i]
@@ -454,10 +687,20 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     def upload(k, first):
         n = min(B, F - first)
         ready[k].synchronize()                                 # the previous upload out of this pinned buffer is done
-        pinned[k][:n].numpy()[...] = get(first, n)             # page cache / memmap -> pinned
+        if not lead:
+            pinned[k][:n].numpy()[...] = gets[0](first, n)     # page cache / memmap -> pinned
+        elif len(gets) == 1:                                    # interleaved (n,H,W,C): de-interleaved by this one host copy
+            pinned[k][:, :n].numpy()[...] = np.moveaxis(gets[0](first, n), -1, 0)
+        else:
+            for c, get in enumerate(gets):
+                pinned[k][c, :n].numpy()[...] = get(first, n)
         with torch.cuda.stream(copy_stream):
             copy_stream.wait_event(freed[k])
-            staged[k][:n].copy_(pinned[k][:n], non_blocking=True)
+            if not lead:
+                staged[k][:n].copy_(pinned[k][:n], non_blocking=True)
+            else:
+                for c in range(C):                              # a channel's n frames are contiguous on both sides
+                    staged[k][c, :n].copy_(pinned[k][c, :n], non_blocking=True)
             ready[k].record(copy_stream)
         return n
 
@@ -482,14 +725,14 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         cur.wait_event(ready[k])
         n = counts[b]
         if scratch is None:
-            tiles = tiler.tiles(staged[k][:n], normalise=normalise)
+            tiles = tiler.tiles(take(staged[k], n), normalise=normalise)
         else:
-            tiles = tiler.tiles(staged[k][:n], normalise=normalise, clean=clean, scratch=scratch)
+            tiles = tiler.tiles(take(staged[k], n), normalise=normalise, clean=clean, scratch=scratch)
         if on_batch is None:
             freed[k].record(cur)                               # after the last kernel that reads staged[k]
         masks = tiler.stitch(net.predict(tiles))
         if on_batch is not None:
-            on_batch(b * B, staged[k][:n], masks)
+            on_batch(b * B, take(staged[k], n), masks)
             freed[k].record(cur)                               # the callback's kernels read staged[k] too
             continue
         if on_masks is not None:
@@ -898,10 +1141,15 @@ def tile_sample_plan(frame_shape, tile, frames, count, rng, augment=('rotate',),
 class TileSampler(object):
     """Rotated training tiles cut on the GPU out of whole frames, labels and weight maps that stay in HBM -- the planar twin
     of VolumeSampler and the device form of the reference's tr_augment (include/sequitr_hip.h "Tile sampler").  `plan` and
-    `coef` are tile_sample_plan's rows (or a slice of them) in GPU memory; one launch fills all three outputs."""
+    `coef` are tile_sample_plan's rows (or a slice of them) in GPU memory; one launch fills all three outputs.  With
+    channels > 1 the frames are (C, F, H, W) channel-major planes (FrameTiler's layout), the statistics (C, F) and the image
+    output (count, TH, TW, C) -- sq_tile_sample_affine_mc; labels and weights are as ever."""
 
-    def __init__(self, frame_shape, tile, device=None):
+    def __init__(self, frame_shape, tile, device=None, channels=1):
         self.shape, self.tile = tuple(int(s) for s in frame_shape), tuple(int(s) for s in tile)
+        self.channels = int(channels)
+        if not 1 <= self.channels <= MAX_CHANNELS:
+            raise ValueError('%d channels are not 1 .. %d' % (self.channels, MAX_CHANNELS))
         if len(self.shape) != 2 or len(self.tile) != 2 or min(self.shape + self.tile) < 1:
             raise ValueError('frame_shape and tile are (H, W) pairs of positive sizes, got %r and %r' % (frame_shape, tile))
         if self.shape[0] * self.shape[1] > 1 << 24:
@@ -912,9 +1160,9 @@ class TileSampler(object):
         self._tiler = None
 
     def stats(self, frames):
-        """per-frame float32 (mean, std) of the whole frames: FrameTiler.stats"""
+        """per-frame float32 (mean, std) of the whole frames: FrameTiler.stats ((C, F) each with channels > 1)"""
         if self._tiler is None:
-            self._tiler = FrameTiler(self.shape, min(self.shape), 0, device=self.device)
+            self._tiler = FrameTiler(self.shape, min(self.shape), 0, device=self.device, channels=self.channels)
         return self._tiler.stats(frames)
 
     def _check(self, t, what, dtypes, channel=False):
@@ -950,7 +1198,10 @@ class TileSampler(object):
         (F, H, W) uint8 / uint16 / float32 frames, the class-index uint8 labels and the float32 weight maps (F, H, W[, 1]).
         Any of the three sources may be None, and its output is then None.  ImageNorm is applied per whole frame when
         `normalise` (with `stats` = self.stats(frames) when the caller already has them).  `out` takes the three
-        preallocated tensors (None for a source that is None)."""
+        preallocated tensors (None for a source that is None).  With channels > 1 the frames are (C, F, H, W) planes, the
+        stats (C, F) and the image (count, TH, TW, C)."""
+        if self.channels > 1:
+            return self._sample_mc(frames, labels, weights, plan, coef, C, normalise, stats, out)
         count = self._rows(plan, 'plan', 4, torch.int32)
         if self._rows(coef, 'coef', 6, torch.float32) != count:
             raise ValueError('plan has %d rows, coef %d' % (count, coef.shape[0]))
@@ -986,6 +1237,47 @@ class TileSampler(object):
                                                      ptr(o_img), ptr(o_hot), ptr(o_wts), F, self.shape[0], self.shape[1],
                                                      self.tile[0], self.tile[1], C, count,
                                                      torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine')
+        return o_img, o_hot, o_wts
+
+    def _sample_mc(self, frames, labels, weights, plan, coef, C, normalise, stats, out):
+        count = self._rows(plan, 'plan', 4, torch.int32)
+        if self._rows(coef, 'coef', 6, torch.float32) != count:
+            raise ValueError('plan has %d rows, coef %d' % (count, coef.shape[0]))
+        if not 1 <= count <= 65535:
+            raise ValueError('a plan of %d rows is not one launch (1 .. 65535 rows)' % count)
+        C, CI = int(C), self.channels
+        if not 1 <= C <= 16:
+            raise ValueError('%d classes are not 1 .. 16' % C)
+        if frames is None and labels is None and weights is None:
+            raise ValueError('give at least one of frames, labels and weights')
+        F = [self._check(t, what, dt, ch) for t, what, dt, ch in (
+            (labels, 'labels', (torch.uint8,), False), (weights, 'weights', (torch.float32,), True)) if t is not None]
+        if frames is not None:
+            if self._tiler is None:
+                self._tiler = FrameTiler(self.shape, min(self.shape), 0, device=self.device, channels=CI)
+            F.append(self._tiler._check_planes(frames))
+        if len(set(F)) != 1:
+            raise ValueError('frames, labels and weights must hold the same number of frames, got %r' % (F,))
+        F = F[0]
+        if out is None:
+            out = (None, None, None)
+        if len(out) != 3:
+            raise ValueError('out takes the three tensors (image, onehot, weights)')
+        mean = std = None
+        if frames is not None and normalise:
+            mean, std = stats if stats is not None else self.stats(frames)
+            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (CI, F)
+                       and t.is_contiguous() for t in (mean, std)):
+                raise ValueError('stats must be the (mean, std) float32 tensors (%d, %d) of these frames in GPU memory' % (CI, F))
+        o_img = self._out(out[0], count, CI, torch.float32) if frames is not None else None
+        o_hot = self._out(out[1], count, C, torch.uint8) if labels is not None else None
+        o_wts = self._out(out[2], count, 1, torch.float32) if weights is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(_lib.load().sq_tile_sample_affine_mc(
+            ptr(frames), PIX[frames.dtype] if frames is not None else 0, frames.stride(0) if frames is not None else 0,
+            ptr(mean), ptr(std), ptr(labels), ptr(weights), plan.data_ptr(), coef.data_ptr(), ptr(o_img), ptr(o_hot),
+            ptr(o_wts), F, self.shape[0], self.shape[1], CI, self.tile[0], self.tile[1], C, count,
+            torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine_mc')
         return o_img, o_hot, o_wts
 
 

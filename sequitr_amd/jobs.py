@@ -364,6 +364,82 @@ def _open_frames(params):
     return frames, int(F), int(H), int(W)
 
 
+def _open_channels(params):
+    """params['input'] of the frame jobs with more than one channel -> (frames, F, H, W, C), what segment_frames takes: a
+    list of C sources (each an Octopus stem, a .npy or an ndarray of (F,H,W) frames; one length, shape and pixel type) or
+    one interleaved (F,H,W,C) .npy / ndarray.  A single (F,H,W) source is _open_frames' and gives C = None.  No pixel is
+    read here; ragged channels raise."""
+    from .frontend import open_channels
+    src = params.get('input')
+
+    def one(s):
+        if isinstance(s, str) and not s.endswith('.npy'):
+            from .dataio import OctopusData
+            return OctopusData(s, timeout=params.get('timeout', 60))
+        if isinstance(s, str):
+            return np.load(s, mmap_mode='r', allow_pickle=False)
+        return s if hasattr(s, 'shape') and hasattr(s, 'dtype') else np.asarray(s)
+
+    if isinstance(src, (list, tuple)):
+        frames = [one(s) for s in src]
+    else:
+        if isinstance(src, str) and not src.endswith('.npy'):   # one Octopus stream
+            return _open_frames(params) + (None,)
+        frames = one(src)                                       # a header or an attribute: no pixel
+        if frames.ndim == 3:
+            return _open_frames(params) + (None,)               # the single-channel path, as it was
+    _, (F, H, W), _, C = open_channels(frames)
+    return frames, int(F), int(H), int(W), int(C)
+
+
+def _parse_pipelines(params):
+    """params['pipeline'] through FrameClean.from_pipeline, before any input is opened: None, one (clean, normalise), or a
+    list of them with (None, True) -- ImageNorm alone, the default -- for a null entry.  A pipe the device does not run
+    raises here."""
+    from .frontend import FrameClean
+    pipeline = params.get('pipeline')
+    if pipeline is None:
+        return None
+    if isinstance(pipeline, (list, tuple)):
+        return [(None, True) if p is None else FrameClean.from_pipeline(p) for p in pipeline]
+    return FrameClean.from_pipeline(pipeline)
+
+
+def _channel_setup(params, C, parsed=None):
+    """What the frame jobs derive from params once the number of channels is known, before a pixel is read:
+    (clean, normalise, pipeline record or None, num_inputs or None).  params['pipeline'] (`parsed`: what _parse_pipelines
+    made of it, when the job has called it already) is one pipeline for every channel or, with C channels, a list of C with
+    null entries; the channels must agree on whether ImageNorm closes the chain.  params['num_inputs'] defaults to C and
+    must equal it."""
+    from .frontend import FrameClean
+    pipeline = params.get('pipeline')
+    if pipeline is not None and parsed is None:
+        parsed = _parse_pipelines(params)
+    if C is None:
+        clean, normalise = None, True
+        if pipeline is not None:
+            if isinstance(parsed, list):
+                raise ValueError("params['pipeline'] is a list of %d pipelines, the input has one channel" % len(parsed))
+            clean, normalise = parsed
+        return clean, normalise, None if pipeline is None else (clean or FrameClean()).pipes(normalise), None
+    if params.get('num_inputs') is not None and int(params['num_inputs']) != C:
+        raise ValueError("params['num_inputs'] is %d, the input has %d channels" % (int(params['num_inputs']), C))
+    if pipeline is None:
+        return None, True, None, C
+    if isinstance(parsed, list):
+        if len(parsed) != C:
+            raise ValueError("params['pipeline'] holds %d pipelines for %d channels" % (len(parsed), C))
+    else:
+        parsed = [parsed] * C
+    flags = set(n for _, n in parsed)
+    if len(flags) != 1:
+        raise ValueError("params['pipeline']: the channels must agree on ImageNorm (a null entry is ImageNorm alone); "
+                         "per-channel normalisation is not built")
+    normalise = flags.pop()
+    clean = [c for c, _ in parsed]
+    return clean, normalise, [(c or FrameClean()).pipes(normalise) for c in clean], C
+
+
 def SERVER_segment_frames(params, options):
     """Segment whole camera frames (larger than the network tile): params['input'] = an Octopus stream stem
     (sequitr/dataio/octopus.py), a .npy of (F,H,W) uint8/uint16/float32 frames, or an ndarray.  Raw frames
@@ -379,19 +455,31 @@ def SERVER_segment_frames(params, options):
     pipeline: the JSON ImagePipeline.save wrote (or an ImagePipeline).  It runs on the GPU per whole frame and may hold
     any subsequence of ImageOutliers, ImageBGSubtract, ImageNorm in that order (frontend.FrameClean.from_pipeline; anything
     else raises before a frame is read -- there is no host fallback); segment.json records it under 'pipeline'.  Without
-    it the frames are normalised with ImageNorm alone."""
+    it the frames are normalised with ImageNorm alone.
+
+    Multi-channel frames (bright field + fluorescence): params['input'] may be a list of C sources, each an Octopus stem, a
+    .npy or an ndarray of (F,H,W) frames of one length, shape and pixel type, or one interleaved (F,H,W,C) .npy / ndarray.
+    num_inputs defaults to C and must equal it; params['pipeline'] may then be a list of C pipelines with null entries (one
+    pipeline applies to every channel; each channel gets its own background fit); options['measure'] measures intensity in
+    channel params['measure_channel'] (default 0).  segment.json gains 'channels' and 'pipeline' is recorded per channel.
+    Ragged sources, a num_inputs other than C, a pipeline list of the wrong length or a measure_channel out of range raise
+    before a pixel is read.  With one (F,H,W) source every file is what it was."""
     import torch
     from .networks.unet import UNet2D
     from . import utils
-    from .frontend import FrameClean, segment_frames
+    from .frontend import segment_frames
 
     device = _resolve_device(params, options)
     out_dir = params['output']
-    clean, normalise = None, True
-    if params.get('pipeline') is not None:
-        clean, normalise = FrameClean.from_pipeline(params['pipeline'])
-    frames, F, H, W = _open_frames(params)
+    parsed = _parse_pipelines(params)                           # a pipe the device does not run: before the frames are opened
+    frames, F, H, W, C_in = _open_channels(params)
+    clean, normalise, pipe_record, num_inputs = _channel_setup(params, C_in, parsed)
+    measure_channel = int(params.get('measure_channel', 0))
+    if not 0 <= measure_channel < (C_in or 1):
+        raise ValueError("params['measure_channel'] is %d, the input has %d channel(s)" % (measure_channel, C_in or 1))
     net_p = _net_params(params, device)
+    if num_inputs is not None:
+        net_p['num_inputs'] = num_inputs
     net_p.setdefault('shape', (512, 512))
     tile = int(net_p['shape'][0])
     net = UNet2D(net_p, 'infer')
@@ -424,7 +512,8 @@ def SERVER_segment_frames(params, options):
 
     def measure_sink(first, raw, m):                           # objects against the raw frames, both still in HBM
         from .objects import measure_objects
-        t = measure_objects(m, image=raw, min_area=min_area, max_area=max_area, labels=label_stack is not None,
+        image = raw if raw.dim() == 3 else raw[measure_channel]   # (C, n, H, W) planes: the channel's slice as it lies
+        t = measure_objects(m, image=image, min_area=min_area, max_area=max_area, labels=label_stack is not None,
                             filtered_mask=bounded)
         masks[first:first + m.shape[0]] = (t.mask if bounded else m).cpu().numpy()
         if label_stack is not None:
@@ -446,8 +535,12 @@ def SERVER_segment_frames(params, options):
     np.save(os.path.join(out_dir, 'mask.npy'), masks)
     info = {'frames': int(F), 'shape': [int(H), int(W)], 'tile': tile, 'seconds': dt,
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
-    if params.get('pipeline') is not None:
-        info['pipeline'] = (clean or FrameClean()).pipes(normalise)
+    if C_in is not None:
+        info['channels'] = C_in
+        if want_measure:
+            info['measure_channel'] = measure_channel
+    if pipe_record is not None:
+        info['pipeline'] = pipe_record
     if want_measure:
         from .centroids import CentroidWriter
         from .objects import ObjectTable
@@ -588,19 +681,19 @@ def SERVER_evaluate(params, options):
     Writes ``confusion.npy``, int64 (F, C, C) with row = truth and column = prediction, and ``evaluate.json``: the total
     matrix ``confusion``, ``ignored``, ``scores`` (iou, dice, precision, recall and support per class, accuracy, mean_iou;
     a class absent from both sides scores null), ``per_frame`` with the same per frame, ``seconds``, ``mpixels_per_s``
-    and the ``pipeline`` record as segment.json has it.  ``mask.npy`` is written only with options['masks'].  The labels
+    and the ``pipeline`` record as segment.json has it (with a multi-channel input -- a list of C sources or an (F,H,W,C)
+    array, as SERVER_segment_frames takes it -- also ``channels``, and ``pipeline`` per channel).  ``mask.npy`` is written
+    only with options['masks'].  The labels
     follow the frames to the device batch by batch; a stack up to options['resident_label_gib'] (default 4) is uploaded
     once instead.  A label shape that does not match the frames raises before any frame is read."""
     if params.get('brick') is not None:
         return _evaluate_volume_bricks(params, options)
     labels = _load_labels(params.get('labels'))
-    frames, F, H, W = _open_frames(params)
+    frames, F, H, W, C_in = _open_channels(params)
     if tuple(labels.shape) != (F, H, W):
         raise ValueError('labels %s do not match the frames %s' % (tuple(labels.shape), (F, H, W)))
-    from .frontend import FrameClean, segment_frames
-    clean, normalise = None, True
-    if params.get('pipeline') is not None:
-        clean, normalise = FrameClean.from_pipeline(params['pipeline'])
+    from .frontend import segment_frames
+    clean, normalise, pipe_record, num_inputs = _channel_setup(params, C_in)
 
     import torch
     from . import ops
@@ -609,6 +702,8 @@ def SERVER_evaluate(params, options):
     torch.cuda.set_device(torch.device(device))
     out_dir = params['output']
     net_p = _net_params(params, device)
+    if num_inputs is not None:
+        net_p['num_inputs'] = num_inputs
     net_p.setdefault('shape', (512, 512))
     tile = int(net_p['shape'][0])
     net = UNet2D(net_p, 'infer')
@@ -636,8 +731,10 @@ def SERVER_evaluate(params, options):
         np.save(os.path.join(out_dir, 'mask.npy'), masks)
     info = {'frames': F, 'shape': [H, W], 'tile': tile, 'num_classes': C, 'seconds': dt,
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
-    if params.get('pipeline') is not None:
-        info['pipeline'] = (clean or FrameClean()).pipes(normalise)
+    if C_in is not None:
+        info['channels'] = C_in
+    if pipe_record is not None:
+        info['pipeline'] = pipe_record
     info.update(_evaluation_record(counts_h, ignored_h))
     with open(os.path.join(out_dir, 'evaluate.json'), 'w') as f:
         json.dump(info, f, indent=2)
@@ -728,7 +825,13 @@ class _Validator(object):
 def _train_frame_tiles(params, options):
     """SERVER_train with params['tile']: whole raw frames of any size, their class-index labels and weight maps stay in
     HBM, and every step's batch of rotated tiles is cut there by one kernel (frontend.tile_sample_plan, TileSampler) --
-    the reference's tr_augment (sequitr/networks/unet.py:348-401) in front of the captured step."""
+    the reference's tr_augment (sequitr/networks/unet.py:348-401) in front of the captured step.  params['images'] (and
+    val_images) may be an (F, H, W, C) .npy with C > 1 or a list of C (F, H, W) .npy: the frames are then uploaded plane by
+    plane into a resident (C, F, H, W) tensor, ImageNorm's statistics are taken once per channel and frame, the sampler
+    writes the step's (batch, th, tw, C) input, and net.config records num_inputs = C, so that the model loads into
+    SERVER_segment_frames with the same list of inputs.  params['num_inputs'] (default 1, as everywhere in SERVER_train)
+    must be given as C.  A channel count the trainer does not take (the bf16 graph: more
+    than 7) raises the trainer's own message before any upload."""
     world = int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
         raise RuntimeError("params['tile'] samples frames in a single process: WORLD_SIZE is %d (data-parallel frame "
@@ -738,13 +841,33 @@ def _train_frame_tiles(params, options):
     if len(tile) != 2:
         raise ValueError("params['tile'] must be (TH, TW), got %r" % (params['tile'],))
     th, tw = (int(s) for s in tile)
-    x = np.load(params['images'], mmap_mode='r', allow_pickle=False)
-    if x.ndim == 4 and x.shape[3] == 1:
-        x = x[..., 0]
-    if x.ndim != 3 or int(params.get('num_inputs', 1)) != 1:
-        raise ValueError("params['tile'] trains on single-channel (F, H, W) frame stacks only, got shape %s" % (x.shape,))
-    if np.dtype(x.dtype) not in NP_TORCH:
-        raise TypeError("with params['tile'] the images must be raw uint8, uint16 or float32 frames, got %s" % x.dtype)
+
+    def open_stack(src, key):
+        """(stack, planes): the frames as segment_frames takes them, and one (F, H, W) array per channel (views, no pixel
+        read).  src is an (F,H,W[,C]) .npy or a list of C (F,H,W) .npy"""
+        from .frontend import open_channels
+        if isinstance(src, (list, tuple)):
+            stack = [np.load(s, mmap_mode='r', allow_pickle=False) for s in src]
+        else:
+            stack = np.load(src, mmap_mode='r', allow_pickle=False)
+            if stack.ndim == 4 and stack.shape[3] == 1:
+                stack = stack[..., 0]
+            if stack.ndim not in (3, 4):
+                raise ValueError("params[%r] with params['tile'] are (F, H, W) or (F, H, W, C) frame stacks, got shape %s"
+                                 % (key, stack.shape))
+        _, _, dtype, C = open_channels(stack)
+        if dtype not in NP_TORCH:
+            raise TypeError("with params['tile'] params[%r] must be raw uint8, uint16 or float32 frames, got %s" % (key, dtype))
+        if C is None:
+            return stack, [stack]
+        return stack, list(stack) if isinstance(stack, list) else [stack[..., c] for c in range(C)]
+
+    _, x_planes = open_stack(params['images'], 'images')
+    x, CI = x_planes[0], len(x_planes)
+    n_in = int(params.get('num_inputs', 1))                    # SERVER_train's default, a single-channel model
+    if n_in != CI:
+        raise ValueError("params['num_inputs'] is %d, the images have %d channel(s)%s" % (n_in, CI, (
+            ': a single-channel model does not train on them, pass num_inputs = %d' % CI) if n_in == 1 else ''))
     F, H, W = (int(s) for s in x.shape)
     labels = np.load(params['labels'], mmap_mode='r', allow_pickle=False)
     if labels.ndim != 3:
@@ -763,15 +886,12 @@ def _train_frame_tiles(params, options):
         raise ValueError('samples_per_epoch must be positive, got %d' % samples)
     want_val, validate_every = _validation_keys(params)
     if want_val:                                               # whole raw frames and (F, H, W) labels, as the training pair
-        vx = np.load(params['val_images'], mmap_mode='r', allow_pickle=False)
-        if vx.ndim == 4 and vx.shape[3] == 1:
-            vx = vx[..., 0]
-        if vx.ndim != 3 or np.dtype(vx.dtype) not in NP_TORCH:
-            raise ValueError("with params['tile'] val_images are raw (F, H, W) uint8, uint16 or float32 frames, got %s %s"
-                             % (vx.dtype, vx.shape))
+        vx, v_planes = open_stack(params['val_images'], 'val_images')
+        if len(v_planes) != CI:
+            raise ValueError('val_images have %d channel(s), the images %d' % (len(v_planes), CI))
         vlab = _load_labels(params['val_labels'], 'val_labels')
-        if tuple(vlab.shape) != tuple(vx.shape):
-            raise ValueError('val_labels %s do not match val_images %s' % (vlab.shape, vx.shape))
+        if tuple(vlab.shape) != tuple(v_planes[0].shape):
+            raise ValueError('val_labels %s do not match val_images %s' % (vlab.shape, v_planes[0].shape))
         if th != tw:
             raise ValueError('validation segments whole frames with square tiles (frontend.segment_frames), got tile %r'
                              % (tile,))
@@ -784,7 +904,7 @@ def _train_frame_tiles(params, options):
 
     cfg_keys = ('name', 'num_outputs', 'num_epochs', 'learning_rate', 'warm_start', 'dropout')
     cfg = {k: params[k] for k in cfg_keys if k in params}
-    cfg['shape'], cfg['num_inputs'] = (th, tw), 1              # net.config records the tile: the shape the model segments at
+    cfg['shape'], cfg['num_inputs'] = (th, tw), CI             # net.config records the tile: the shape the model segments at
     config = utils.NetConfiguration.from_params(cfg)
     n_out = int(config.num_outputs)
     device = _resolve_device(params, options)
@@ -798,22 +918,30 @@ def _train_frame_tiles(params, options):
             t[i].copy_(torch.from_numpy(np.array(arr[i], dtype=np_dtype, order='C')))   # a copy: arr is a read-only memmap
         return t
 
-    x_dev = upload(x, x.dtype)
+    net_p = _net_params(params, device)
+    net_p['shape'] = (th, tw)
+    net_p['num_inputs'], net_p['num_outputs'] = CI, n_out
+    net_p['dropout'] = float(params.get('dropout', 0.4))
+    # before any upload: a trainer that does not take this many input channels says so itself
+    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'))
+
+    if CI == 1:
+        x_dev = upload(x, x.dtype)
+    else:                                                      # channel-major planes, resident: (C, F, H, W), plane by plane
+        x_dev = torch.empty((CI, F, H, W), dtype=NP_TORCH[np.dtype(x.dtype)], device=dev)
+        for c, plane in enumerate(x_planes):
+            for i in range(F):
+                x_dev[c, i].copy_(torch.from_numpy(np.array(plane[i], dtype=x.dtype, order='C')))
     y_dev = upload(labels, np.uint8)
     if params.get('weights'):
         w_dev = upload(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((F, H, W)), np.float32)
     else:
         # once, on the whole frames; the rotation then interpolates the map, as the reference rotates its precomputed TIFFs
         w_dev = device_weightmaps(y_dev, params.get('w0', 10.), params.get('sigma', 5.))
-    sampler = TileSampler((H, W), (th, tw), dev)
+    sampler = TileSampler((H, W), (th, tw), dev, channels=CI)
     normalise = bool(params.get('normalise', True))
     stats = sampler.stats(x_dev) if normalise else None         # ImageNorm of each WHOLE frame, as segment_frames applies it
 
-    net_p = _net_params(params, device)
-    net_p['shape'] = (th, tw)
-    net_p['num_inputs'], net_p['num_outputs'] = 1, n_out
-    net_p['dropout'] = float(params.get('dropout', 0.4))
-    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'))
     config.learning_rate = trainer.lr
     config.warmup_steps = trainer.warmup_steps
     if config.warm_start:
@@ -827,7 +955,7 @@ def _train_frame_tiles(params, options):
     epochs = int(params.get('num_epochs', config.num_epochs))
     max_steps = options.get('max_steps')
     total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
-    bufs = [torch.empty((batch, th, tw, 1), dtype=torch.float32, device=dev),
+    bufs = [torch.empty((batch, th, tw, CI), dtype=torch.float32, device=dev),
             torch.empty((batch, th, tw, n_out), dtype=torch.uint8, device=dev),
             torch.empty((batch, th, tw, 1), dtype=torch.float32, device=dev)]
     use_graph = bool(options.get('graph', True))
@@ -876,6 +1004,7 @@ def _train_frame_tiles(params, options):
     info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
             'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady - val_seconds) * 1e3 / steady if steady > 0 else None,
             'steady_steps': steady, 'batch_size': batch, 'frames': F, 'frame_shape': [H, W], 'tile': [th, tw],
+            **({'channels': CI} if CI > 1 else {}),
             'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed, 'normalise': normalise,
             'graph': use_graph, 'dtype': str(net_p.get('dtype', 'f32')), 'warmup_steps': trainer.warmup_steps,
             'learning_rate': trainer.lr, 'world': 1, 'device': device}
