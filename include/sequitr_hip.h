@@ -1202,6 +1202,73 @@ int64_t sq_confusion_chunk(int64_t items, int64_t n);
 int sq_confusion(const void *pred, int pred_kind, const uint8_t *truth, int truth_kind, int64_t *counts, int64_t *ignored,
                  int64_t items, int64_t n, int C, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask clean-up between "mask" and "objects": morphology, hole filling, border objects (sequitr_amd/maskops.py: morph,
+ * fill_holes, clear_border, MaskCleanup; the frame jobs' `postprocess` key).  The reference has no counterpart: its
+ * CentroidWriter (sequitr/utils.py:492-494) measures the raw argmax mask, and users ran scipy.ndimage on the host.  Planar
+ * masks only: mask and out are (N, H, W) uint8 class labels with C classes, fewer than 2^31 elements; volumes are refused.
+ * Every plane is Boolean, so every result is exact and the same bits on every run.
+ *
+ * Common definitions
+ *   P_c = (mask == c) for c = 1 .. C-1.  Byte 0 is background.  Bytes >= C belong to no class: they are never processed,
+ *   they are copied through unchanged and they are never overwritten; they count as "not background".
+ *   "An object" has the centroid path's connectivity (sq_ccl.h): 4 neighbours, same class > 0.
+ *   Every operation computes one processed plane Q_c per class from the INPUT mask, then merges:
+ *     extensive operations (dilate, close, fill_holes -- they can add pixels):
+ *         out = mask wherever mask > 0, elsewhere the smallest c whose Q_c is set, else 0.
+ *         A clean-up step never changes a pixel that already carries a class or an unknown byte.
+ *     anti-extensive operations (erode, open, clear_border -- they can only remove pixels):
+ *         out = c where Q_c is set and mask == c, else 0; bytes >= C stay.
+ *
+ * sq_mask_morph_u8 : op = SQ_MORPH_ERODE / DILATE / OPEN / CLOSE, structure = SQ_MORPH_CROSS
+ *   (scipy.ndimage.generate_binary_structure(2, 1)) or SQ_MORPH_SQUARE ((2, 2)), iterations r = 1 .. SQ_MORPH_MAX_ITER.
+ *     Q_c = scipy.ndimage.binary_{erosion,dilation,opening,closing}(P_c, structure, iterations=r)
+ *   with scipy's defaults (border_value = 0, origin 0): every one of the r (or r + r) elementary 3x3 steps sees zeros
+ *   outside the frame, so erosion eats in from the frame edge and closing loses pixels near it -- harmless under the
+ *   extensive merge rule for pixels that already carry a class.
+ *   One launch reads the mask once and writes out once, whatever r and C are.  A block of 256 threads owns a tile of
+ *   SQ_MORPH_TILE_ROWS x SQ_MORPH_TILE_COLS pixels, stages it with a halo of r (erode, dilate) or 2r (open, close) as bytes
+ *   in LDS, and then per class present in the staged region: one __ballot of (byte == c) per 64-pixel row segment makes the
+ *   row a 64-bit word, a 3x3 step is shifts with carry from the neighbouring words plus AND / OR with the rows above and
+ *   below, between two LDS copies of the bit plane; a block's result is exact on its tile because an error at the staged
+ *   region's rim travels one pixel per step and the halo is as wide as there are steps.  The classes are merged in
+ *   registers and the tile is stored.  SQ_MORPH_MAX_ITER = 16 makes the widest halo 32 pixels: the staged region is at most
+ *   (64 + 64) x (192 + 64) bytes = 32 KiB plus two bit planes of 4 KiB, 40 KiB of LDS per block.
+ *   out must not overlap mask (a block reads its neighbours' tiles): overlap returns SQ_EINVAL.  No workspace.
+ *
+ * sq_mask_fill_holes_u8 : a hole of class c is a 4-connected component of ~P_c that touches none of the frame's outer rows
+ *   and columns -- what scipy.ndimage.binary_fill_holes(P_c) fills.  Q_c = P_c plus the holes that qualify: all of them for
+ *   max_area <= 0, otherwise those whose area is at most max_area pixels, where the area counts ALL pixels of the component,
+ *   pixels of other classes and bytes >= C inside it included.  Extensive merge.  Per class: the complement plane is
+ *   written, labelled with sq_ccl.h's row scan / merge / compress, the roots that own a pixel of the outer rows or columns
+ *   are marked, the areas of the others are counted per root with integer atomics, and one pointwise pass writes c onto the
+ *   background pixels of the qualifying components that no smaller class has taken.  The results are unique.
+ *   workspace: sq_mask_fill_holes_workspace(N, H, W) bytes (-1: too large), 16-B aligned: 9 B per pixel.
+ *
+ * sq_mask_clear_border_u8 : removes every object that has a pixel in row 0, row H-1, column 0 or column W-1; the rest is
+ *   unchanged (anti-extensive merge; bytes >= C stay).  The centroid path's labelling on the mask itself plus a flag per
+ *   root.  workspace: sq_mask_clear_border_workspace(N, H, W) bytes (-1: too large), 16-B aligned: 8 B per pixel.
+ *
+ * All three return SQ_EINVAL with a message, before any launch, for null pointers, C < 2 or C > 256, a bad op, structure
+ * or iterations, N, H or W < 1, 2^31 or more elements, a workspace that is not 16-B aligned, and out overlapping mask.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_MORPH_ERODE 0
+#define SQ_MORPH_DILATE 1
+#define SQ_MORPH_OPEN 2
+#define SQ_MORPH_CLOSE 3
+#define SQ_MORPH_CROSS 0
+#define SQ_MORPH_SQUARE 1
+#define SQ_MORPH_MAX_ITER 16
+#define SQ_MORPH_TILE_ROWS 64
+#define SQ_MORPH_TILE_COLS 192
+int sq_mask_morph_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, int op, int structure, int iterations,
+                     void *stream);
+int64_t sq_mask_fill_holes_workspace(int N, int H, int W);
+int sq_mask_fill_holes_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, int64_t max_area, void *workspace,
+                          void *stream);
+int64_t sq_mask_clear_border_workspace(int N, int H, int W);
+int sq_mask_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

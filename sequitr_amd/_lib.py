@@ -96,6 +96,11 @@ SIGNATURES = {
     "sq_gan_sample_f32": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "sq_confusion_chunk": (c_int64, [c_int64, c_int64]),
     "sq_confusion": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "sq_mask_morph_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "sq_mask_fill_holes_workspace": (c_int64, [c_int, c_int, c_int]),
+    "sq_mask_fill_holes_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_int64, c_void_p, c_void_p]),
+    "sq_mask_clear_border_workspace": (c_int64, [c_int, c_int, c_int]),
+    "sq_mask_clear_border_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     "sq_dense_workspace_f32": (c_int64, [c_int, c_int, c_int]),
     "sq_dense_fwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "sq_convT_conv3x3_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

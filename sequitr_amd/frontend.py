@@ -639,7 +639,7 @@ def open_channels(frames):
 
 
 def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None,
-                   on_batch=None):
+                   on_batch=None, postprocess=None):
     """Segment a stack of raw frames (numpy array / memmap / OctopusData, (F,H,W) uint8|uint16|float32).
     Raw frames are staged through two pinned buffers and uploaded on a side stream while the previous batch is
     normalised, tiled, segmented (net.predict) and stitched; returns the (F,H,W) uint8 masks (host), or
@@ -653,9 +653,17 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     or an (F,H,W) array -- the Octopus layout, one stack per channel), or one interleaved (F,H,W,C) array, which is
     de-interleaved while it is copied into the pinned buffer.  Staging is then (C,B,H,W) channel-major planes, on_batch
     receives the raw (C,n,H,W) view, `clean` is one FrameClean for all channels or a sequence of C (None entries: no
-    cleaning), and net.n_inputs must equal C (checked before any upload).  The masks are (F,H,W) as ever."""
+    cleaning), and net.n_inputs must equal C (checked before any upload).  The masks are (F,H,W) as ever.
+
+    `postprocess` (a maskops.MaskCleanup, or the step list one is made of) cleans every batch's stitched masks in HBM with
+    net.n_outputs classes; its result takes the stitched batch's place before on_masks / on_batch and before the
+    double-buffered download.  A bad step list raises before a frame is read."""
     if on_masks is not None and on_batch is not None:
         raise ValueError('on_masks and on_batch are two forms of the same sink: pass one of them')
+    if postprocess is not None:
+        from .maskops import MaskCleanup
+        if not isinstance(postprocess, MaskCleanup):
+            postprocess = MaskCleanup(postprocess)
     gets, (F, H, W), np_dtype, C = open_channels(frames)
     if np_dtype not in NP_TORCH:
         raise TypeError('frames must be uint8, uint16 or float32, got %s' % np_dtype)
@@ -731,6 +739,8 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         if on_batch is None:
             freed[k].record(cur)                               # after the last kernel that reads staged[k]
         masks = tiler.stitch(net.predict(tiles))
+        if postprocess is not None:
+            masks = postprocess.apply(masks, int(net.n_outputs))
         if on_batch is not None:
             on_batch(b * B, take(staged[k], n), masks)
             freed[k].record(cur)                               # the callback's kernels read staged[k] too

@@ -294,6 +294,8 @@ def SERVER_segment_volume(params, options):
 
     ``segment_volume.json``: ``seconds`` / ``mvoxels_per_s`` cover the volumes (upload, network, download);
     ``setup_seconds`` is weights plus one warm-up volume."""
+    if params.get('postprocess') is not None:
+        raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope")
     import torch
     from .networks.unet import UNet3D
     from . import utils
@@ -405,6 +407,18 @@ def _parse_pipelines(params):
     return FrameClean.from_pipeline(pipeline)
 
 
+def _parse_postprocess(params):
+    """params['postprocess'] -- a list of mask clean-up steps, or the path of a JSON file that holds one -- as a
+    maskops.MaskCleanup, before any input is opened; None without the key.  A bad step list raises here."""
+    spec = params.get('postprocess')
+    if spec is None:
+        return None
+    from .maskops import MaskCleanup, load_steps
+    if params.get('brick') is not None:
+        raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes (params['brick']) are out of scope")
+    return MaskCleanup(load_steps(spec))
+
+
 def _channel_setup(params, C, parsed=None):
     """What the frame jobs derive from params once the number of channels is known, before a pixel is read:
     (clean, normalise, pipeline record or None, num_inputs or None).  params['pipeline'] (`parsed`: what _parse_pipelines
@@ -463,7 +477,13 @@ def SERVER_segment_frames(params, options):
     pipeline applies to every channel; each channel gets its own background fit); options['measure'] measures intensity in
     channel params['measure_channel'] (default 0).  segment.json gains 'channels' and 'pipeline' is recorded per channel.
     Ragged sources, a num_inputs other than C, a pipeline list of the wrong length or a measure_channel out of range raise
-    before a pixel is read.  With one (F,H,W) source every file is what it was."""
+    before a pixel is read.  With one (F,H,W) source every file is what it was.
+
+    params['postprocess'] (a list of mask clean-up steps, or the path of a JSON file holding one; maskops.MaskCleanup) runs
+    on each batch's stitched masks in HBM before any sink sees them: ``mask.npy``, the centroid file, ``objects.npz``,
+    ``labels.npy`` and the min_area / max_area filter all describe the cleaned mask, and segment.json records the steps
+    under 'postprocess'.  A bad step list raises before a frame is read; without the key nothing changes."""
+    postprocess = _parse_postprocess(params)                    # before anything is opened
     import torch
     from .networks.unet import UNet2D
     from . import utils
@@ -527,7 +547,8 @@ def SERVER_segment_frames(params, options):
     out = segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)),
                          frames_per_batch=int(params.get('frames_per_batch', 4)),
                          on_masks=sink if want_centroids and not want_measure else None,
-                         on_batch=measure_sink if want_measure else None, normalise=normalise, clean=clean)
+                         on_batch=measure_sink if want_measure else None, normalise=normalise, clean=clean,
+                         postprocess=postprocess)
     if not want_centroids:
         masks = out
     torch.cuda.synchronize()
@@ -541,6 +562,8 @@ def SERVER_segment_frames(params, options):
             info['measure_channel'] = measure_channel
     if pipe_record is not None:
         info['pipeline'] = pipe_record
+    if postprocess is not None:
+        info['postprocess'] = postprocess.record()
     if want_measure:
         from .centroids import CentroidWriter
         from .objects import ObjectTable
@@ -685,7 +708,12 @@ def SERVER_evaluate(params, options):
     array, as SERVER_segment_frames takes it -- also ``channels``, and ``pipeline`` per channel).  ``mask.npy`` is written
     only with options['masks'].  The labels
     follow the frames to the device batch by batch; a stack up to options['resident_label_gib'] (default 4) is uploaded
-    once instead.  A label shape that does not match the frames raises before any frame is read."""
+    once instead.  A label shape that does not match the frames raises before any frame is read.
+
+    params['postprocess'] (as SERVER_segment_frames takes it) cleans each batch's masks in HBM first: ``confusion.npy``, the
+    scores and ``mask.npy`` describe the cleaned masks and evaluate.json records the steps under 'postprocess'.  It covers
+    frames only: together with params['brick'] it is refused."""
+    postprocess = _parse_postprocess(params)                    # before anything is opened
     if params.get('brick') is not None:
         return _evaluate_volume_bricks(params, options)
     labels = _load_labels(params.get('labels'))
@@ -723,7 +751,7 @@ def SERVER_evaluate(params, options):
 
     t0 = time.time()
     segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)), frames_per_batch=B, on_masks=sink,
-                   normalise=normalise, clean=clean)
+                   normalise=normalise, clean=clean, postprocess=postprocess)
     counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
@@ -735,6 +763,8 @@ def SERVER_evaluate(params, options):
         info['channels'] = C_in
     if pipe_record is not None:
         info['pipeline'] = pipe_record
+    if postprocess is not None:
+        info['postprocess'] = postprocess.record()
     info.update(_evaluation_record(counts_h, ignored_h))
     with open(os.path.join(out_dir, 'evaluate.json'), 'w') as f:
         json.dump(info, f, indent=2)
