@@ -151,7 +151,8 @@ int sq_maxpool2x2_bwd_f32(const float *x, const float *dy, float *dx, int N, int
 int sq_broadcast2x2_f32(const float *src, float *dst, int N, int H, int W, int C, float scale, void *stream);
 int sq_sumpool2x2_f32(const float *x, float *y, int N, int H, int W, int C, float scale, void *stream);
 
-/* bridge backward: (da, db) from dY and the forward operands a (up-scaled) and b (skip). */
+/* bridge backward: (da, db) from dY and the forward operands a (up-scaled) and b (skip).  n % 4 == 0; dy, da, db 16-byte
+ * aligned.  a, b are read by eltwise_mul only (may be NULL otherwise) and must then be 16-byte aligned too. */
 int sq_bridge_bwd_f32(const float *dy, const float *a, const float *b, float *da, float *db, int64_t n,
                       int bridge, void *stream);
 
@@ -166,7 +167,7 @@ int sq_conv1x1_small_bwd_f32(const float *x, const float *w, const float *dz, fl
 /* tf.layers.dropout (sequitr/networks/unet.py:274-276): y = x * keep / (1 - rate).  mask (u8, n) is
  * written from a counter-based hash of (seed, index), or read when mask_given != 0.  step_dev (may be
  * NULL): device int32 whose value is folded into the seed, so a captured hipGraph draws a new mask on
- * every replay. */
+ * every replay.  n % 4 == 0, rate in [0,1); x, y, dy, dx 16-byte aligned, mask 4-byte aligned (four bytes per access). */
 int sq_dropout_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t n, float rate, uint32_t seed,
                        int mask_given, const int32_t *step_dev, void *stream);
 int sq_dropout_bwd_f32(const float *dy, const uint8_t *mask, float *dx, int64_t n, float rate, void *stream);

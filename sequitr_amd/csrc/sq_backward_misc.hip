@@ -447,6 +447,7 @@ extern "C" int sq_bridge_bwd_f32(const float *dy, const float *a, const float *b
     SQ_REQUIRE(bridge >= SQ_BRIDGE_ADD && bridge <= SQ_BRIDGE_SUB, "sq_bridge_bwd_f32: bad bridge %d", bridge);
     SQ_REQUIRE(bridge != SQ_BRIDGE_MUL || (a && b), "sq_bridge_bwd_f32: eltwise_mul needs both forward operands");
     SQ_REQUIRE_ALIGNED(dy); SQ_REQUIRE_ALIGNED(da); SQ_REQUIRE_ALIGNED(db);
+    if (bridge == SQ_BRIDGE_MUL) { SQ_REQUIRE_ALIGNED(a); SQ_REQUIRE_ALIGNED(b); }    // read as float4 by that branch only
     hipLaunchKernelGGL(bridge_bwd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, SQ_ST(stream),
                        reinterpret_cast<const float4 *>(dy), reinterpret_cast<const float4 *>(a),
                        reinterpret_cast<const float4 *>(b), reinterpret_cast<float4 *>(da),
@@ -528,6 +529,7 @@ extern "C" int sq_dropout_fwd_f32(const float *x, float *y, uint8_t *mask, int64
     SQ_REQUIRE(x && y && mask && n > 0 && n % 4 == 0, "sq_dropout_fwd_f32: bad arguments (n %% 4 == 0)");
     SQ_REQUIRE(rate >= 0.f && rate < 1.f, "sq_dropout_fwd_f32: rate must be in [0,1)");
     SQ_REQUIRE_ALIGNED(x); SQ_REQUIRE_ALIGNED(y);
+    SQ_REQUIRE((((uintptr_t)mask) & 3u) == 0, "sq_dropout_fwd_f32: mask must be 4-byte aligned (read and written as uchar4)");
     hipLaunchKernelGGL(dropout_fwd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, SQ_ST(stream),
                        reinterpret_cast<const float4 *>(x), reinterpret_cast<float4 *>(y),
                        reinterpret_cast<uchar4 *>(mask), n / 4, rate, seed, mask_given, step_dev);
@@ -538,6 +540,7 @@ extern "C" int sq_dropout_bwd_f32(const float *dy, const uint8_t *mask, float *d
     SQ_REQUIRE(dy && mask && dx && n > 0 && n % 4 == 0, "sq_dropout_bwd_f32: bad arguments (n %% 4 == 0)");
     SQ_REQUIRE(rate >= 0.f && rate < 1.f, "sq_dropout_bwd_f32: rate must be in [0,1)");
     SQ_REQUIRE_ALIGNED(dy); SQ_REQUIRE_ALIGNED(dx);
+    SQ_REQUIRE((((uintptr_t)mask) & 3u) == 0, "sq_dropout_bwd_f32: mask must be 4-byte aligned (read as uchar4)");
     hipLaunchKernelGGL(dropout_bwd_kernel, dim3(grid_for(n / 4)), dim3(256), 0, SQ_ST(stream),
                        reinterpret_cast<const float4 *>(dy), reinterpret_cast<const uchar4 *>(mask),
                        reinterpret_cast<float4 *>(dx), n / 4, rate);

@@ -108,11 +108,15 @@ __device__ __forceinline__ float sq_wce_pixel(const float (&zc)[MAXC], const flo
 #pragma unroll
     for (int c = 0; c < MAXC; ++c)
         if (c < C) s += expf(zc[c] - m);
-    const float lse = m + logf(s);
+    const float ls = logf(s);
+    const float lse = m + ls;
     if (dz) {
+        // softmax = exp((z - m) - log s), not exp(z - lse): lse is rounded at the size of the logits (half an ulp at 80 is
+        // 3.8e-6, which exp would carry into the softmax as a relative error), while t = (z - m) - log s is <= 0 and rounded
+        // relative to itself: the softmax is off by at most about 2 u |t| exp(t) < u
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
-            if (c < C) dz[c] = g * (expf(zc[c] - lse) * yt - yc[c]);
+            if (c < C) dz[c] = g * (expf((zc[c] - m) - ls) * yt - yc[c]);
     }
     return wp * (lse * yt - dot);
 }

@@ -782,6 +782,8 @@ def act_bwd(dy, y, act):
 def maxpool2x2_bwd(x, dy):
     _chk(x, "x", ndim=4), _chk(dy, "dy", ndim=4)
     N, H, W, C = x.shape
+    if tuple(dy.shape) != (N, H // 2, W // 2, C):
+        raise ValueError("dy %s does not match the pooled %s" % (tuple(dy.shape), (N, H // 2, W // 2, C)))
     dx = torch.empty_like(x)
     lib = _lib.load()
     _lib.check(lib.sq_maxpool2x2_bwd_f32(_ptr(x), _ptr(dy), _ptr(dx), N, H, W, C, _stream()), "sq_maxpool2x2_bwd_f32")
@@ -829,6 +831,9 @@ def sumpool2x2(x, scale=1.0):
 
 def bridge_bwd(dy, a, b, kind):
     _chk(dy, "dy")
+    for t, n in ((a, "a"), (b, "b")):                           # None: not needed by eltwise_add / eltwise_sub
+        if t is not None and _chk(t, n).numel() != dy.numel():
+            raise ValueError("bridge_bwd: %s has %d elements, dy %d" % (n, t.numel(), dy.numel()))
     da, db = torch.empty_like(dy), torch.empty_like(dy)
     lib = _lib.load()
     _lib.check(lib.sq_bridge_bwd_f32(_ptr(dy), _ptr(a), _ptr(b), _ptr(da), _ptr(db), dy.numel(), BRIDGE[kind],
@@ -840,6 +845,8 @@ def space_to_depth2(dy):
     """(N,2H,2W,C) -> (N,H,W,4C), channel index (2a+b)*C + c."""
     _chk(dy, "dy", ndim=4)
     N, H2, W2, C = dy.shape
+    if H2 % 2 or W2 % 2:
+        raise ValueError("space_to_depth2: dy %s needs even H and W" % (tuple(dy.shape),))
     g = torch.empty((N, H2 // 2, W2 // 2, 4 * C), dtype=torch.float32, device=dy.device)
     lib = _lib.load()
     _lib.check(lib.sq_space_to_depth2_f32(_ptr(dy), _ptr(g), N, H2 // 2, W2 // 2, C, _stream()),
@@ -933,7 +940,11 @@ def conv1x1_small_bwd(x, w, dz, want_dx=True, dw_out=None, db_out=None):
     """Backward of the to_image head: returns (dx or None, dw (1,1,Cin,Cout), db (Cout))."""
     _chk(x, "x", ndim=4), _chk(w, "w", ndim=4), _chk(dz, "dz", ndim=4)
     N, H, W, Cin = x.shape
+    if tuple(w.shape[:3]) != (1, 1, Cin):
+        raise ValueError("1x1 weight must be (1,1,%d,Cout), got %s" % (Cin, tuple(w.shape)))
     Cout = w.shape[3]
+    if tuple(dz.shape) != (N, H, W, Cout):
+        raise ValueError("dz %s does not match %s" % (tuple(dz.shape), (N, H, W, Cout)))
     npix = N * H * W
     lib = _lib.load()
     ws = _workspace(lib.sq_conv1x1_small_bwd_workspace_f32(npix, Cin, Cout), x.device)
@@ -951,7 +962,8 @@ def dropout_fwd(x, rate, seed=0, mask=None, step_dev=None):
     y = torch.empty_like(x)
     given = mask is not None
     if given:
-        _chk(mask, "mask", dtype=torch.uint8)
+        if _chk(mask, "mask", dtype=torch.uint8).numel() != x.numel():
+            raise ValueError("dropout_fwd: mask has %d elements, x %d" % (mask.numel(), x.numel()))
     else:
         mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     lib = _lib.load()
@@ -962,6 +974,8 @@ def dropout_fwd(x, rate, seed=0, mask=None, step_dev=None):
 
 def dropout_bwd(dy, mask, rate):
     _chk(dy, "dy"), _chk(mask, "mask", dtype=torch.uint8)
+    if mask.numel() != dy.numel():
+        raise ValueError("dropout_bwd: mask has %d elements, dy %d" % (mask.numel(), dy.numel()))
     dx = torch.empty_like(dy)
     lib = _lib.load()
     _lib.check(lib.sq_dropout_bwd_f32(_ptr(dy), _ptr(mask), _ptr(dx), dy.numel(), float(rate), _stream()),
@@ -1371,6 +1385,8 @@ def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, state, grad_scale=1.0):
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, n)
     _chk(state, "state", dtype=torch.int32)
+    if not (p.numel() == g.numel() == m.numel() == v.numel()):
+        raise ValueError("adam_step_dev: buffers differ in size")
     lib = _lib.load()
     _lib.check(lib.sq_adam_step_dev_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1),
                                        float(beta2), float(eps), _ptr(state), float(grad_scale), _stream()),
@@ -1397,6 +1413,8 @@ def adam_apply_dev(p, g, m, v, beta1, beta2, eps, state, grad_scale=1.0):
     for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, n)
     _chk(state, "state", dtype=torch.int32)
+    if not (p.numel() == g.numel() == m.numel() == v.numel()):
+        raise ValueError("adam_apply_dev: buffers differ in size")
     _lib.check(_lib.load().sq_adam_apply_dev_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(beta1), float(beta2),
                                                 float(eps), _ptr(state), float(grad_scale), _stream()),
                "sq_adam_apply_dev_f32")
@@ -1440,6 +1458,13 @@ def _bn_shape(x):
     return x.numel() // C, C
 
 
+def _bn_vectors(C, **vectors):
+    """every per-channel vector is float32, contiguous and holds C values"""
+    for n, t in vectors.items():
+        if _chk(t, n).numel() != C:
+            raise ValueError("%s has %d values for %d channels" % (n, t.numel(), C))
+
+
 def bn_stats(x):
     """(mean, population variance) per channel over every leading axis of the NHWC tensor x."""
     npix, C = _bn_shape(x)
@@ -1467,7 +1492,7 @@ def bn_fold(gamma, beta, mean, var, eps=BN_EPS):
 
 def bn_apply(x, scale, shift, act=None):
     npix, C = _bn_shape(x)
-    _chk(scale, "scale"), _chk(shift, "shift")
+    _bn_vectors(C, scale=scale, shift=shift)
     y = torch.empty_like(x)
     lib = _lib.load()
     _lib.check(lib.sq_bn_apply_f32(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), npix, C, ACT[act], _stream()),
@@ -1492,8 +1517,16 @@ def bn_bwd(x, dy, y, act, mean, var, gamma, eps=BN_EPS):
     """(dx, dgamma, dbeta) of y = act(BN_batchstats(x)); y is needed only when act is not None."""
     npix, C = _bn_shape(x)
     _chk(dy, "dy")
+    _bn_vectors(C, mean=mean, var=var, gamma=gamma)
+    if dy.shape != x.shape:
+        raise ValueError("bn_bwd: dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
+    if ACT[act] and _chk(y, "y").shape != x.shape:
+        raise ValueError("bn_bwd: y %s does not match x %s" % (tuple(y.shape), tuple(x.shape)))
     lib = _lib.load()
-    ws = _workspace(lib.sq_bn_workspace_f32(npix, C), x.device)
+    nbytes = lib.sq_bn_workspace_f32(npix, C)
+    if nbytes < 0:
+        raise _lib.SequitrHipError("bn_bwd: unsupported channel count %d" % C)
+    ws = _workspace(nbytes, x.device)
     dx = torch.empty_like(x)
     dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
     _lib.check(lib.sq_bn_bwd_f32(_ptr(x), _ptr(dy), _ptr(y) if ACT[act] else None, ACT[act], _ptr(mean), _ptr(var),
@@ -1517,6 +1550,8 @@ def zero_insert2x(x):
 def gather_odd2x(du):
     _chk(du, "du", ndim=4)
     N, H2, W2, C = du.shape
+    if H2 % 2 or W2 % 2:
+        raise ValueError("gather_odd2x: du %s needs even H and W" % (tuple(du.shape),))
     dx = torch.empty((N, H2 // 2, W2 // 2, C), dtype=torch.float32, device=du.device)
     lib = _lib.load()
     _lib.check(lib.sq_gather_odd2x_f32(_ptr(du), _ptr(dx), N, H2 // 2, W2 // 2, C, _stream()), "sq_gather_odd2x_f32")
