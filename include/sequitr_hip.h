@@ -1270,6 +1270,71 @@ int sq_mask_fill_holes_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W
 int64_t sq_mask_clear_border_workspace(int N, int H, int W);
 int sq_mask_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask clean-up: splitting (sequitr_amd/maskops.py: split, the `split` step of MaskCleanup and of the frame jobs'
+ * `postprocess` key).  Everything downstream of the mask calls a 4-connected component of one class "an object", so two
+ * cells that touch are one object with one centroid.  sq_mask_split_u8 cuts a one-pixel line of background between the
+ * parts of an object; the mask format does not change, so every consumer that runs after it sees separate objects.
+ * Planar (N, H, W) uint8 masks with C classes, fewer than 2^31 elements; volumes are refused.  P_c, bytes >= C and "an
+ * object" are those of "Mask clean-up" above: bytes >= C belong to no class, are copied through, are never written and
+ * never propagate a label.  Only integer and Boolean arithmetic: the same bits on every run.
+ *
+ * Definition.  erosions r = 1 .. SQ_MORPH_MAX_ITER, structure = SQ_MORPH_CROSS or SQ_MORPH_SQUARE, reach T = 1 ..
+ * SQ_SPLIT_MAX_REACH (the Python binding's default, None, means 2 r).  Per class c = 1 .. C-1:
+ *   1. Seeds.   S_c = scipy.ndimage.binary_erosion(P_c, structure, iterations=r) with scipy's defaults (border_value 0: the
+ *               seeds shrink away from the frame edge exactly as sq_mask_morph_u8's erode does).
+ *   2. Labels.  The 4-connected components of S_c are numbered in the raster order of their first pixel
+ *               (scipy.ndimage.label's order, the root order of sq_ccl.h).  L_0 = that number on seed pixels, 0 ("none")
+ *               elsewhere.  Labels of different classes are never compared.
+ *   3. Regrowth.  T synchronous steps.  For every pixel p with mask(p) = c and L_{t-1}(p) = 0:
+ *               L_t(p) = the smallest non-zero L_{t-1}(q) over the 4 neighbours q inside the frame with mask(q) = c,
+ *               or 0 when there is none.  Every other pixel keeps its label.  All reads of step t see step t-1 (Jacobi,
+ *               never in place): which label a pixel takes depends on the step at which the labels arrive, not only on
+ *               their order, so this is part of the definition.
+ *   4. Cut.     out(p) = 0 iff L_T(p) > 0 and some 4-neighbour q inside the frame with mask(q) = mask(p) has
+ *               0 < L_T(q) < L_T(p); otherwise out(p) = mask(p).  Anti-extensive: out is mask or 0 everywhere.
+ * Consequences (tests/test_mask_split_cpu.py asserts them on the restatement, tests/mask_split_cases.py):
+ *   - two surviving pixels with different non-zero labels are never 4-adjacent;
+ *   - a component without a seed is unchanged, and a mask with at most one seed per component comes back unchanged;
+ *   - pixels that T steps do not reach keep their class and may still bridge two parts: the price of a bounded T.
+ * Deliberately not built: growth until nothing changes (it would need a device-to-host readback inside the frame stream and
+ * could not be captured in a graph), and seeds from the Euclidean distance transform or its h-maxima.  Known limit: objects
+ * whose eroded cores stay connected (three mutually overlapping disks) are not split.
+ *
+ * Kernels (sq_mask_split.hip).  A fixed chain of launches on `stream`, no host readback, no block waits on another, no
+ * flag is polled: the call can be captured in a graph.
+ *   seeds    : one sq_mask_morph_u8 erosion launch, all classes, into a 1 B / pixel plane of the workspace.
+ *   labels   : sq_ccl.h's row scan / merge / compress on the seed plane; a label is the root's linear index + 1 (the batch
+ *              is one index space, frames are never linked).  The first regrowth launch turns roots into labels as it reads.
+ *   regrowth : a block of 256 threads owns a tile of SQ_SPLIT_TILE_ROWS x SQ_SPLIT_TILE_COLS pixels and stages the class
+ *              bytes and the int32 labels of the tile and a halo of as many pixels as the launch runs steps, at most
+ *              SQ_SPLIT_STEPS, in LDS; beyond the halo and the frame there is nothing (class 0, label 0).  Every thread
+ *              owns 25 staged cells; per step it computes their new labels from LDS into registers -- the second copy a
+ *              synchronous step needs -- and writes them after a barrier.  A step that changes nothing in the staged region
+ *              ends the block's loop (so does every later one), which is also how a block with nothing to grow copies
+ *              through.  The tile's labels go to the other global label plane; ceil(T / SQ_SPLIT_STEPS) launches
+ *              ping-pong between the two planes, the last one runs the remainder.  The tile is exact because what is
+ *              missing beyond the staged rim travels one pixel per step.  (64 + 16) x (64 + 16) cells x 5 B = 32 000 B of
+ *              static LDS (32 256 allocated), 102 VGPRs, no spills: 4 blocks = 16 waves per CU (tools/resource_report.py:
+ *              4 waves per SIMD).
+ *   cut      : one pointwise pass, labels + mask -> out.
+ *   SQ_SPLIT_LDS=0 (environment, read per call) runs the regrowth as one synchronous step per launch on the global planes:
+ *   trivially the definition, the in-tree cross-check and the baseline of tools/mask_split_bench.py.  Same bits.
+ *
+ * workspace: sq_mask_split_workspace(N, H, W) = 9 N H W rounded up to 16 bytes (-1: N, H or W < 1, or 2^31 or more
+ * elements): two int32 label planes and the seed plane; 16-B aligned, overlapping neither mask nor out.
+ * sq_mask_split_u8 returns SQ_EINVAL with a message, before any launch, for null pointers, C < 2 or C > 256, a bad
+ * structure, erosions outside 1 .. 16, reach outside 1 .. 64, N, H or W < 1, 2^31 or more elements, a workspace that is not
+ * 16-B aligned or overlaps mask or out, and out overlapping mask.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_SPLIT_MAX_REACH 64
+#define SQ_SPLIT_TILE_ROWS 64
+#define SQ_SPLIT_TILE_COLS 64
+#define SQ_SPLIT_STEPS 8
+int64_t sq_mask_split_workspace(int N, int H, int W);
+int sq_mask_split_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, int erosions, int structure, int reach,
+                     void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -657,7 +657,8 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
 
     `postprocess` (a maskops.MaskCleanup, or the step list one is made of) cleans every batch's stitched masks in HBM with
     net.n_outputs classes; its result takes the stitched batch's place before on_masks / on_batch and before the
-    double-buffered download.  A bad step list raises before a frame is read."""
+    double-buffered download.  A bad step list raises before a frame is read.  The steps are maskops.MaskCleanup's:
+    morphology, fill_holes, split (touching objects cut apart), clear_border."""
     if on_masks is not None and on_batch is not None:
         raise ValueError('on_masks and on_batch are two forms of the same sink: pass one of them')
     if postprocess is not None:

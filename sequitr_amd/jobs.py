@@ -482,7 +482,9 @@ def SERVER_segment_frames(params, options):
     params['postprocess'] (a list of mask clean-up steps, or the path of a JSON file holding one; maskops.MaskCleanup) runs
     on each batch's stitched masks in HBM before any sink sees them: ``mask.npy``, the centroid file, ``objects.npz``,
     ``labels.npy`` and the min_area / max_area filter all describe the cleaned mask, and segment.json records the steps
-    under 'postprocess'.  A bad step list raises before a frame is read; without the key nothing changes."""
+    under 'postprocess'.  A bad step list raises before a frame is read; without the key nothing changes.  A step
+    {"op": "split", "erosions": r, "structure": ..., "reach": ...} (maskops.split) cuts touching cells apart, so the
+    centroid file and ``objects.npz`` get one row per cell instead of one per clump."""
     postprocess = _parse_postprocess(params)                    # before anything is opened
     import torch
     from .networks.unet import UNet2D
@@ -710,7 +712,7 @@ def SERVER_evaluate(params, options):
     follow the frames to the device batch by batch; a stack up to options['resident_label_gib'] (default 4) is uploaded
     once instead.  A label shape that does not match the frames raises before any frame is read.
 
-    params['postprocess'] (as SERVER_segment_frames takes it) cleans each batch's masks in HBM first: ``confusion.npy``, the
+    params['postprocess'] (as SERVER_segment_frames takes it, the ``split`` step included) cleans each batch's masks in HBM first: ``confusion.npy``, the
     scores and ``mask.npy`` describe the cleaned masks and evaluate.json records the steps under 'postprocess'.  It covers
     frames only: together with params['brick'] it is refused."""
     postprocess = _parse_postprocess(params)                    # before anything is opened

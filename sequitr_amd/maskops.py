@@ -2,11 +2,19 @@
 filling, removal of objects cut by the frame edge.  The reference has no counterpart -- its CentroidWriter
 (sequitr/utils.py:492-494) measures the raw argmax mask and users ran scipy.ndimage on a downloaded mask.npy.
 
-``morph``, ``fill_holes`` and ``clear_border`` are one C-ABI call each (sq_mask_morph_u8, sq_mask_fill_holes_u8,
-sq_mask_clear_border_u8; include/sequitr_hip.h, "Mask clean-up", is the contract: classes, merge rules, scipy's
-definitions).  ``MaskCleanup`` is a validated list of such steps that runs on a batch of device masks between two cached
+``morph``, ``fill_holes``, ``clear_border`` and ``split`` are one C-ABI call each (sq_mask_morph_u8,
+sq_mask_fill_holes_u8, sq_mask_clear_border_u8, sq_mask_split_u8; include/sequitr_hip.h, "Mask clean-up" and "Mask
+clean-up: splitting", is the contract: classes, merge rules, scipy's definitions).  ``MaskCleanup`` is a validated list of such steps that runs on a batch of device masks between two cached
 buffers; the frame jobs take one as ``params['postprocess']``.  Planar (N, H, W) uint8 masks only; there is no CPU path.
-Every result equals the scipy restatement in tests/mask_cleanup_cases.py exactly (tests/test_gpu_mask_cleanup.py).
+Every result equals the scipy restatement in tests/mask_cleanup_cases.py and tests/mask_split_cases.py exactly
+(tests/test_gpu_mask_cleanup.py, tests/test_gpu_mask_split.py).
+
+``split`` separates touching objects: seeds are the components of the eroded class planes, they grow back through
+their class for a bounded number of synchronous steps, and a one-pixel line of background is cut where two different
+seeds' growths meet.  Deliberately not built: growth until nothing changes (it would need a device-to-host readback
+inside the frame stream and could not be captured in a graph; pixels beyond ``reach`` keep their class and may still
+bridge two parts), and seeds from the Euclidean distance transform or its h-maxima (the seeds are plain erosions).
+Objects whose eroded cores stay connected -- three mutually overlapping disks, say -- are not split.
 """
 import json
 
@@ -18,10 +26,14 @@ MORPH_TILE = (64, 192)                                          # SQ_MORPH_TILE_
 MORPH_MAX_ITER = 16                                             # SQ_MORPH_MAX_ITER
 MORPH_OPS = {'erode': 0, 'dilate': 1, 'open': 2, 'close': 3}    # SQ_MORPH_*
 STRUCTURES = {'cross': 0, 'square': 1}                          # generate_binary_structure(2, 1) / (2, 2)
+SPLIT_MAX_REACH = 64                                            # SQ_SPLIT_MAX_REACH
+SPLIT_TILE = (64, 64)                                           # SQ_SPLIT_TILE_ROWS, SQ_SPLIT_TILE_COLS
+SPLIT_STEPS = 8                                                 # SQ_SPLIT_STEPS: synchronous steps per launch = halo
 
 # op -> the keys a step may carry besides 'op', with their defaults
 _STEP_KEYS = dict({op: {'iterations': 1, 'structure': 'cross'} for op in MORPH_OPS},
-                  fill_holes={'max_area': None}, clear_border={})
+                  fill_holes={'max_area': None}, clear_border={},
+                  split={'erosions': None, 'structure': 'cross', 'reach': None})
 
 
 def _check_mask(mask, classes):
@@ -119,6 +131,30 @@ def clear_border(mask, classes=None, out=None, workspace=None):
     return out
 
 
+def split(mask, erosions, structure='cross', reach=None, classes=None, out=None, workspace=None):
+    """Cut a one-pixel line of background between the parts of an object (include/sequitr_hip.h, "Mask clean-up:
+    splitting").  Seeds are the 4-connected components of every class plane eroded `erosions` = 1 .. MORPH_MAX_ITER times
+    with `structure`; they grow back through their class for `reach` = 1 .. SPLIT_MAX_REACH synchronous steps (None:
+    2 * erosions), the smallest label winning where several arrive together, and a labelled pixel with a same-class
+    neighbour of a smaller label becomes background.  Everything else is unchanged; bytes >= classes pass through."""
+    if structure not in STRUCTURES:
+        raise ValueError("structure must be one of %s, got %r" % (sorted(STRUCTURES), structure))
+    erosions = int(erosions)
+    if not 1 <= erosions <= MORPH_MAX_ITER:
+        raise ValueError("erosions must be 1 .. %d, got %d" % (MORPH_MAX_ITER, erosions))
+    reach = 2 * erosions if reach is None else int(reach)
+    if not 1 <= reach <= SPLIT_MAX_REACH:
+        raise ValueError("reach must be 1 .. %d, got %d" % (SPLIT_MAX_REACH, reach))
+    classes = _check_mask(mask, classes)
+    out = _check_out(out, mask)
+    lib = _lib.load()
+    ws = _workspace(lib.sq_mask_split_workspace, mask, workspace)
+    N, H, W = _dims(mask)
+    _lib.check(lib.sq_mask_split_u8(mask.data_ptr(), out.data_ptr(), N, H, W, classes, erosions, STRUCTURES[structure], reach,
+                                    ws.data_ptr(), _stream(mask)), "sq_mask_split_u8")
+    return out
+
+
 def load_steps(spec):
     """a step list as the jobs take it: the list itself, or the path of a JSON file that holds one"""
     if isinstance(spec, str):
@@ -129,7 +165,7 @@ def load_steps(spec):
 
 class MaskCleanup(object):
     """A validated list of clean-up steps, e.g. [{"op": "open", "iterations": 2, "structure": "cross"},
-    {"op": "fill_holes", "max_area": 400}, {"op": "clear_border"}].  Unknown ops, unknown keys and bad values raise a
+    {"op": "fill_holes", "max_area": 400}, {"op": "split", "erosions": 8}, {"op": "clear_border"}].  Unknown ops, unknown keys and bad values raise a
     ValueError that names them, at construction.  ``apply`` runs the steps in order on a batch of device masks."""
 
     def __init__(self, steps):
@@ -162,6 +198,17 @@ class MaskCleanup(object):
                 if a is not None and (isinstance(a, bool) or not isinstance(a, int) or a < 1):
                     raise ValueError("postprocess step %d (fill_holes): max_area must be a positive integer or null, got %r"
                                      % (i, a))
+            elif op == 'split':
+                r, t = full['erosions'], full['reach']
+                if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= MORPH_MAX_ITER:
+                    raise ValueError("postprocess step %d (split): erosions must be an integer 1 .. %d, got %r"
+                                     % (i, MORPH_MAX_ITER, r))
+                if full['structure'] not in STRUCTURES:
+                    raise ValueError("postprocess step %d (split): structure must be one of %s, got %r"
+                                     % (i, sorted(STRUCTURES), full['structure']))
+                if t is not None and (isinstance(t, bool) or not isinstance(t, int) or not 1 <= t <= SPLIT_MAX_REACH):
+                    raise ValueError("postprocess step %d (split): reach must be an integer 1 .. %d or null, got %r"
+                                     % (i, SPLIT_MAX_REACH, t))
             self.steps.append(full)
         self._cache = {}
 
@@ -175,7 +222,8 @@ class MaskCleanup(object):
             lib = _lib.load()
             need = 0
             for s in self.steps:
-                fn = {'fill_holes': lib.sq_mask_fill_holes_workspace, 'clear_border': lib.sq_mask_clear_border_workspace}.get(s['op'])
+                fn = {'fill_holes': lib.sq_mask_fill_holes_workspace, 'clear_border': lib.sq_mask_clear_border_workspace,
+                      'split': lib.sq_mask_split_workspace}.get(s['op'])
                 if fn is not None:
                     nbytes = fn(*_dims(mask))
                     if nbytes < 0:
@@ -201,6 +249,8 @@ class MaskCleanup(object):
                 morph(src, s['op'], s['iterations'], s['structure'], classes, out=dst)
             elif s['op'] == 'fill_holes':
                 fill_holes(src, s['max_area'], classes, out=dst, workspace=ws)
+            elif s['op'] == 'split':
+                split(src, s['erosions'], s['structure'], s['reach'], classes, out=dst, workspace=ws)
             else:
                 clear_border(src, classes, out=dst, workspace=ws)
             src = dst
