@@ -1335,6 +1335,66 @@ int64_t sq_mask_split_workspace(int N, int H, int W);
 int sq_mask_split_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, int erosions, int structure, int reach,
                      void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Label zones and the zone contact graph (sequitr_amd/analysis/neighbors.py: which cells are next to
+ * which).  The reference counts neighbours per frame on the host with scipy's Voronoi / Delaunay of the centroids
+ * (sequitr/analysis/neighbors.py); here the per-pixel part -- the zone of influence of every object -- and the per-pixel
+ * part of the adjacency run on the device.  Planar (N, H, W) int32 images only, fewer than 2^31 elements.  Only integer
+ * arithmetic: the same bits on every run.  Neither call reads anything back, waits on a flag or lets one block wait on
+ * another: both can be captured in a graph.
+ *
+ * sq_label_zones_i32.  labels (N,H,W) int32: a pixel is a SEED of object L iff 1 <= L <= max_label; every other value,
+ * negative and too-large ones included, is background and not an error.  max_distance R >= 0, 0 = unbounded.
+ *   D(n,p)     = the minimum over the seeds q of frame n of the exact squared Euclidean distance |p - q|^2
+ *   zones(n,p) = the smallest label among the seeds of frame n at squared distance D(n,p)
+ *   d2(n,p)    = D(n,p)                                        (d2 may be NULL)
+ *   With R > 0 a pixel with D > R*R gets zone 0; d2 still holds D.
+ *   A frame without a seed gets zone 0 and d2 = 0x7fffffff everywhere (scipy's feature transform points such a frame at
+ *   index (-1, 0); that artefact is not reproduced).  The search never crosses from frame n into n +- 1.
+ * Consequences: a seed pixel lies in its own zone (D = 0 and it is the only seed there); without a reach the zones of a
+ * frame with a seed cover it.  This is skimage.segmentation.expand_labels with the tie rule pinned.
+ * The transform is separable and exact, the tie rule included:
+ *   rows    : per pixel the distance g along the row to the nearest seed of that row (30000 = none) and the smaller label
+ *             of the at most two seeds at that distance.  One wave per row over 64-pixel segments: the ballot of seed
+ *             lanes, the nearest set bit to the left / right by clz / ffs with a carry between segments, the label
+ *             fetched from that lane by a shuffle or from the carried value.  u16 + int32 = 6 B per pixel of workspace.
+ *   columns : the lexicographic minimum over rows y' of (g(y',x)^2 + (y - y')^2, label(y',x)), searched outwards from y,
+ *             lanes along x, while dy^2 <= the best distance so far -- <=, not <: an equidistant seed with a smaller label
+ *             further out must still be seen.  Without d2 and with R > 0 the search also stops at dy > R; with d2 it runs
+ *             on, because d2 = D beyond the reach too.  A per-frame flag spares a frame without a seed the search.
+ * workspace: sq_label_zones_workspace(N, H, W) bytes = 16 ceil(N / 4) + 6 N H W rounded up to 16 (-1: N, H or W < 1, H or
+ * W >= 30000, or 2^31 or more elements), 16-B aligned.
+ * SQ_EINVAL with a message, before any launch: null labels, zones or workspace; N, H or W < 1; H or W >= 30000; 2^31 or
+ * more elements; max_label outside 1 .. 2^21 - 1; max_distance outside 0 .. 46340 (R*R must fit an int32); a workspace
+ * that is not 16-B aligned or overlaps labels, zones or d2; zones overlapping d2.
+ *
+ * sq_zone_graph.  zones (N,H,W) int32; values outside 1 .. max_label count as 0.
+ *   stats (N, max_label + 1, 2) int64, [area, edge] per label: area = the number of pixels of the zone, edge = the number
+ *       of those on the frame's outer border (first / last row or column; a corner counts once).  Row 0 stays 0.
+ *   pairs (max_pairs, 4) int32 [frame, a, b, border], a < b, in no particular order: border = the number of pixel pairs
+ *       (p, right neighbour) and (p, lower neighbour) within the frame in which one pixel has zone a and the other zone
+ *       b, both > 0.  One row per distinct (frame, a, b) with border > 0.
+ *   count (device int32): the number of rows written, at most max_pairs.
+ *   dropped (device int32): 0 iff the rows are complete.  It counts the boundary runs that found no free slot in the
+ *       table plus the distinct pairs that found no row; when it is not 0 the caller comes back with a larger max_pairs.
+ * The call clears stats, count, dropped and its table itself.  One wave per image row, one lane per pixel: runs of equal
+ * (a, b) along the row are found with a shuffle and a ballot, and the leader lane of each run makes one insert-and-add of
+ * the run's length into an open-addressing table in the workspace (a 64-bit key of (frame, a, b) claimed with a
+ * compare-and-swap, a 32-bit integer add for the count; the smallest power of two >= 2 max_pairs slots).  Areas and edges
+ * get the same treatment: one 64-bit add per run of equal zone, never one per pixel.  A second kernel writes the rows.
+ * Sums of integers: the set of rows and every count are independent of the order in which the atomics arrive.
+ * workspace: sq_zone_graph_workspace(max_pairs) bytes = 12 per slot rounded up to 16 (-1: max_pairs outside 1 .. 2^28).
+ * SQ_EINVAL with a message, before any launch: a null pointer; N, H or W < 1; N >= 2^21; 2^31 or more elements; max_label
+ * outside 1 .. 2^21 - 1; max_pairs outside 1 .. 2^28; a workspace that is not 16-B aligned or overlaps zones or an output;
+ * stats not 8-B aligned.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_label_zones_workspace(int N, int H, int W);
+int sq_label_zones_i32(const int32_t *labels, int32_t *zones, int32_t *d2, int N, int H, int W, int max_label,
+                       int max_distance, void *workspace, void *stream);
+int64_t sq_zone_graph_workspace(int max_pairs);
+int sq_zone_graph(const int32_t *zones, int N, int H, int W, int max_label, int64_t *stats, int32_t *pairs, int max_pairs,
+                  int32_t *count, int32_t *dropped, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

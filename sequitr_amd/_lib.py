@@ -103,6 +103,10 @@ SIGNATURES = {
     "sq_mask_clear_border_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     "sq_mask_split_workspace": (c_int64, [c_int, c_int, c_int]),
     "sq_mask_split_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
+    "sq_label_zones_workspace": (c_int64, [c_int, c_int, c_int]),
+    "sq_label_zones_i32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p]),
+    "sq_zone_graph_workspace": (c_int64, [c_int]),
+    "sq_zone_graph": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int] + [c_void_p] * 4),
     "sq_dense_workspace_f32": (c_int64, [c_int, c_int, c_int]),
     "sq_dense_fwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "sq_convT_conv3x3_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

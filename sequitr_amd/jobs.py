@@ -484,8 +484,22 @@ def SERVER_segment_frames(params, options):
     ``labels.npy`` and the min_area / max_area filter all describe the cleaned mask, and segment.json records the steps
     under 'postprocess'.  A bad step list raises before a frame is read; without the key nothing changes.  A step
     {"op": "split", "erosions": r, "structure": ..., "reach": ...} (maskops.split) cuts touching cells apart, so the
-    centroid file and ``objects.npz`` get one row per cell instead of one per clump."""
+    centroid file and ``objects.npz`` get one row per cell instead of one per clump.
+
+    options['neighbors'] (implies measure) finds every object's neighbours per batch in HBM (sequitr_amd/analysis/
+    neighbors.py: touching zones of influence, NOT the reference's Delaunay of the centroids): ``neighbors.npz`` holds
+    NeighborTable.columns() of the whole stack, one row per row of ``objects.npz`` with ``indices`` global, segment.json a
+    ``neighbors`` record (objects, pairs, pairs_removed and the parameters with their defaults filled in);
+    options['save_zones'] adds ``zones.npy`` (F,H,W) int32.  params['d_thresh'] (default 100.0), params['zone_reach'] (the
+    zones' max_distance, default none) and params['neighbor_seeds'] ('objects' or 'centroids'); a bad value raises before a
+    frame is opened.  The table describes the mask after `postprocess` and the size filter: dropped objects are no seeds.
+    Without the option every file is what it was."""
     postprocess = _parse_postprocess(params)                    # before anything is opened
+    want_neighbors = bool(options.get('neighbors'))
+    if want_neighbors:                                          # a bad value raises here, before a frame is opened
+        from .analysis.neighbors import check_params
+        d_thresh, zone_reach, neighbor_seeds = check_params(params.get('d_thresh', 100.0), params.get('zone_reach'),
+                                                            params.get('neighbor_seeds', 'objects'))
     import torch
     from .networks.unet import UNet2D
     from . import utils
@@ -515,7 +529,7 @@ def SERVER_segment_frames(params, options):
     else:
         net.initialize()
     per_frame = {}
-    want_measure = bool(options.get('measure'))
+    want_measure = bool(options.get('measure')) or want_neighbors
     want_centroids = bool(options.get('centroids')) or want_measure
     masks = np.empty((F, H, W), np.uint8) if want_centroids else None
     min_area, max_area = int(params.get('min_area') or 1), params.get('max_area')
@@ -524,8 +538,11 @@ def SERVER_segment_frames(params, options):
         raise ValueError("params['min_area'] / params['max_area'] need options['measure']")
     label_stack = np.empty((F, H, W), np.int32) if want_measure and options.get('save_labels') else None
     tables, firsts = [], []
+    neighbor_tables = []
+    zone_stack = np.empty((F, H, W), np.int32) if want_neighbors and options.get('save_zones') else None
+    num_classes = int(net_p.get('num_outputs', 2))
 
-    def sink(first, m):                                        # centroids need the masks while they are in HBM
+    def sink(first, m):                                       # centroids need the masks while they are in HBM
         from .centroids import mask_centroids
         masks[first:first + m.shape[0]] = m.cpu().numpy()
         for k, coords in enumerate(mask_centroids(m)):
@@ -535,11 +552,19 @@ def SERVER_segment_frames(params, options):
     def measure_sink(first, raw, m):                           # objects against the raw frames, both still in HBM
         from .objects import measure_objects
         image = raw if raw.dim() == 3 else raw[measure_channel]   # (C, n, H, W) planes: the channel's slice as it lies
-        t = measure_objects(m, image=image, min_area=min_area, max_area=max_area, labels=label_stack is not None,
-                            filtered_mask=bounded)
+        t = measure_objects(m, image=image, min_area=min_area, max_area=max_area,
+                            labels=label_stack is not None or want_neighbors, filtered_mask=bounded)
         masks[first:first + m.shape[0]] = (t.mask if bounded else m).cpu().numpy()
         if label_stack is not None:
             label_stack[first:first + m.shape[0]] = t.labels.cpu().numpy()
+        if want_neighbors:                                      # on the kept objects' labels, while the batch is in HBM
+            from .analysis.neighbors import neighbors_from_objects
+            nt = neighbors_from_objects(t, num_classes, d_thresh, zone_reach, neighbor_seeds,
+                                        return_zones=zone_stack is not None)
+            if zone_stack is not None:
+                zone_stack[first:first + m.shape[0]] = nt.zones.cpu().numpy()
+                nt.zones = None
+            neighbor_tables.append(nt)
         tables.append(t)
         firsts.append(first)
 
@@ -579,6 +604,16 @@ def SERVER_segment_frames(params, options):
         info['centroids'] = {'file': os.path.basename(cw.filename), 'objects': len(table)}
         info['objects'] = {'count': len(table), 'found': int(table.found), 'min_area': min_area,
                            'max_area': None if max_area is None else int(max_area), 'with_intensity': True}
+        if want_neighbors:
+            from .analysis.neighbors import NeighborTable
+            order = np.argsort(firsts, kind='stable')           # batches in the stack's order: indices become global rows
+            ntable = NeighborTable.concatenate([neighbor_tables[i] for i in order], [firsts[i] for i in order], F)
+            np.savez(os.path.join(out_dir, 'neighbors.npz'), **ntable.columns())
+            if zone_stack is not None:
+                np.save(os.path.join(out_dir, 'zones.npy'), zone_stack)
+            info['neighbors'] = {'objects': len(ntable), 'pairs': int(ntable.n_pairs),
+                                 'pairs_removed': int(ntable.n_pairs_removed), 'num_classes': num_classes,
+                                 'd_thresh': d_thresh, 'zone_reach': zone_reach, 'neighbor_seeds': neighbor_seeds}
     elif want_centroids:
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
