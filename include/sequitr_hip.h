@@ -952,7 +952,8 @@ int sq_frames_to_tiles_mc(const void *frames, int dtype, int64_t chan_stride, co
 
 /* ------------------------------------------------------------------------------------------
  * Frame cleaning: the pipes the reference applies to raw microscope frames in front of ImageNorm, per whole frame,
- * in the order ImageOutliers -> ImageBGSubtract -> ImageNorm (sequitr_amd/frontend.py: FrameClean, FrameTiler).
+ * in the order ImageOutliers -> ImageBlur -> ImageBGSubtract -> ImageNorm (sequitr_amd/frontend.py: FrameClean,
+ * FrameTiler).
  *   sq_frame_outliers_f32 : ImageOutliers (sequitr/pipeline.py:266-295: median_filter(image, sigma), then
  *                           image[|image - med| > threshold] = med).  frames (F,H,W) SQ_PIX_* -> out (F,H,W) f32,
  *                           BIT-EXACT: x = the pixel as float32; med = the element of rank size*size/2 (0-based,
@@ -975,8 +976,34 @@ int sq_frames_to_tiles_mc(const void *frames, int dtype, int64_t chan_stride, co
  *                           (float)((r - mean[f]) / (1e-99 + stdv[f])) evaluated in fp64, or (float)r when
  *                           mean == stdv == NULL.  The reference's result after ImageBGSubtract is float64; this is
  *                           where the chain's one rounding to the network's float32 happens.
+ *   sq_frame_blur_f32     : ImageBlur (sequitr/pipeline.py:244-263: gaussian_filter(image, sigma) per channel).  frames
+ *                           (F,H,W) SQ_PIX_* -> out (F,H,W) f32, never aliasing frames, BIT-EXACT with scipy's
+ *                           gaussian_filter of the float32 plane, whose radius is R = int(4.0 * sigma + 0.5).  `weights`
+ *                           is a HOST array of radius + 1 doubles, w[0] the centre, read before the launch and carried
+ *                           in the kernel arguments by value (a captured graph replays them).  The caller computes them
+ *                           in numpy float64 with scipy's own expressions (the library never calls exp: the last bit of
+ *                           two libms may differ):
+ *                               x = np.arange(-R, R + 1); phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+ *                               phi /= phi.sum(); w[k] = phi[R + k], k = 0 .. R
+ *                           One pass along an axis of length L, for each output i:
+ *                               acc = (double)a[i] * w[0]
+ *                               for k = R, R-1, .. 1:  acc = acc + ((double)a[refl(i-k)] + (double)a[refl(i+k)]) * w[k]
+ *                           the add, the multiply and the add three separate float64 roundings (no fused multiply-add:
+ *                           the kernel is compiled with contraction off), the result rounded once to float32.  refl is
+ *                           scipy's mode='reflect' repeated until the index is inside (i < 0 -> -i-1, i >= L -> 2L-1-i;
+ *                           L == 1 -> 0): a frame may be far smaller than R.  The first pass runs along axis 0 (down
+ *                           the columns) over the pixel cast to float32, the second along axis 1 over the float32
+ *                           result of the first; that intermediate rounding is part of the definition.  radius 0
+ *                           (sigma < 0.125) still multiplies by w[0] == 1.0.  One launch; the intermediate lives in LDS.
+ *                           Refused before any launch: radius outside 0 .. 32 (sigma >= 8.125), a weight that is not
+ *                           finite, F outside 1 .. 65535, H or W < 1, H*W > 2^24, an unknown pixel type, a null pointer.
+ *                           On the device the order is ImageOutliers -> ImageBlur -> ImageBGSubtract -> ImageNorm: after
+ *                           hot-pixel removal, which a blur would smear, before the fit and the statistics, which see
+ *                           the blurred frame.
  * F <= 65535 (a grid dimension).
  * ---------------------------------------------------------------------------------------- */
+int sq_frame_blur_f32(const void *frames, int dtype, float *out, const double *weights, int radius, int F, int H, int W,
+                      void *stream);
 int sq_frame_outliers_f32(const void *frames, int dtype, float *out, int F, int H, int W, int size, float threshold,
                           void *stream);
 int64_t sq_frame_bgfit_workspace(int F, int H, int W);

@@ -77,6 +77,7 @@ SIGNATURES = {
     "sq_stitch_masks_u8": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "sq_frames_to_tiles_mc": (c_int, [c_void_p, c_int, c_int64] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
     "sq_frame_outliers_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "sq_frame_blur_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sq_frame_bgfit_workspace": (c_int64, [c_int, c_int, c_int]),
     "sq_frame_bgfit_f64": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "sq_frame_bg_stats_f64": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),

@@ -9,9 +9,10 @@ Tiling (build-defined: the reference only ever crops fixed-size tiles, pipeline.
 length L, tiles of size T start at 0, T-2m, 2(T-2m), ... and the last one at L-T; every pixel is owned by the
 tile in which it lies at least `m` (margin) pixels from the tile border, except at the frame border.
 
-In front of ImageNorm the reference's ImageOutliers (hot pixels, pipeline.py:266-295) and ImageBGSubtract (uneven
-illumination, pipeline.py:360-405) run on the device too, per whole frame before tiling (FrameClean, FrameTiler.outliers /
-background / tiles(clean=), segment_frames(clean=); include/sequitr_hip.h "Frame cleaning").
+In front of ImageNorm the reference's ImageOutliers (hot pixels, pipeline.py:266-295), ImageBlur (a Gaussian,
+pipeline.py:244-263) and ImageBGSubtract (uneven illumination, pipeline.py:360-405) run on the device too, per whole frame
+before tiling (FrameClean, FrameTiler.outliers / blur / background / tiles(clean=), segment_frames(clean=);
+include/sequitr_hip.h "Frame cleaning").
 
 Volumes take the same path in three dimensions (VolumeTiler, segment_volumes): a brick is a box of the network's
 input shape, the rule above holds along each axis, and an axis shorter than the brick is padded with the
@@ -110,40 +111,75 @@ def volume_bricks(vol_shape, brick, margin):
     return BrickGeometry(vol_shape, brick, margin)
 
 
+BLUR_MAX_RADIUS = 32
+BLUR_TILES = ((8, 32, 128), (16, 32, 96), (32, 32, 64))        # sq_frame_blur.hip's radius classes: (largest R, tile H, tile W)
+
+
+def blur_weights(sigma):
+    """(R, w) of ImageBlur(sigma) on the device: scipy's radius R = int(4.0 * sigma + 0.5) and the float64 weights w[0 .. R]
+    of its _gaussian_kernel1d, w[0] the centre, computed with scipy's own numpy expressions (include/sequitr_hip.h "Frame
+    cleaning").  sigma must be a finite number > 0 with R <= 32 (sigma < 8.125); anything else raises ValueError."""
+    if isinstance(sigma, (bool, str, bytes)) or not isinstance(sigma, (int, float, np.integer, np.floating)):
+        raise ValueError('ImageBlur: sigma must be a number, got %r' % (sigma,))
+    sigma = float(sigma)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError('ImageBlur: sigma must be finite and > 0, got %r' % (sigma,))
+    R = int(4.0 * sigma + 0.5)
+    if R > BLUR_MAX_RADIUS:
+        raise ValueError('ImageBlur: sigma %r gives a filter radius of %d, the device takes up to %d (sigma < 8.125)'
+                         % (sigma, R, BLUR_MAX_RADIUS))
+    x = np.arange(-R, R + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return R, np.ascontiguousarray(phi[R:], dtype=np.float64)
+
+
 class FrameClean(object):
     """What is done to a whole raw frame on the GPU in front of ImageNorm (include/sequitr_hip.h "Frame cleaning"), a plain
     value: `outliers` is None or (size, threshold) of ImageOutliers (the pipe calls its window size `sigma`,
-    sequitr/pipeline.py:266-295), `bgsubtract` whether ImageBGSubtract follows.  The order is the only one the device
-    has: ImageOutliers -> ImageBGSubtract -> ImageNorm."""
+    sequitr/pipeline.py:266-295), `bgsubtract` whether ImageBGSubtract follows, `blur` None or the sigma of ImageBlur
+    (sequitr/pipeline.py:244-263).  The order is the only one the device has:
+    ImageOutliers -> ImageBlur -> ImageBGSubtract -> ImageNorm."""
 
-    PIPES = ('ImageOutliers', 'ImageBGSubtract', 'ImageNorm')
+    PIPES = ('ImageOutliers', 'ImageBlur', 'ImageBGSubtract', 'ImageNorm')
 
-    def __init__(self, outliers=None, bgsubtract=False):
+    def __init__(self, outliers=None, bgsubtract=False, blur=None):
         if outliers is not None:
             size, threshold = outliers
             if isinstance(size, bool) or int(size) != size or not 2 <= int(size) <= 5:
                 raise ValueError('ImageOutliers: the window (sigma) is 2, 3, 4 or 5 on the device, got %r' % (size,))
             outliers = (int(size), float(threshold))
+        if blur is not None:
+            blur_weights(blur)                                  # raises for a sigma the device does not take
+            blur = float(blur)
         self.outliers = outliers
         self.bgsubtract = bool(bgsubtract)
+        self.blur = blur
+
+    def _key(self):
+        return (self.outliers, self.bgsubtract, self.blur)
 
     def __eq__(self, other):
-        return isinstance(other, FrameClean) and (self.outliers, self.bgsubtract) == (other.outliers, other.bgsubtract)
+        return isinstance(other, FrameClean) and self._key() == other._key()
 
     def __hash__(self):
-        return hash((self.outliers, self.bgsubtract))
+        return hash(self._key())
 
     def __repr__(self):
-        return 'FrameClean(outliers=%r, bgsubtract=%r)' % (self.outliers, self.bgsubtract)
+        if self.blur is None:
+            return 'FrameClean(outliers=%r, bgsubtract=%r)' % (self.outliers, self.bgsubtract)
+        return 'FrameClean(outliers=%r, bgsubtract=%r, blur=%r)' % (self.outliers, self.bgsubtract, self.blur)
 
     def __bool__(self):
-        return self.outliers is not None or self.bgsubtract
+        return self.outliers is not None or self.bgsubtract or self.blur is not None
 
     def pipes(self, normalise=True):
         """the chain as SERVER_segment_frames records it: [{pipe name: its arguments}, ...]"""
         chain = []
         if self.outliers is not None:
             chain.append({'ImageOutliers': {'sigma': self.outliers[0], 'threshold': self.outliers[1]}})
+        if self.blur is not None:
+            chain.append({'ImageBlur': {'sigma': self.blur}})
         if self.bgsubtract:
             chain.append({'ImageBGSubtract': {}})
         if normalise:
@@ -153,8 +189,9 @@ class FrameClean(object):
     @classmethod
     def from_pipeline(cls, pipeline):
         """(clean or None, normalise) of an ImagePipeline, or of the path of the JSON ImagePipeline.save wrote.  Accepted
-        are exactly the subsequences of [ImageOutliers, ImageBGSubtract, ImageNorm] in that order; any other pipe, order
-        or duplicate, or an ImageOutliers.sigma outside 2 .. 5, raises ValueError naming the pipe (no CPU fallback)."""
+        are exactly the subsequences of [ImageOutliers, ImageBlur, ImageBGSubtract, ImageNorm] in that order; any other
+        pipe, order or duplicate, an ImageOutliers.sigma outside 2 .. 5 or an ImageBlur.sigma that is not a finite number
+        in (0, 8.125), raises ValueError naming the pipe (no CPU fallback)."""
         from . import pipeline as pl
         if isinstance(pipeline, str):
             with open(pipeline, 'r') as f:
@@ -167,10 +204,10 @@ class FrameClean(object):
             pipeline = pl.ImagePipeline.load(pipeline)
         if not isinstance(pipeline, pl.ImagePipeline):
             raise TypeError('pipeline must be an ImagePipeline or the path of its JSON, got %r' % (pipeline,))
-        outliers, bgsubtract, normalise, stage = None, False, False, -1
+        outliers, blur, bgsubtract, normalise, stage = None, None, False, False, -1
         for pipe in pipeline.pipeline:
             name = pipe.__class__.__name__
-            if type(pipe) not in (pl.ImageOutliers, pl.ImageBGSubtract, pl.ImageNorm):
+            if type(pipe) not in (pl.ImageOutliers, pl.ImageBlur, pl.ImageBGSubtract, pl.ImageNorm):
                 raise ValueError('%s does not run on whole frames on the GPU (only %s do, in that order)'
                                  % (name, ', '.join(cls.PIPES)))
             at = cls.PIPES.index(name)
@@ -185,10 +222,15 @@ class FrameClean(object):
                 except (TypeError, ValueError) as e:
                     raise ValueError('ImageOutliers(sigma=%r, threshold=%r): %s' % (pipe.sigma, pipe.threshold, e))
             elif at == 1:
+                try:
+                    blur = cls(blur=pipe.sigma).blur
+                except (TypeError, ValueError) as e:
+                    raise ValueError('ImageBlur(sigma=%r): %s' % (pipe.sigma, e))
+            elif at == 2:
                 bgsubtract = True
             else:
                 normalise = True
-        clean = cls(outliers, bgsubtract)
+        clean = cls(outliers, bgsubtract, blur)
         return (clean if clean else None), normalise
 
 
@@ -290,6 +332,8 @@ class FrameTiler(object):
             return None
         F, d, lib = int(F), self.device, _lib.load()
         s = {'frames': F, 'f32': torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)}
+        if clean.outliers is not None and clean.blur is not None:   # the blur reads what the outliers step wrote
+            s['blurred'] = torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)
         if clean.bgsubtract:
             nbytes = lib.sq_frame_bgfit_workspace(F, self.H, self.W)
             if nbytes < 0:
@@ -337,6 +381,30 @@ class FrameTiler(object):
         _lib.check(_lib.load().sq_frame_outliers_f32(frames.data_ptr(), PIX[frames.dtype], out.data_ptr(), F, self.H, self.W,
                                                      size, float(threshold), torch.cuda.current_stream().cuda_stream),
                    'sq_frame_outliers_f32')
+        return out
+
+    def blur(self, frames, sigma, out=None):
+        """ImageBlur(sigma) of every frame, raw or float32: (F,H,W) float32, bit-exact with the host pipe (scipy's
+        gaussian_filter of the float32 plane; (C,F,H,W) planes in, (C,F,H,W) out with channels > 1).  `out` must not be
+        `frames`."""
+        if self.channels > 1:
+            F = self._check_planes(frames)
+            out = self._mc_f32_out(F, out)
+            for c in range(self.channels):
+                self._one.blur(frames[c], sigma, out=out[c])
+            return out
+        self._check_frames(frames)
+        R, w = blur_weights(sigma)
+        F = frames.shape[0]
+        if not 1 <= F <= 65535 or self.H * self.W > 1 << 24:
+            raise ValueError('ImageBlur on the device takes 1 .. 65535 frames of H*W <= 2^24, got %d of %d x %d'
+                             % (F, self.H, self.W))
+        out = self._f32_out(F, out)
+        if out.data_ptr() == frames.data_ptr():
+            raise ValueError('ImageBlur does not run in place: out must not be frames')
+        _lib.check(_lib.load().sq_frame_blur_f32(frames.data_ptr(), PIX[frames.dtype], out.data_ptr(), w.ctypes.data, R, F,
+                                                 self.H, self.W, torch.cuda.current_stream().cuda_stream),
+                   'sq_frame_blur_f32')
         return out
 
     def to_f32(self, frames, out=None):
@@ -434,6 +502,10 @@ class FrameTiler(object):
         f32 = scratch['f32'][:F] if scratch is not None else None
         if clean.outliers is not None:
             x = self.outliers(frames, clean.outliers[0], clean.outliers[1], out=f32)
+            if clean.blur is not None:
+                x = self.blur(x, clean.blur, out=scratch['blurred'][:F] if scratch is not None else None)
+        elif clean.blur is not None:                            # straight from the raw pixels: no cast pass
+            x = self.blur(frames, clean.blur, out=f32)
         else:
             x = self.to_f32(frames, out=f32)
         if not clean.bgsubtract:                                # ImageNorm of the cleaned frames: the kernels of the plain path
@@ -449,10 +521,10 @@ class FrameTiler(object):
 
     def tiles(self, frames, normalise=True, clean=None, scratch=None):
         """(F*TR*TC, T, T, 1) float32 tiles, ImageNorm applied per frame when `normalise`; with `clean` (a FrameClean) the
-        frames go through ImageOutliers and / or ImageBGSubtract first, per whole frame (`scratch`: clean_scratch(), for
-        callers that come back batch after batch).  With channels > 1: (C,F,H,W) planes in, (F*TR*TC, T, T, C) tiles out of
-        one sq_frames_to_tiles_mc launch, `clean` one FrameClean for all channels or a sequence of C (None: that channel is
-        not cleaned)."""
+        frames go through ImageOutliers, ImageBlur and / or ImageBGSubtract first, per whole frame (`scratch`:
+        clean_scratch(), for callers that come back batch after batch).  With channels > 1: (C,F,H,W) planes in,
+        (F*TR*TC, T, T, C) tiles out of one sq_frames_to_tiles_mc launch, `clean` one FrameClean for all channels or a
+        sequence of C (None: that channel is not cleaned)."""
         if self.channels > 1:
             return self._mc_tiles(frames, normalise, clean, scratch)
         self._check_frames(frames)
@@ -509,6 +581,8 @@ class FrameTiler(object):
         s = {'frames': F, 'cleans': tuple(cleans), 'normalise': bool(normalise)}
         if any(cleans):
             s['f32'] = torch.empty((C, F, self.H, self.W), dtype=torch.float32, device=d)
+        if any(c is not None and c.outliers is not None and c.blur is not None for c in cleans):
+            s['blur_in'] = torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)   # shared by the channels
         if any(c is not None and c.bgsubtract for c in cleans):
             nbytes = lib.sq_frame_bgfit_workspace(F, self.H, self.W)
             if nbytes < 0:
@@ -540,7 +614,13 @@ class FrameTiler(object):
             src = scratch['f32'][:, :F]
             for c in range(C):
                 if cleans[c] is not None and cleans[c].outliers is not None:
-                    one.outliers(frames[c], cleans[c].outliers[0], cleans[c].outliers[1], out=src[c])
+                    blurred = cleans[c].blur is not None        # then the outliers step writes the shared temporary
+                    x = one.outliers(frames[c], cleans[c].outliers[0], cleans[c].outliers[1],
+                                     out=scratch['blur_in'][:F] if blurred else src[c])
+                    if blurred:
+                        one.blur(x, cleans[c].blur, out=src[c])
+                elif cleans[c] is not None and cleans[c].blur is not None:
+                    one.blur(frames[c], cleans[c].blur, out=src[c])
                 elif frames.dtype == torch.float32:
                     src[c].copy_(frames[c])
                 else:
@@ -644,8 +724,8 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     Raw frames are staged through two pinned buffers and uploaded on a side stream while the previous batch is
     normalised, tiled, segmented (net.predict) and stitched; returns the (F,H,W) uint8 masks (host), or
     streams each batch's device masks to on_masks(first_frame, masks) and returns None.  `clean` (a FrameClean) puts
-    ImageOutliers and / or ImageBGSubtract in front of ImageNorm, per whole frame, on the same stream: nothing on the host
-    waits between a batch's upload and its net.predict.  on_batch(first_frame, raw_frames, masks) is on_masks with the
+    ImageOutliers, ImageBlur and / or ImageBGSubtract in front of ImageNorm, per whole frame, on the same stream: nothing
+    on the host waits between a batch's upload and its net.predict.  on_batch(first_frame, raw_frames, masks) is on_masks with the
     batch's raw device frames as well (a slice of a staging buffer, valid until the callback returns: the buffer is
     released to the next upload after it); it also makes the function return None, and only one of the two may be given.
 

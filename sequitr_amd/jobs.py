@@ -467,9 +467,9 @@ def SERVER_segment_frames(params, options):
     the range from all of these, and ``mask.npy`` is then the mask without them.
     params: shape (tile, default (512,512)), margin, frames_per_batch, model / filters / ... as SERVER_segment;
     pipeline: the JSON ImagePipeline.save wrote (or an ImagePipeline).  It runs on the GPU per whole frame and may hold
-    any subsequence of ImageOutliers, ImageBGSubtract, ImageNorm in that order (frontend.FrameClean.from_pipeline; anything
-    else raises before a frame is read -- there is no host fallback); segment.json records it under 'pipeline'.  Without
-    it the frames are normalised with ImageNorm alone.
+    any subsequence of ImageOutliers, ImageBlur, ImageBGSubtract, ImageNorm in that order (frontend.FrameClean.from_pipeline;
+    ImageBlur with a finite sigma in (0, 8.125); anything else raises before a frame is read -- there is no host fallback);
+    segment.json records it under 'pipeline'.  Without it the frames are normalised with ImageNorm alone.
 
     Multi-channel frames (bright field + fluorescence): params['input'] may be a list of C sources, each an Octopus stem, a
     .npy or an ndarray of (F,H,W) frames of one length, shape and pixel type, or one interleaved (F,H,W,C) .npy / ndarray.
