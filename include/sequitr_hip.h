@@ -905,7 +905,11 @@ int sq_space_to_depth2x2x2_f32(const float *dy, float *g, int N, int D, int H, i
  *                        workspace: sq_frame_stats_workspace bytes.  frames need the alignment of their pixel type
  *                        only (a channel's slice of multi-channel planes, below).
  *   sq_frames_to_tiles : tiles (F*TR*TC, TS, TS) f32, tile (f,ty,tx) = frame f at origin (oy[ty], ox[tx]),
- *                        value (x - mean[f]) / std[f], or the plain cast when mean == std == NULL.
+ *                        value (x - mean[f]) / std[f], or the plain cast when mean == std == NULL.  One kernel cuts the
+ *                        tiles of this entry, of sq_frames_to_tiles_bg and of sq_frames_to_tiles_mc (C = 1 here); it
+ *                        indexes tile rows in 32 bits, so all three refuse F*TR*TC*TS > 2^31 - 1 ("tile rows are out of
+ *                        range") before any launch -- unreachable for TS >= 36 within 288 GB of tiles.  tiles need no
+ *                        more than float alignment here: C = 1 stores scalars.
  *   sq_stitch_masks_u8 : out (F,H,W): pixel (y,x) = tile_masks[(f, ymap[y]>>16, xmap[x]>>16)][ymap[y]&0xffff][xmap[x]&0xffff]
  *
  * Multi-channel frames (bright field + fluorescence, one stack per channel: sequitr/dataio/octopus.py:321-328) are
@@ -921,8 +925,8 @@ int sq_space_to_depth2x2x2_f32(const float *dy, float *g, int N, int D, int H, i
  *                          SQ_CH_BG_NORM : (float)((r - mean64[c,f]) / (1e-99 + std64[c,f])) in fp64 (sq_frames_to_tiles_bg's)
  *                        with bg evaluated by rows as sq_frames_to_tiles_bg does, every multiply-add of the surface one
  *                        fused operation:  t' = fma(t, fma(c5, t, c2), c0),  b = fma(c4, t, c1),
- *                        bg = fma(s, fma(c3, s, b), t').  Channel c has the bits sq_frames_to_tiles / sq_frames_to_tiles_bg
- *                        give on channel c's stack.  All channels are read in one pixel type `dtype`; the two background
+ *                        bg = fma(s, fma(c3, s, b), t').  Channel c is what sq_frames_to_tiles / sq_frames_to_tiles_bg
+ *                        give on channel c's stack: the same kernel.  All channels are read in one pixel type `dtype`; the two background
  *                        modes need SQ_PIX_F32 (the float32 frames sq_frame_outliers_f32 or a cast wrote) and H, W >= 3.
  *                        A statistics pointer may be NULL only if no channel's mode reads it.  An unknown mode or pixel
  *                        type, C outside 1 .. 8, chan_stride < F*H*W, a tile that does not fit, F*TR*TC*TS >= 2^31 and
@@ -975,7 +979,9 @@ int sq_frames_to_tiles_mc(const void *frames, int dtype, int64_t chan_stride, co
  *   sq_frames_to_tiles_bg : sq_frames_to_tiles' geometry on the residual (sequitr/pipeline.py:402-405, then :350-356):
  *                           (float)((r - mean[f]) / (1e-99 + stdv[f])) evaluated in fp64, or (float)r when
  *                           mean == stdv == NULL.  The reference's result after ImageBGSubtract is float64; this is
- *                           where the chain's one rounding to the network's float32 happens.
+ *                           where the chain's one rounding to the network's float32 happens.  The kernel is
+ *                           sq_frames_to_tiles_mc's in mode SQ_CH_BG / SQ_CH_BG_NORM with C = 1 ("Tile front end"): the
+ *                           surface is evaluated by rows with every multiply-add one fused operation, as stated there.
  *   sq_frame_blur_f32     : ImageBlur (sequitr/pipeline.py:244-263: gaussian_filter(image, sigma) per channel).  frames
  *                           (F,H,W) SQ_PIX_* -> out (F,H,W) f32, never aliasing frames, BIT-EXACT with scipy's
  *                           gaussian_filter of the float32 plane, whose radius is R = int(4.0 * sigma + 0.5).  `weights`
@@ -1126,8 +1132,9 @@ int sq_volume_sample_onehot_u8(const uint8_t *labels, int C, const int32_t *plan
  *                           +-2^23 rule, "no load ever leaves the arrays" and SQ_ROTATE_LDS are the contract above, word
  *                           for word (under SQ_ROTATE_LDS=1 the planes pass through the staging buffer one after the
  *                           other and the image is stored one channel per pass, CI floats apart; only the default
- *                           direct form was timed for this entry, tools/multichannel_bench.py).  Channel c has the bits sq_tile_sample_affine gives on channel c's stack, and with
- *                           CI == 1 the call is sq_tile_sample_affine.  CI outside 1 .. 8 or chan_stride < F*H*W (with
+ *                           direct form was timed for this entry, tools/multichannel_bench.py).  Channel c is what
+ *                           sq_tile_sample_affine gives on channel c's stack -- the same kernel: sq_tile_sample_affine
+ *                           is this entry with CI == 1 and chan_stride = F*H*W.  CI outside 1 .. 8 or chan_stride < F*H*W (with
  *                           frames given) is refused before any launch, next to everything the entry above refuses.
  * ---------------------------------------------------------------------------------------- */
 int sq_tile_sample_affine(const void *frames, int dtype, const float *mean, const float *stdv, const uint8_t *labels,

@@ -39,6 +39,25 @@ int sq_wgrad_f32_plan(int N, int H, int W, int Cin, int Cout, int K, int64_t *ou
         }                                                         \
     } while (0)
 
+// the C floats of one interleaved pixel at p, in the widest pieces C allows (p aligned to them: 16 bytes when C % 4 == 0,
+// 8 when C % 2 == 0); C = 1 is a scalar store
+template <int C>
+__device__ __forceinline__ void sq_store_pixel(float *__restrict__ p, const float (&o)[C]) {
+    if constexpr (C % 4 == 0) {
+#pragma unroll
+        for (int q = 0; q < C; q += 4) {
+            const f32x4 v = {o[q], o[q + 1], o[q + 2], o[q + 3]};
+            *reinterpret_cast<f32x4 *>(p + q) = v;
+        }
+    } else if constexpr (C % 2 == 0) {
+#pragma unroll
+        for (int q = 0; q < C; q += 2) *reinterpret_cast<float2 *>(p + q) = make_float2(o[q], o[q + 1]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < C; ++q) p[q] = o[q];
+    }
+}
+
 static inline int sq_check_launch(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

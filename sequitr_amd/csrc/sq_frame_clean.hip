@@ -15,6 +15,7 @@
 // closed form.  No atomics: the result is the same on every run, and a frame's strips depend on (H, W) only.
 #include "sq_common.h"
 #include "sq_rank_select.h"
+#include "sq_bg_surface.h"   // the surface's coordinates (bg_axis), shared with the tile cutter (sq_frontend.hip)
 
 namespace {
 
@@ -104,19 +105,6 @@ inline int bg_strips(int H) {
     const int n = (H + BG_MIN_ROWS - 1) / BG_MIN_ROWS;
     return n < BG_MAX_STRIPS ? n : BG_MAX_STRIPS;
 }
-
-struct BgAxis { double centre, inv; };                          // scaled coordinate = (index - centre) * inv
-__host__ __device__ inline BgAxis bg_axis(int L) {
-    const double c = 0.5 * (double)(L - 1);
-    return {c, 1.0 / c};
-}
-
-// the surface in the basis of the header, by rows: (c0 + c2 t + c5 t^2) + s ((c1 + c4 t) + c3 s)
-struct BgRow { double a, b, c; };
-__device__ __forceinline__ BgRow bg_row(const double *__restrict__ k, double t) {
-    return {k[0] + t * (k[2] + k[5] * t), k[1] + k[4] * t, k[3]};
-}
-__device__ __forceinline__ double bg_eval(const BgRow &r, double s) { return r.a + s * (r.b + r.c * s); }
 
 // sums of NV doubles over the block in a fixed order: xor butterfly inside a wave, then the four waves in order
 template <int NV>
@@ -217,10 +205,15 @@ __global__ __launch_bounds__(256) void bg_resid_sums_kernel(const float *__restr
     double m[2] = {0, 0};
     for (int v = v0; v < v1; ++v) {
         const float *__restrict__ row = src + (size_t)v * W;
-        const BgRow br = bg_row(coef + (size_t)f * 6, ((double)v - ay.centre) * ay.inv);
+        // sq_bg_surface.h's bg_row and bg_eval as plain expressions: the compiler's default contraction fuses the same five
+        // multiply-adds (the ISA shows them), and this kernel's instruction stream stays the one its results were pinned on
+        const double *__restrict__ k = coef + (size_t)f * 6;
+        const double t = ((double)v - ay.centre) * ay.inv;
+        const double ra = k[0] + t * (k[2] + k[5] * t), rb = k[1] + k[4] * t, rc = k[3];
 #pragma unroll 4
         for (int u = threadIdx.x; u < W; u += 256) {
-            const double r = (double)row[u] - bg_eval(br, ((double)u - ax.centre) * ax.inv);
+            const double s = ((double)u - ax.centre) * ax.inv;
+            const double r = (double)row[u] - (ra + s * (rb + rc * s));
             m[0] += r;
             m[1] += r * r;
         }
@@ -243,34 +236,6 @@ __global__ void bg_stats_finish_kernel(const double *__restrict__ ws, double *__
     const double mu = s1 / n, var = s2 / n - mu * mu;
     mean[f] = mu;
     stdv[f] = sqrt(var > 0.0 ? var : 0.0);
-}
-
-// sq_frames_to_tiles' geometry on the residual; the one rounding to float32 of the chain happens here
-__global__ __launch_bounds__(256) void tiles_bg_kernel(const float *__restrict__ frames, const double *__restrict__ coef,
-                                                       const double *__restrict__ mean, const double *__restrict__ stdv,
-                                                       const int *__restrict__ oy, const int *__restrict__ ox,
-                                                       float *__restrict__ tiles, int F, int H, int W, int TR, int TC, int TS) {
-    const int64_t total = (int64_t)F * TR * TC * TS * TS;
-    const BgAxis ax = bg_axis(W), ay = bg_axis(H);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % TS);
-        int64_t t = i / TS;
-        const int y = (int)(t % TS);
-        t /= TS;
-        const int tx = (int)(t % TC);
-        t /= TC;
-        const int ty = (int)(t % TR);
-        const int f = (int)(t / TR);
-        const int v = oy[ty] + y, u = ox[tx] + x;
-        const BgRow br = bg_row(coef + (size_t)f * 6, ((double)v - ay.centre) * ay.inv);
-        const double r = (double)frames[((size_t)f * H + v) * W + u] - bg_eval(br, ((double)u - ax.centre) * ax.inv);
-        tiles[i] = (float)(mean ? (r - mean[f]) / (1e-99 + stdv[f]) : r);
-    }
-}
-
-inline unsigned fc_grid(int64_t items) {
-    int64_t b = (items + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
 inline bool bg_shape_ok(int F, int H, int W) {
@@ -327,16 +292,4 @@ extern "C" int sq_frame_bg_stats_f64(const float *frames, const double *coef, do
     hipLaunchKernelGGL(bg_stats_finish_kernel, dim3((F + 63) / 64), dim3(64), 0, st, ws, mean, stdv, F,
                        (double)H * (double)W, ns);
     return sq_check_launch("sq_frame_bg_stats_f64");
-}
-
-extern "C" int sq_frames_to_tiles_bg(const float *frames, const double *coef, const double *mean, const double *stdv,
-                                     const int32_t *oy, const int32_t *ox, float *tiles, int F, int H, int W, int TR, int TC,
-                                     int TS, void *stream) {
-    SQ_REQUIRE(frames && coef && oy && ox && tiles, "sq_frames_to_tiles_bg: null pointer");
-    SQ_REQUIRE((mean == nullptr) == (stdv == nullptr), "sq_frames_to_tiles_bg: give both mean and std, or neither");
-    SQ_REQUIRE(F > 0 && H >= 3 && W >= 3 && TR > 0 && TC > 0 && TS > 0 && TS <= H && TS <= W,
-               "sq_frames_to_tiles_bg: tile %d does not fit %d x %d (H, W >= 3)", TS, H, W);
-    hipLaunchKernelGGL(tiles_bg_kernel, dim3(fc_grid((int64_t)F * TR * TC * TS * TS)), dim3(256), 0, (hipStream_t)stream,
-                       frames, coef, mean, stdv, oy, ox, tiles, F, H, W, TR, TC, TS);
-    return sq_check_launch("sq_frames_to_tiles_bg");
 }

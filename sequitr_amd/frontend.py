@@ -248,10 +248,11 @@ def channel_cleans(clean, channels):
 
 
 class FrameTiler(object):
-    """Geometry + device kernels for frames of one (H, W) shape.  With channels > 1 the frames are channel-major planes,
-    a (C, F, H, W) tensor or the [:, :n] view of a contiguous (C, B, H, W) one (include/sequitr_hip.h "Tile front end"):
-    every per-frame kernel runs on each channel's slice, statistics come back as (C, F), and tiles() weaves the planes into
-    (F*TR*TC, T, T, C) in one launch."""
+    """Geometry + device kernels for frames of one (H, W) shape.  Inside, a batch is always (C, F, H, W) channel-major planes
+    (include/sequitr_hip.h "Tile front end"): every per-frame kernel runs on each channel's slice and tiles() weaves the
+    planes into (F*TR*TC, T, T, C) in one launch.  A one-channel tiler takes and returns what a single stack needs --
+    (F, H, W) frames, (F,) statistics, (F, 6) coefficients -- as the one plane of that layout; with channels > 1 the frames
+    are a (C, F, H, W) tensor or the [:, :n] view of a contiguous (C, B, H, W) one, and statistics come back as (C, F)."""
 
     def __init__(self, frame_shape, tile=512, margin=32, device=None, channels=1):
         self.H, self.W = int(frame_shape[0]), int(frame_shape[1])
@@ -268,14 +269,12 @@ class FrameTiler(object):
         d = self.device
         self._oy, self._ox = torch.from_numpy(self.oy).to(d), torch.from_numpy(self.ox).to(d)
         self._ymap, self._xmap = torch.from_numpy(self.ymap).to(d), torch.from_numpy(self.xmap).to(d)
-        if self.channels > 1:                                   # the per-frame kernels, on one channel's slice at a time
-            self._one = FrameTiler.__new__(FrameTiler)
-            self._one.__dict__.update(self.__dict__, channels=1)
 
     @property
     def tiles_per_frame(self):
         return self.TR * self.TC
 
+    # ---- what goes in and out: (F, ...) for one channel, (C, F, ...) for more ---------------------------------------
     def _check_planes(self, frames, dtypes=None):
         """(C, F, H, W) channel-major planes: every (H, W) plane contiguous, frames of a channel back to back"""
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
@@ -293,154 +292,146 @@ class FrameTiler(object):
                              'got strides %r' % (st,))
         return F
 
-    def _check_frames(self, frames):
-        if self.channels > 1:
-            raise ValueError('this tiler was built for %d channels: pass (C,F,H,W) planes' % self.channels)
+    def _check_frames(self, frames, dtypes=None):
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise _lib.SequitrHipError('frames must be a tensor in GPU memory (no CPU fallback exists)')
         if frames.dtype not in PIX or frames.dim() != 3 or not frames.is_contiguous():
             raise ValueError('frames must be a contiguous (F,H,W) uint8 / uint16 / float32 tensor')
         if tuple(frames.shape[1:]) != (self.H, self.W):
             raise ValueError('frames are %s, tiler was built for %s' % (tuple(frames.shape[1:]), (self.H, self.W)))
+        if dtypes and frames.dtype not in dtypes:
+            raise ValueError('the background fit reads float32 frames (outliers() or to_f32() make them), got %s' % frames.dtype)
+        return int(frames.shape[0])
 
-    def stats(self, frames, scratch=None):
-        """per-frame float32 (mean, std) exactly as np.mean / np.std of the float32 frame; (C, F) each with channels > 1."""
+    def _planes(self, frames, dtypes=None):
+        """the caller's frames as (C, F, H, W) planes, and F; a one-channel tiler's (F, H, W) stack is the one plane"""
         if self.channels > 1:
-            return self._mc_stats(frames, scratch)
-        self._check_frames(frames)
-        F = frames.shape[0]
-        lib = _lib.load()
-        nbytes = lib.sq_frame_stats_workspace(F, self.H, self.W)
-        if nbytes < 0:
-            raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
-        if scratch is not None:
-            ws, mean, std = scratch['stats_ws'], scratch['mean'][:F], scratch['std'][:F]
-        else:
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-            mean = torch.empty(F, dtype=torch.float32, device=self.device)
-            std = torch.empty(F, dtype=torch.float32, device=self.device)
-        _lib.check(lib.sq_frame_stats(frames.data_ptr(), PIX[frames.dtype], mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
-                                      F, self.H, self.W, torch.cuda.current_stream().cuda_stream), 'sq_frame_stats')
-        return mean, std
+            return frames, self._check_planes(frames, dtypes)
+        F = self._check_frames(frames, dtypes)
+        return frames[None], F
 
-    def clean_scratch(self, F, clean, normalise=True):
-        """The tensors tiles(..., clean=clean) needs for up to F frames, so that a caller that streams batches (segment_frames)
-        allocates them once: the cleaned float32 frames and, per chain, the fit's coefficients, statistics and workspaces."""
-        if self.channels > 1:
-            return self._mc_scratch(F, channel_cleans(clean, self.channels), normalise)
-        if not clean:
-            return None
-        F, d, lib = int(F), self.device, _lib.load()
-        s = {'frames': F, 'f32': torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)}
-        if clean.outliers is not None and clean.blur is not None:   # the blur reads what the outliers step wrote
-            s['blurred'] = torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)
-        if clean.bgsubtract:
-            nbytes = lib.sq_frame_bgfit_workspace(F, self.H, self.W)
-            if nbytes < 0:
-                raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
-                                 '%d x %d' % (F, self.H, self.W))
-            s['bg_ws'] = torch.empty(nbytes // 8, dtype=torch.float64, device=d)
-            s['coef'] = torch.empty((F, 6), dtype=torch.float64, device=d)
-            s['mean64'], s['std64'] = (torch.empty(F, dtype=torch.float64, device=d) for _ in range(2))
-        elif normalise:
-            nbytes = lib.sq_frame_stats_workspace(F, self.H, self.W)
-            if nbytes < 0:
-                raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
-            s['stats_ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=d)
-            s['mean'], s['std'] = (torch.empty(F, dtype=torch.float32, device=d) for _ in range(2))
-        return s
+    def _lead(self, F):
+        return (F,) if self.channels == 1 else (self.channels, F)
+
+    def _result(self, t):
+        """a (C, F, ...) result as the caller sees it"""
+        return t[0] if self.channels == 1 else t
+
+    def _rows(self, buf, F, tail=()):
+        """the (C, F) + tail array at the start of a scratch buffer made for F or more frames: index c * F + f"""
+        n = self.channels * F * int(np.prod(tail, dtype=np.int64))
+        return buf.view(-1)[:n].view((self.channels, F) + tuple(tail))
 
     def _f32_out(self, F, out):
+        """(`out`, or a new tensor for the float32 frames a kernel writes; the same as planes)"""
+        shape = self._lead(F) + (self.H, self.W)
         if out is None:
-            return torch.empty((F, self.H, self.W), dtype=torch.float32, device=self.device)
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                and tuple(out.shape) == (F, self.H, self.W)):
-            raise ValueError('out must be a contiguous (%d,%d,%d) float32 tensor in GPU memory' % (F, self.H, self.W))
-        return out
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+                  and (self.channels > 1 or out.is_contiguous())):
+            raise ValueError('out must be a %s(%s) float32 tensor in GPU memory'
+                             % ('contiguous ' if self.channels == 1 else '', ','.join(str(n) for n in shape)))
+        return out, self._planes(out, (torch.float32,))[0]
 
-    def _check_f32(self, frames):
-        self._check_frames(frames)
-        if frames.dtype != torch.float32:
-            raise ValueError('the background fit reads float32 frames (outliers() or to_f32() make them), got %s' % frames.dtype)
+    def _stats_workspace(self, F):
+        nbytes = _lib.load().sq_frame_stats_workspace(F, self.H, self.W)
+        if nbytes < 0:
+            raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
+        return torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+
+    def _bg_workspace(self, F):
+        nbytes = _lib.load().sq_frame_bgfit_workspace(F, self.H, self.W)
+        if nbytes < 0:
+            raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
+                             '%d x %d' % (F, self.H, self.W))
+        return torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+
+    # ---- the per-frame kernels on one channel's (F, H, W) slice: arguments already checked ---------------------------
+    def _stats(self, x, F, ws, mean, std):
+        _lib.check(_lib.load().sq_frame_stats(x.data_ptr(), PIX[x.dtype], mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
+                                              F, self.H, self.W, torch.cuda.current_stream().cuda_stream), 'sq_frame_stats')
+
+    def _outliers(self, x, F, size, threshold, out):
+        size = FrameClean(outliers=(size, threshold)).outliers[0]
+        if min(self.H, self.W) < size:
+            raise ValueError('a window of %d does not fit frames of %d x %d' % (size, self.H, self.W))
+        _lib.check(_lib.load().sq_frame_outliers_f32(x.data_ptr(), PIX[x.dtype], out.data_ptr(), F, self.H, self.W, size,
+                                                     float(threshold), torch.cuda.current_stream().cuda_stream),
+                   'sq_frame_outliers_f32')
+
+    def _blur(self, x, F, sigma, out):
+        R, w = blur_weights(sigma)
+        if not 1 <= F <= 65535 or self.H * self.W > 1 << 24:
+            raise ValueError('ImageBlur on the device takes 1 .. 65535 frames of H*W <= 2^24, got %d of %d x %d'
+                             % (F, self.H, self.W))
+        if out.data_ptr() == x.data_ptr():
+            raise ValueError('ImageBlur does not run in place: out must not be frames')
+        _lib.check(_lib.load().sq_frame_blur_f32(x.data_ptr(), PIX[x.dtype], out.data_ptr(), w.ctypes.data, R, F, self.H,
+                                                 self.W, torch.cuda.current_stream().cuda_stream), 'sq_frame_blur_f32')
+
+    def _cast(self, x, F, out):
+        """integer frames to float32 through the volume front end's cast, every frame one brick of a one-slice volume"""
+        if not hasattr(self, '_whole'):
+            self._whole = torch.tensor([0, 0, 0, 0, 0, 0, 1, self.H, self.W], dtype=torch.int32).to(self.device)
+        for lo in range(0, F, 65535):
+            n = min(65535, F - lo)
+            _lib.check(_lib.load().sq_volume_to_bricks(x[lo:].data_ptr(), PIX[x.dtype], None, None, self._whole.data_ptr(),
+                                                       out[lo:].data_ptr(), n, 1, self.H, self.W, 1, 1, 1, 1, self.H, self.W,
+                                                       0, n, torch.cuda.current_stream().cuda_stream), 'sq_volume_to_bricks')
+
+    def _fit(self, x, F, ws, coef):
+        _lib.check(_lib.load().sq_frame_bgfit_f64(x.data_ptr(), coef.data_ptr(), ws.data_ptr(), F, self.H, self.W,
+                                                  torch.cuda.current_stream().cuda_stream), 'sq_frame_bgfit_f64')
+
+    def _residual_stats(self, x, F, coef, ws, mean, std):
+        _lib.check(_lib.load().sq_frame_bg_stats_f64(x.data_ptr(), coef.data_ptr(), mean.data_ptr(), std.data_ptr(),
+                                                     ws.data_ptr(), F, self.H, self.W,
+                                                     torch.cuda.current_stream().cuda_stream), 'sq_frame_bg_stats_f64')
+
+    # ---- the same, for callers: every channel of the frames ----------------------------------------------------------
+    def stats(self, frames, scratch=None):
+        """per-frame float32 (mean, std) exactly as np.mean / np.std of the float32 frame; (C, F) each with channels > 1."""
+        x, F = self._planes(frames)
+        if scratch is not None and 'stats_ws' not in scratch:   # clean_scratch() makes them when a channel's mode reads them
+            scratch = None
+        if scratch is not None:
+            ws, mean, std = scratch['stats_ws'], self._rows(scratch['mean'], F), self._rows(scratch['std'], F)
+        else:
+            ws = self._stats_workspace(F)
+            mean, std = (torch.empty((self.channels, F), dtype=torch.float32, device=self.device) for _ in range(2))
+        for c in range(self.channels):
+            self._stats(x[c], F, ws, mean[c], std[c])
+        return self._result(mean), self._result(std)
 
     def outliers(self, frames, size, threshold, out=None):
         """ImageOutliers(sigma=size, threshold) of every raw frame: (F,H,W) float32, bit-exact with the host pipe
         ((C,F,H,W) planes in, (C,F,H,W) out with channels > 1)."""
-        if self.channels > 1:
-            F = self._check_planes(frames)
-            out = self._mc_f32_out(F, out)
-            for c in range(self.channels):
-                self._one.outliers(frames[c], size, threshold, out=out[c])
-            return out
-        self._check_frames(frames)
-        size = FrameClean(outliers=(size, threshold)).outliers[0]
-        if min(self.H, self.W) < size:
-            raise ValueError('a window of %d does not fit frames of %d x %d' % (size, self.H, self.W))
-        F = frames.shape[0]
-        out = self._f32_out(F, out)
-        _lib.check(_lib.load().sq_frame_outliers_f32(frames.data_ptr(), PIX[frames.dtype], out.data_ptr(), F, self.H, self.W,
-                                                     size, float(threshold), torch.cuda.current_stream().cuda_stream),
-                   'sq_frame_outliers_f32')
+        x, F = self._planes(frames)
+        out, o = self._f32_out(F, out)
+        for c in range(self.channels):
+            self._outliers(x[c], F, size, threshold, o[c])
         return out
 
     def blur(self, frames, sigma, out=None):
         """ImageBlur(sigma) of every frame, raw or float32: (F,H,W) float32, bit-exact with the host pipe (scipy's
         gaussian_filter of the float32 plane; (C,F,H,W) planes in, (C,F,H,W) out with channels > 1).  `out` must not be
         `frames`."""
-        if self.channels > 1:
-            F = self._check_planes(frames)
-            out = self._mc_f32_out(F, out)
-            for c in range(self.channels):
-                self._one.blur(frames[c], sigma, out=out[c])
-            return out
-        self._check_frames(frames)
-        R, w = blur_weights(sigma)
-        F = frames.shape[0]
-        if not 1 <= F <= 65535 or self.H * self.W > 1 << 24:
-            raise ValueError('ImageBlur on the device takes 1 .. 65535 frames of H*W <= 2^24, got %d of %d x %d'
-                             % (F, self.H, self.W))
-        out = self._f32_out(F, out)
-        if out.data_ptr() == frames.data_ptr():
-            raise ValueError('ImageBlur does not run in place: out must not be frames')
-        _lib.check(_lib.load().sq_frame_blur_f32(frames.data_ptr(), PIX[frames.dtype], out.data_ptr(), w.ctypes.data, R, F,
-                                                 self.H, self.W, torch.cuda.current_stream().cuda_stream),
-                   'sq_frame_blur_f32')
+        x, F = self._planes(frames)
+        blur_weights(sigma)                                     # refused before anything is allocated
+        out, o = self._f32_out(F, out)
+        for c in range(self.channels):
+            self._blur(x[c], F, sigma, o[c])
         return out
 
     def to_f32(self, frames, out=None):
-        """the raw frames cast to float32 (what ImagePipe.__call__ does first): float32 frames are returned as they are,
-        integer ones go through the volume front end's cast, every frame one brick of a one-slice volume"""
-        if self.channels > 1:
-            F = self._check_planes(frames)
-            if frames.dtype == torch.float32:
-                return frames
-            out = self._mc_f32_out(F, out)
-            for c in range(self.channels):
-                self._one.to_f32(frames[c], out=out[c])
-            return out
-        self._check_frames(frames)
+        """the raw frames cast to float32 (what ImagePipe.__call__ does first): float32 frames are returned as they are"""
+        x, F = self._planes(frames)
         if frames.dtype == torch.float32:
             return frames
-        F = frames.shape[0]
-        out = self._f32_out(F, out)
-        if not hasattr(self, '_whole'):
-            self._whole = torch.tensor([0, 0, 0, 0, 0, 0, 1, self.H, self.W], dtype=torch.int32).to(self.device)
-        for lo in range(0, F, 65535):
-            n = min(65535, F - lo)
-            _lib.check(_lib.load().sq_volume_to_bricks(frames[lo:].data_ptr(), PIX[frames.dtype], None, None,
-                                                       self._whole.data_ptr(), out[lo:].data_ptr(), n, 1, self.H, self.W,
-                                                       1, 1, 1, 1, self.H, self.W, 0, n,
-                                                       torch.cuda.current_stream().cuda_stream), 'sq_volume_to_bricks')
+        out, o = self._f32_out(F, out)
+        for c in range(self.channels):
+            self._cast(x[c], F, o[c])
         return out
-
-    def _bg_workspace(self, F, scratch):
-        if scratch is not None:
-            return scratch['bg_ws']
-        nbytes = _lib.load().sq_frame_bgfit_workspace(F, self.H, self.W)
-        if nbytes < 0:
-            raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
-                             '%d x %d' % (F, self.H, self.W))
-        return torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
 
     def background(self, frames_f32, scratch=None):
         """ImageBGSubtract's least-squares surface of every float32 frame: coef (F,6) float64 with
@@ -448,183 +439,89 @@ class FrameTiler(object):
         t = (v - (H-1)/2) / ((H-1)/2) for row v (include/sequitr_hip.h "Frame cleaning").  With channels > 1 every
         channel of every frame gets its own fit, coef (C,F,6): the single-channel contract per plane (the reference's
         ImageBGSubtract does not take more than one channel)."""
-        if self.channels > 1:
-            F = self._check_planes(frames_f32, (torch.float32,))
-            ws = self._bg_workspace(F, scratch)
+        x, F = self._planes(frames_f32, (torch.float32,))
+        ws = scratch['bg_ws'] if scratch is not None else self._bg_workspace(F)
+        if scratch is not None and 'coef' in scratch:
+            coef = self._rows(scratch['coef'], F, (6,))
+        else:
             coef = torch.empty((self.channels, F, 6), dtype=torch.float64, device=self.device)
-            for c in range(self.channels):
-                self._one.background(frames_f32[c], scratch={'bg_ws': ws, 'coef': coef[c]})
-            return coef
-        self._check_f32(frames_f32)
-        F = frames_f32.shape[0]
-        ws = self._bg_workspace(F, scratch)
-        coef = scratch['coef'][:F] if scratch is not None else torch.empty((F, 6), dtype=torch.float64, device=self.device)
-        _lib.check(_lib.load().sq_frame_bgfit_f64(frames_f32.data_ptr(), coef.data_ptr(), ws.data_ptr(), F, self.H, self.W,
-                                                  torch.cuda.current_stream().cuda_stream), 'sq_frame_bgfit_f64')
-        return coef
+        for c in range(self.channels):
+            self._fit(x[c], F, ws, coef[c])
+        return self._result(coef)
 
     def background_stats(self, frames_f32, coef, scratch=None):
         """per-frame float64 (mean, std) of the residual frame - bg(coef), np.std's definition; (C, F) each with channels > 1"""
-        if self.channels > 1:
-            F = self._check_planes(frames_f32, (torch.float32,))
-            C = self.channels
-            if not (isinstance(coef, torch.Tensor) and coef.is_cuda and coef.dtype == torch.float64 and coef.is_contiguous()
-                    and tuple(coef.shape) == (C, F, 6)):
-                raise ValueError('coef must be the contiguous (%d,%d,6) float64 tensor background() returned' % (C, F))
-            ws = self._bg_workspace(F, scratch)
-            mean, std = (torch.empty((C, F), dtype=torch.float64, device=self.device) for _ in range(2))
-            for c in range(C):
-                self._one.background_stats(frames_f32[c], coef[c], scratch={'bg_ws': ws, 'mean64': mean[c], 'std64': std[c]})
-            return mean, std
-        self._check_f32(frames_f32)
-        F = frames_f32.shape[0]
-        self._check_coef(coef, F)
-        ws = self._bg_workspace(F, scratch)
-        if scratch is not None:
-            mean, std = scratch['mean64'][:F], scratch['std64'][:F]
-        else:
-            mean, std = (torch.empty(F, dtype=torch.float64, device=self.device) for _ in range(2))
-        _lib.check(_lib.load().sq_frame_bg_stats_f64(frames_f32.data_ptr(), coef.data_ptr(), mean.data_ptr(), std.data_ptr(),
-                                                     ws.data_ptr(), F, self.H, self.W,
-                                                     torch.cuda.current_stream().cuda_stream), 'sq_frame_bg_stats_f64')
-        return mean, std
-
-    def _check_coef(self, coef, F):
+        x, F = self._planes(frames_f32, (torch.float32,))
+        shape = self._lead(F) + (6,)
         if not (isinstance(coef, torch.Tensor) and coef.is_cuda and coef.dtype == torch.float64 and coef.is_contiguous()
-                and tuple(coef.shape) == (F, 6)):
-            raise ValueError('coef must be the contiguous (%d,6) float64 tensor background() returned' % F)
-
-    def _tiles_clean(self, frames, normalise, clean, scratch):
-        """tiles() behind a FrameClean: the cleaned float32 frames are written once, every later kernel reads them"""
-        F = frames.shape[0]
-        if scratch is not None and scratch['frames'] < F:
-            raise ValueError('scratch was made for %d frames, got %d' % (scratch['frames'], F))
-        f32 = scratch['f32'][:F] if scratch is not None else None
-        if clean.outliers is not None:
-            x = self.outliers(frames, clean.outliers[0], clean.outliers[1], out=f32)
-            if clean.blur is not None:
-                x = self.blur(x, clean.blur, out=scratch['blurred'][:F] if scratch is not None else None)
-        elif clean.blur is not None:                            # straight from the raw pixels: no cast pass
-            x = self.blur(frames, clean.blur, out=f32)
+                and tuple(coef.shape) == shape):
+            raise ValueError('coef must be the contiguous (%s) float64 tensor background() returned'
+                             % ','.join(str(n) for n in shape))
+        ws = scratch['bg_ws'] if scratch is not None else self._bg_workspace(F)
+        if scratch is not None and 'mean64' in scratch:
+            mean, std = self._rows(scratch['mean64'], F), self._rows(scratch['std64'], F)
         else:
-            x = self.to_f32(frames, out=f32)
-        if not clean.bgsubtract:                                # ImageNorm of the cleaned frames: the kernels of the plain path
-            return self.tiles(x, normalise=normalise, scratch=scratch)
-        coef = self.background(x, scratch=scratch)
-        mean, std = self.background_stats(x, coef, scratch=scratch) if normalise else (None, None)
-        out = torch.empty((F * self.TR * self.TC, self.T, self.T, 1), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.load().sq_frames_to_tiles_bg(x.data_ptr(), coef.data_ptr(), mean.data_ptr() if normalise else None,
-                                                     std.data_ptr() if normalise else None, self._oy.data_ptr(),
-                                                     self._ox.data_ptr(), out.data_ptr(), F, self.H, self.W, self.TR, self.TC,
-                                                     self.T, torch.cuda.current_stream().cuda_stream), 'sq_frames_to_tiles_bg')
-        return out
+            mean, std = (torch.empty((self.channels, F), dtype=torch.float64, device=self.device) for _ in range(2))
+        k = self._rows(coef, F, (6,))
+        for c in range(self.channels):
+            self._residual_stats(x[c], F, k[c], ws, mean[c], std[c])
+        return self._result(mean), self._result(std)
 
-    def tiles(self, frames, normalise=True, clean=None, scratch=None):
-        """(F*TR*TC, T, T, 1) float32 tiles, ImageNorm applied per frame when `normalise`; with `clean` (a FrameClean) the
-        frames go through ImageOutliers, ImageBlur and / or ImageBGSubtract first, per whole frame (`scratch`:
-        clean_scratch(), for callers that come back batch after batch).  With channels > 1: (C,F,H,W) planes in,
-        (F*TR*TC, T, T, C) tiles out of one sq_frames_to_tiles_mc launch, `clean` one FrameClean for all channels or a
-        sequence of C (None: that channel is not cleaned)."""
-        if self.channels > 1:
-            return self._mc_tiles(frames, normalise, clean, scratch)
-        self._check_frames(frames)
-        if clean:
-            if not isinstance(clean, FrameClean):
-                raise TypeError('clean must be a FrameClean, got %r' % (clean,))
-            return self._tiles_clean(frames, normalise, clean, scratch)
-        F = frames.shape[0]
-        mean, std = self.stats(frames, scratch if scratch and 'stats_ws' in scratch else None) if normalise else (None, None)
-        out = torch.empty((F * self.TR * self.TC, self.T, self.T, 1), dtype=torch.float32, device=self.device)
-        lib = _lib.load()
-        _lib.check(lib.sq_frames_to_tiles(frames.data_ptr(), PIX[frames.dtype],
-                                          mean.data_ptr() if normalise else None, std.data_ptr() if normalise else None,
-                                          self._oy.data_ptr(), self._ox.data_ptr(), out.data_ptr(), F, self.H, self.W,
-                                          self.TR, self.TC, self.T, torch.cuda.current_stream().cuda_stream),
-                   'sq_frames_to_tiles')
-        return out
-
-    # ---- channels > 1 -----------------------------------------------------------------------------------------------
-    def _mc_f32_out(self, F, out):
-        C = self.channels
-        if out is None:
-            return torch.empty((C, F, self.H, self.W), dtype=torch.float32, device=self.device)
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
-                and tuple(out.shape) == (C, F, self.H, self.W)):
-            raise ValueError('out must be a (%d,%d,%d,%d) float32 tensor in GPU memory' % (C, F, self.H, self.W))
-        self._check_planes(out, (torch.float32,))
-        return out
-
-    def _mc_stats(self, frames, scratch=None):
-        F = self._check_planes(frames)
-        C = self.channels
-        nbytes = _lib.load().sq_frame_stats_workspace(F, self.H, self.W)
-        if nbytes < 0:
-            raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
-        if scratch is not None and 'stats_ws' in scratch:        # clean_scratch() made them when a channel's mode reads them
-            ws, mean, std = scratch['stats_ws'], self._rows(scratch['mean'], F), self._rows(scratch['std'], F)
-        else:
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
-            mean, std = (torch.empty((C, F), dtype=torch.float32, device=self.device) for _ in range(2))
-        for c in range(C):
-            self._one.stats(frames[c], scratch={'stats_ws': ws, 'mean': mean[c], 'std': std[c]})
-        return mean, std
-
-    def _rows(self, flat, F, tail=()):
-        """the (C, F) + tail array at the start of a flat scratch buffer made for more frames: index c * F + f"""
-        n = self.channels * F * int(np.prod(tail, dtype=np.int64))
-        return flat[:n].view((self.channels, F) + tuple(tail))
-
-    def _mc_scratch(self, F, cleans, normalise):
-        """clean_scratch for channel-major planes: one float32 copy of all channels when any is cleaned, and flat buffers
-        for whatever statistics the channels' modes read"""
-        F, C, d, lib = int(F), self.channels, self.device, _lib.load()
+    def clean_scratch(self, F, clean, normalise=True, f32=True):
+        """The tensors tiles(..., clean=clean) needs for up to F frames, so that a caller that streams batches (segment_frames)
+        allocates them once: one float32 copy of all channels when any is cleaned, a temporary between ImageOutliers and
+        ImageBlur that the channels share, and flat buffers for whatever statistics the channels' modes read.  `f32=False`
+        leaves the float32 copy out: for float32 frames that no channel filters, which tiles() reads in place."""
+        cleans = channel_cleans(clean, self.channels)
+        F, C, d = int(F), self.channels, self.device
         s = {'frames': F, 'cleans': tuple(cleans), 'normalise': bool(normalise)}
-        if any(cleans):
+        if any(cleans) and f32:
             s['f32'] = torch.empty((C, F, self.H, self.W), dtype=torch.float32, device=d)
         if any(c is not None and c.outliers is not None and c.blur is not None for c in cleans):
-            s['blur_in'] = torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)   # shared by the channels
+            s['blur_in'] = torch.empty((F, self.H, self.W), dtype=torch.float32, device=d)
+            if C == 1:
+                s['blurred'] = s['blur_in']                     # the name a one-channel tiler's scratch has had for it
         if any(c is not None and c.bgsubtract for c in cleans):
-            nbytes = lib.sq_frame_bgfit_workspace(F, self.H, self.W)
-            if nbytes < 0:
-                raise ValueError('ImageBGSubtract on the device takes 1 .. 65535 frames of H, W >= 3 and H*W <= 2^24, got %d of '
-                                 '%d x %d' % (F, self.H, self.W))
-            s['bg_ws'] = torch.empty(nbytes // 8, dtype=torch.float64, device=d)
+            s['bg_ws'] = self._bg_workspace(F)
             s['coef'] = torch.empty(C * F * 6, dtype=torch.float64, device=d)
             if normalise:
                 s['mean64'], s['std64'] = (torch.empty(C * F, dtype=torch.float64, device=d) for _ in range(2))
         if normalise and any(c is None or not c.bgsubtract for c in cleans):
-            nbytes = lib.sq_frame_stats_workspace(F, self.H, self.W)
-            if nbytes < 0:
-                raise ValueError('frames of %d x %d pixels exceed 2^24 pixels' % (self.H, self.W))
-            s['stats_ws'] = torch.empty(nbytes // 4, dtype=torch.float32, device=d)
+            s['stats_ws'] = self._stats_workspace(F)
             s['mean'], s['std'] = (torch.empty(C * F, dtype=torch.float32, device=d) for _ in range(2))
         return s
 
-    def _mc_tiles(self, frames, normalise, clean, scratch):
-        F = self._check_planes(frames)
-        C, one = self.channels, self._one
+    def tiles(self, frames, normalise=True, clean=None, scratch=None):
+        """(F*TR*TC, T, T, C) float32 tiles out of one sq_frames_to_tiles_mc launch, ImageNorm applied per frame when
+        `normalise`; with `clean` the frames go through ImageOutliers, ImageBlur and / or ImageBGSubtract first, per whole
+        frame: one FrameClean for all channels or a sequence of C (None: that channel is not cleaned).  The cleaned float32
+        frames are written once and every later kernel reads them; float32 frames that no channel filters are read where
+        they are.  `scratch`: clean_scratch(), for callers that come back batch after batch."""
+        x, F = self._planes(frames)
+        C = self.channels
         cleans = channel_cleans(clean, C)
+        filtered = any(c is not None and (c.outliers is not None or c.blur is not None) for c in cleans)
+        copy = any(cleans) and (filtered or x.dtype != torch.float32)   # one pixel type for the launch: float32
         if scratch is None:
-            scratch = self._mc_scratch(F, cleans, normalise)
+            scratch = self.clean_scratch(F, cleans, normalise, f32=copy)
         elif scratch['frames'] < F or scratch['cleans'] != tuple(cleans) or scratch['normalise'] != bool(normalise):
             raise ValueError('scratch was made by clean_scratch(%d, %r, %r): it does not serve %d frames under %r, %r'
                              % (scratch['frames'], scratch['cleans'], scratch['normalise'], F, cleans, bool(normalise)))
-        src = frames
-        if any(cleans):                                         # one pixel type for the launch: float32, cleaned or cast
+        src = x
+        if copy:
             src = scratch['f32'][:, :F]
-            for c in range(C):
-                if cleans[c] is not None and cleans[c].outliers is not None:
-                    blurred = cleans[c].blur is not None        # then the outliers step writes the shared temporary
-                    x = one.outliers(frames[c], cleans[c].outliers[0], cleans[c].outliers[1],
-                                     out=scratch['blur_in'][:F] if blurred else src[c])
-                    if blurred:
-                        one.blur(x, cleans[c].blur, out=src[c])
-                elif cleans[c] is not None and cleans[c].blur is not None:
-                    one.blur(frames[c], cleans[c].blur, out=src[c])
-                elif frames.dtype == torch.float32:
-                    src[c].copy_(frames[c])
+            for c, cl in enumerate(cleans):
+                if cl is not None and cl.outliers is not None:
+                    first = scratch['blur_in'][:F] if cl.blur is not None else src[c]
+                    self._outliers(x[c], F, cl.outliers[0], cl.outliers[1], first)
+                    if cl.blur is not None:
+                        self._blur(first, F, cl.blur, src[c])
+                elif cl is not None and cl.blur is not None:    # straight from the raw pixels: no cast pass
+                    self._blur(x[c], F, cl.blur, src[c])
+                elif x.dtype == torch.float32:
+                    src[c].copy_(x[c])
                 else:
-                    one.to_f32(frames[c], out=src[c])
+                    self._cast(x[c], F, src[c])
         mean32 = std32 = coef = mean64 = std64 = None
         if 'mean' in scratch:
             mean32, std32 = self._rows(scratch['mean'], F), self._rows(scratch['std'], F)
@@ -633,20 +530,19 @@ class FrameTiler(object):
         if 'mean64' in scratch:
             mean64, std64 = self._rows(scratch['mean64'], F), self._rows(scratch['std64'], F)
         modes = np.zeros(C, np.int32)
-        for c in range(C):
-            if cleans[c] is not None and cleans[c].bgsubtract:
-                sub = {'bg_ws': scratch['bg_ws'], 'coef': coef[c]}
-                one.background(src[c], scratch=sub)
+        for c, cl in enumerate(cleans):
+            if cl is not None and cl.bgsubtract:
+                self._fit(src[c], F, scratch['bg_ws'], coef[c])
                 if normalise:
-                    sub['mean64'], sub['std64'] = mean64[c], std64[c]
-                    one.background_stats(src[c], coef[c], scratch=sub)
+                    self._residual_stats(src[c], F, coef[c], scratch['bg_ws'], mean64[c], std64[c])
                 modes[c] = CH_BG_NORM if normalise else CH_BG
             elif normalise:
-                one.stats(src[c], scratch={'stats_ws': scratch['stats_ws'], 'mean': mean32[c], 'std': std32[c]})
+                self._stats(src[c], F, scratch['stats_ws'], mean32[c], std32[c])
                 modes[c] = CH_NORM
         out = torch.empty((F * self.TR * self.TC, self.T, self.T, C), dtype=torch.float32, device=self.device)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(_lib.load().sq_frames_to_tiles_mc(src.data_ptr(), PIX[src.dtype], src.stride(0), modes.ctypes.data,
+        chan_stride = src.stride(0) if C > 1 else F * self.H * self.W
+        _lib.check(_lib.load().sq_frames_to_tiles_mc(src.data_ptr(), PIX[src.dtype], chan_stride, modes.ctypes.data,
                                                      ptr(mean32), ptr(std32), ptr(coef), ptr(mean64), ptr(std64),
                                                      self._oy.data_ptr(), self._ox.data_ptr(), out.data_ptr(), F, self.H,
                                                      self.W, C, self.TR, self.TC, self.T,
@@ -731,9 +627,10 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
 
     Multi-channel frames: `frames` may be a list or tuple of C sources of one dtype, shape and length (each an OctopusData
     or an (F,H,W) array -- the Octopus layout, one stack per channel), or one interleaved (F,H,W,C) array, which is
-    de-interleaved while it is copied into the pinned buffer.  Staging is then (C,B,H,W) channel-major planes, on_batch
-    receives the raw (C,n,H,W) view, `clean` is one FrameClean for all channels or a sequence of C (None entries: no
-    cleaning), and net.n_inputs must equal C (checked before any upload).  The masks are (F,H,W) as ever.
+    de-interleaved while it is copied into the pinned buffer.  Staging is always (C,B,H,W) channel-major planes (C = 1 for
+    a single stack); on_batch then receives the raw (C,n,H,W) view (the (n,H,W) frames of a single channel), `clean` is
+    one FrameClean for all channels or a sequence of C (None entries: no cleaning), and net.n_inputs must equal C (checked
+    before any upload).  The masks are (F,H,W) as ever.
 
     `postprocess` (a maskops.MaskCleanup, or the step list one is made of) cleans every batch's stitched masks in HBM with
     net.n_outputs classes; its result takes the stitched batch's place before on_masks / on_batch and before the
@@ -751,23 +648,17 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     if C is not None and int(net.n_inputs) != C:
         raise ValueError('the network takes %d input channels, the frames have %d' % (int(net.n_inputs), C))
     tdt = NP_TORCH[np_dtype]
-    tiler = FrameTiler((H, W), tile, margin, device=net.device, channels=C or 1)
+    if C is None and clean is not None and not isinstance(clean, FrameClean):
+        raise TypeError('clean must be a FrameClean or None, got %r' % (clean,))
+    single = C is None or C == 1                                # on_batch then sees (n,H,W) frames, the one plane
+    C = C or 1
+    tiler = FrameTiler((H, W), tile, margin, device=net.device, channels=C)
     dev = tiler.device
     B = int(frames_per_batch)
-    if C is None or C == 1:
-        lead, take = (), (lambda t, n: t[:n])
-        cleans = clean
-        if C == 1 and isinstance(clean, (list, tuple)):        # a list of one source may come with a list of one clean
-            cleans = channel_cleans(clean, 1)[0]
-        if cleans is not None and not isinstance(cleans, FrameClean):
-            raise TypeError('clean must be a FrameClean or None, got %r' % (clean,))
-    else:
-        lead, take = (C,), (lambda t, n: t[:, :n])
-        cleans = channel_cleans(clean, C)
-    pinned = [_pinned('in%d' % i, lead + (B, H, W), tdt) for i in range(2)]
-    staged = [torch.empty(lead + (B, H, W), dtype=tdt, device=dev) for _ in range(2)]
-    scratch = tiler.clean_scratch(B, cleans, normalise)         # once per call; the batches share it on the compute stream
-    clean = cleans
+    clean = channel_cleans(clean, C)
+    pinned = [_pinned('in%d' % i, (C, B, H, W), tdt) for i in range(2)]
+    staged = [torch.empty((C, B, H, W), dtype=tdt, device=dev) for _ in range(2)]
+    scratch = tiler.clean_scratch(B, clean, normalise)          # once per call; the batches share it on the compute stream
     copy_stream = torch.cuda.Stream(device=dev)
     ready = [torch.cuda.Event(), torch.cuda.Event()]            # upload of buffer i finished
     freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[i]
@@ -776,20 +667,15 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     def upload(k, first):
         n = min(B, F - first)
         ready[k].synchronize()                                 # the previous upload out of this pinned buffer is done
-        if not lead:
-            pinned[k][:n].numpy()[...] = gets[0](first, n)     # page cache / memmap -> pinned
-        elif len(gets) == 1:                                    # interleaved (n,H,W,C): de-interleaved by this one host copy
+        if len(gets) == 1 and C > 1:                            # interleaved (n,H,W,C): de-interleaved by this one host copy
             pinned[k][:, :n].numpy()[...] = np.moveaxis(gets[0](first, n), -1, 0)
         else:
             for c, get in enumerate(gets):
-                pinned[k][c, :n].numpy()[...] = get(first, n)
+                pinned[k][c, :n].numpy()[...] = get(first, n)  # page cache / memmap -> pinned
         with torch.cuda.stream(copy_stream):
             copy_stream.wait_event(freed[k])
-            if not lead:
-                staged[k][:n].copy_(pinned[k][:n], non_blocking=True)
-            else:
-                for c in range(C):                              # a channel's n frames are contiguous on both sides
-                    staged[k][c, :n].copy_(pinned[k][c, :n], non_blocking=True)
+            for c in range(C):                                  # a channel's n frames are contiguous on both sides
+                staged[k][c, :n].copy_(pinned[k][c, :n], non_blocking=True)
             ready[k].record(copy_stream)
         return n
 
@@ -813,17 +699,15 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         cur = torch.cuda.current_stream(dev)
         cur.wait_event(ready[k])
         n = counts[b]
-        if scratch is None:
-            tiles = tiler.tiles(take(staged[k], n), normalise=normalise)
-        else:
-            tiles = tiler.tiles(take(staged[k], n), normalise=normalise, clean=clean, scratch=scratch)
+        raw = staged[k][0, :n] if single else staged[k][:, :n]
+        tiles = tiler.tiles(raw, normalise=normalise, clean=clean, scratch=scratch)
         if on_batch is None:
             freed[k].record(cur)                               # after the last kernel that reads staged[k]
         masks = tiler.stitch(net.predict(tiles))
         if postprocess is not None:
             masks = postprocess.apply(masks, int(net.n_outputs))
         if on_batch is not None:
-            on_batch(b * B, take(staged[k], n), masks)
+            on_batch(b * B, raw, masks)
             freed[k].record(cur)                               # the callback's kernels read staged[k] too
             continue
         if on_masks is not None:
@@ -1234,7 +1118,7 @@ class TileSampler(object):
     of VolumeSampler and the device form of the reference's tr_augment (include/sequitr_hip.h "Tile sampler").  `plan` and
     `coef` are tile_sample_plan's rows (or a slice of them) in GPU memory; one launch fills all three outputs.  With
     channels > 1 the frames are (C, F, H, W) channel-major planes (FrameTiler's layout), the statistics (C, F) and the image
-    output (count, TH, TW, C) -- sq_tile_sample_affine_mc; labels and weights are as ever."""
+    output (count, TH, TW, C); labels and weights are as ever.  One entry, sq_tile_sample_affine_mc, for every C."""
 
     def __init__(self, frame_shape, tile, device=None, channels=1):
         self.shape, self.tile = tuple(int(s) for s in frame_shape), tuple(int(s) for s in tile)
@@ -1291,46 +1175,6 @@ class TileSampler(object):
         `normalise` (with `stats` = self.stats(frames) when the caller already has them).  `out` takes the three
         preallocated tensors (None for a source that is None).  With channels > 1 the frames are (C, F, H, W) planes, the
         stats (C, F) and the image (count, TH, TW, C)."""
-        if self.channels > 1:
-            return self._sample_mc(frames, labels, weights, plan, coef, C, normalise, stats, out)
-        count = self._rows(plan, 'plan', 4, torch.int32)
-        if self._rows(coef, 'coef', 6, torch.float32) != count:
-            raise ValueError('plan has %d rows, coef %d' % (count, coef.shape[0]))
-        if not 1 <= count <= 65535:
-            raise ValueError('a plan of %d rows is not one launch (1 .. 65535 rows)' % count)
-        C = int(C)
-        if not 1 <= C <= 16:
-            raise ValueError('%d classes are not 1 .. 16' % C)
-        if frames is None and labels is None and weights is None:
-            raise ValueError('give at least one of frames, labels and weights')
-        F = [self._check(t, what, dt, ch) for t, what, dt, ch in (
-            (frames, 'frames', tuple(PIX), False), (labels, 'labels', (torch.uint8,), False),
-            (weights, 'weights', (torch.float32,), True)) if t is not None]
-        if len(set(F)) != 1:
-            raise ValueError('frames, labels and weights must hold the same number of frames, got %r' % (F,))
-        F = F[0]
-        if out is None:
-            out = (None, None, None)
-        if len(out) != 3:
-            raise ValueError('out takes the three tensors (image, onehot, weights)')
-        mean = std = None
-        if frames is not None and normalise:
-            mean, std = stats if stats is not None else self.stats(frames)
-            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == F
-                       and t.is_contiguous() for t in (mean, std)):
-                raise ValueError('stats must be the (mean, std) float32 tensors of these %d frames in GPU memory' % F)
-        o_img = self._out(out[0], count, 1, torch.float32) if frames is not None else None
-        o_hot = self._out(out[1], count, C, torch.uint8) if labels is not None else None
-        o_wts = self._out(out[2], count, 1, torch.float32) if weights is not None else None
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(_lib.load().sq_tile_sample_affine(ptr(frames), PIX[frames.dtype] if frames is not None else 0, ptr(mean),
-                                                     ptr(std), ptr(labels), ptr(weights), plan.data_ptr(), coef.data_ptr(),
-                                                     ptr(o_img), ptr(o_hot), ptr(o_wts), F, self.shape[0], self.shape[1],
-                                                     self.tile[0], self.tile[1], C, count,
-                                                     torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine')
-        return o_img, o_hot, o_wts
-
-    def _sample_mc(self, frames, labels, weights, plan, coef, C, normalise, stats, out):
         count = self._rows(plan, 'plan', 4, torch.int32)
         if self._rows(coef, 'coef', 6, torch.float32) != count:
             raise ValueError('plan has %d rows, coef %d' % (count, coef.shape[0]))
@@ -1341,9 +1185,12 @@ class TileSampler(object):
             raise ValueError('%d classes are not 1 .. 16' % C)
         if frames is None and labels is None and weights is None:
             raise ValueError('give at least one of frames, labels and weights')
-        F = [self._check(t, what, dt, ch) for t, what, dt, ch in (
+        F = []
+        if frames is not None and CI == 1:
+            F.append(self._check(frames, 'frames', tuple(PIX)))
+        F += [self._check(t, what, dt, ch) for t, what, dt, ch in (
             (labels, 'labels', (torch.uint8,), False), (weights, 'weights', (torch.float32,), True)) if t is not None]
-        if frames is not None:
+        if frames is not None and CI > 1:
             if self._tiler is None:
                 self._tiler = FrameTiler(self.shape, min(self.shape), 0, device=self.device, channels=CI)
             F.append(self._tiler._check_planes(frames))
@@ -1357,18 +1204,19 @@ class TileSampler(object):
         mean = std = None
         if frames is not None and normalise:
             mean, std = stats if stats is not None else self.stats(frames)
-            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (CI, F)
-                       and t.is_contiguous() for t in (mean, std)):
-                raise ValueError('stats must be the (mean, std) float32 tensors (%d, %d) of these frames in GPU memory' % (CI, F))
+            if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                       and (t.numel() == F if CI == 1 else tuple(t.shape) == (CI, F)) for t in (mean, std)):
+                raise ValueError('stats must be the (mean, std) float32 tensors %s in GPU memory'
+                                 % ('of these %d frames' % F if CI == 1 else '(%d, %d) of these frames' % (CI, F)))
         o_img = self._out(out[0], count, CI, torch.float32) if frames is not None else None
         o_hot = self._out(out[1], count, C, torch.uint8) if labels is not None else None
         o_wts = self._out(out[2], count, 1, torch.float32) if weights is not None else None
         ptr = lambda t: t.data_ptr() if t is not None else None
+        chan_stride = 0 if frames is None else frames.stride(0) if CI > 1 else F * self.shape[0] * self.shape[1]
         _lib.check(_lib.load().sq_tile_sample_affine_mc(
-            ptr(frames), PIX[frames.dtype] if frames is not None else 0, frames.stride(0) if frames is not None else 0,
-            ptr(mean), ptr(std), ptr(labels), ptr(weights), plan.data_ptr(), coef.data_ptr(), ptr(o_img), ptr(o_hot),
-            ptr(o_wts), F, self.shape[0], self.shape[1], CI, self.tile[0], self.tile[1], C, count,
-            torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine_mc')
+            ptr(frames), PIX[frames.dtype] if frames is not None else 0, chan_stride, ptr(mean), ptr(std), ptr(labels),
+            ptr(weights), plan.data_ptr(), coef.data_ptr(), ptr(o_img), ptr(o_hot), ptr(o_wts), F, self.shape[0], self.shape[1],
+            CI, self.tile[0], self.tile[1], C, count, torch.cuda.current_stream().cuda_stream), 'sq_tile_sample_affine_mc')
         return o_img, o_hot, o_wts
 
 

@@ -65,13 +65,15 @@ API_MODES = [("cast", False, None, mc.CAST), ("norm", True, None, mc.NORM), ("bg
 
 
 @pytest.mark.parametrize("dtype", mc.DTYPES)
-@pytest.mark.parametrize("C", [2, 3, 4, 8])
+@pytest.mark.parametrize("C", [1, 2, 3, 4, 8])
 def test_tiles_channel_c_is_the_single_channel_tiler(C, dtype):
+    """C = 1: FrameTiler(channels=1) takes the (F, H, W) stack and returns (F,) statistics and (F, 6) coefficients; it is
+    held to the numpy restatement like the others"""
     for shape, F in zip(mc.FRAME_SHAPES, (3, 1)):
         fr = mc.planes(C, F, shape, dtype, seed=10 + C)
-        x = dev(fr)
         one = single(shape)
         many = FrameTiler(shape, mc.TILE, mc.MARGIN, device=DEV, channels=C)
+        x = dev(fr) if C > 1 else dev(fr[0])
         N = F * one.TR * one.TC
         for name, normalise, clean, mode in API_MODES:
             got = many.tiles(x, normalise=normalise, clean=clean)
@@ -80,7 +82,7 @@ def test_tiles_channel_c_is_the_single_channel_tiler(C, dtype):
             assert torch.equal(got.view(torch.int32), again.view(torch.int32)), "%s: two runs differ" % name
             g = got.cpu().numpy()
             for c in range(C):
-                want = one.tiles(x[c], normalise=normalise, clean=clean).cpu().numpy()
+                want = one.tiles(x[c] if C > 1 else x, normalise=normalise, clean=clean).cpu().numpy()
                 assert_bit_exact(g[..., c], want[..., 0], "%s %s C=%d channel %d" % (name, shape, C, c))
             # the numpy restatement, from numpy's own float32 statistics or from the device's fit
             if mode in (mc.CAST, mc.NORM):
@@ -95,9 +97,9 @@ def test_tiles_channel_c_is_the_single_channel_tiler(C, dtype):
                 f32 = many.to_f32(x)
                 coef = many.background(f32)
                 m64, s64 = many.background_stats(f32, coef)
-                assert coef.shape == (C, F, 6) and m64.shape == (C, F)
-                ref = mc.np_tiles_mc(fr, [mode] * C, one.oy, one.ox, mc.TILE, coef=coef.cpu().numpy(),
-                                     mean64=m64.cpu().numpy(), std64=s64.cpu().numpy())
+                assert coef.shape == ((C, F, 6) if C > 1 else (F, 6)) and m64.shape == ((C, F) if C > 1 else (F,))
+                ref = mc.np_tiles_mc(fr, [mode] * C, one.oy, one.ox, mc.TILE, coef=coef.cpu().numpy().reshape(C, F, 6),
+                                     mean64=m64.cpu().numpy().reshape(C, F), std64=s64.cpu().numpy().reshape(C, F))
             assert_bit_exact(g, ref, "%s %s C=%d against numpy" % (name, shape, C))
 
 
@@ -197,10 +199,27 @@ def test_nothing_is_written_past_the_output(C):
     assert_bit_exact(out.cpu().numpy(), ref, "cast tiles in front of the guard")
 
 
+def single_entry(x, tl, mean=None, std=None, coef=None):
+    """sq_frames_to_tiles on one (F, H, W) stack, or sq_frames_to_tiles_bg when `coef` is given"""
+    F = int(x.shape[0])
+    out = torch.empty((F * tl.TR * tl.TC, tl.T, tl.T, 1), dtype=torch.float32, device=DEV)
+    tail = (tl._oy.data_ptr(), tl._ox.data_ptr(), out.data_ptr(), F, tl.H, tl.W, tl.TR, tl.TC, tl.T, stream())
+    lib = _lib.load()
+    if coef is None:
+        _lib.check(lib.sq_frames_to_tiles(x.data_ptr(), frontend.PIX[x.dtype], ptr(mean), ptr(std), *tail), 'sq_frames_to_tiles')
+    else:
+        _lib.check(lib.sq_frames_to_tiles_bg(x.data_ptr(), coef.data_ptr(), ptr(mean), ptr(std), *tail), 'sq_frames_to_tiles_bg')
+    return out
+
+
 @pytest.mark.parametrize("dtype", mc.DTYPES)
 def test_one_channel_is_the_single_channel_entries_byte_for_byte(dtype):
+    """C = 1 of sq_frames_to_tiles_mc, FrameTiler(channels=1) and the direct single-channel entries are one kernel; the
+    direct entries equal the numpy restatement bit for bit in all four modes, the background ones included (statistics and
+    coefficients are the device's own)"""
     for shape, F in zip(mc.FRAME_SHAPES, (3, 1)):
-        x = dev(mc.planes(1, F, shape, dtype, seed=25))
+        fr = mc.planes(1, F, shape, dtype, seed=25)
+        x = dev(fr)
         one = single(shape)
         mean, std = one.stats(x[0])
         for name, got, want in (("cast", cut(x, [mc.CAST], one), one.tiles(x[0], normalise=False)),
@@ -214,6 +233,15 @@ def test_one_channel_is_the_single_channel_entries_byte_for_byte(dtype):
         assert torch.equal(got.view(torch.int32), one.tiles(x[0], normalise=False, clean=BG).view(torch.int32)), ("bg", shape)
         got = cut(planes32, [mc.BG_NORM], one, coef=coef, mean64=m64, std64=s64)
         assert torch.equal(got.view(torch.int32), one.tiles(x[0], clean=BG).view(torch.int32)), ("bg_norm", shape)
+        # the direct entries against numpy
+        stats = dict(mean32=mean.cpu().numpy()[None], std32=std.cpu().numpy()[None], coef=coef.cpu().numpy()[None],
+                     mean64=m64.cpu().numpy()[None], std64=s64.cpu().numpy()[None])
+        for name, mode, got in (("cast", mc.CAST, single_entry(x[0], one)),
+                                ("norm", mc.NORM, single_entry(x[0], one, mean, std)),
+                                ("bg", mc.BG, single_entry(f32, one, coef=coef)),
+                                ("bg_norm", mc.BG_NORM, single_entry(f32, one, m64, s64, coef=coef))):
+            ref = mc.np_tiles_mc(fr, [mode], one.oy, one.ox, mc.TILE, **stats)
+            assert_bit_exact(got.cpu().numpy(), ref, "%s %s: the single-channel entry against numpy" % (name, shape))
 
 
 # ---- (b) the sampler ------------------------------------------------------------------------------------------------------

@@ -122,6 +122,17 @@ def test_tile_cutter_refuses_bad_arguments_without_a_device():
     assert call(F=40000, TR=60, TC=60, TS=15, chan_stride=40000 * 37 * 53) == -1 and b"out of range" in err()
 
 
+def test_single_channel_cutter_refuses_tile_rows_beyond_32_bits_without_a_device():
+    """the shared kernel indexes tile rows in 32 bits: F * TR * TC * TS beyond 2^31 - 1 is refused, not looped over"""
+    lib = _lib.load()
+    keep, p = _buf()
+    call = lambda F: lib.sq_frames_to_tiles(p, 1, p, p, p, p, p, F, 37, 53, 60, 60, 15, None)
+    assert 39769 * 60 * 60 * 15 > 2 ** 31 - 1 >= 39768 * 60 * 60 * 15
+    assert call(39769) == -1 and b"sq_frames_to_tiles: 2147526000 tile rows are out of range" in lib.sq_last_error()
+    assert lib.sq_frames_to_tiles_bg(p, p, p, p, p, p, p, 39769, 37, 53, 60, 60, 15, None) == -1
+    assert b"sq_frames_to_tiles_bg: 2147526000 tile rows are out of range" in lib.sq_last_error()
+
+
 def test_sampler_refuses_bad_arguments_without_a_device():
     lib = _lib.load()
     keep, p = _buf()
@@ -164,7 +175,7 @@ def test_geometry_does_not_depend_on_the_channels(monkeypatch):
             assert (many.TR, many.TC, many.tiles_per_frame) == (one.TR, one.TC, one.tiles_per_frame)
             for name in ('oy', 'ox', 'ymap', 'xmap'):
                 assert np.array_equal(getattr(many, name), getattr(one, name)), name
-            assert many.channels == C and many._one.channels == 1
+            assert many.channels == C
     with pytest.raises(ValueError, match='channels'):
         frontend.FrameTiler((64, 64), 32, 0, device='cuda:0', channels=9)
     with pytest.raises(ValueError, match='channels'):

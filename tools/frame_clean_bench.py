@@ -84,8 +84,8 @@ def main():
                                              tl._ox.data_ptr(), tiles_out.data_ptr(), F, H, W, tl.TR, tl.TC, TILE,
                                              torch.cuda.current_stream().cuda_stream), 'sq_frames_to_tiles_bg')
 
-    steps = {'outliers_size2': lambda: tl.outliers(raw, 2, 50., out=scratch['f32']),
-             'outliers_size3': lambda: tl.outliers(raw, 3, 50., out=scratch['f32']),
+    steps = {'outliers_size2': lambda: tl.outliers(raw, 2, 50., out=scratch['f32'][0]),   # the one channel's planes
+             'outliers_size3': lambda: tl.outliers(raw, 3, 50., out=scratch['f32'][0]),
              'fit': lambda: tl.background(f32, scratch=scratch),
              'residual_stats': lambda: tl.background_stats(f32, coef, scratch=scratch),
              'tile_kernel': tile_kernel,
