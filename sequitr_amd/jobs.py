@@ -82,7 +82,6 @@ def SERVER_segment(params, options):
     """
     import torch
     from .networks.unet import UNet2D
-    from . import utils
     from .pipeline import ImagePipeline
     from .frontend import TileStreamer
 
@@ -94,16 +93,7 @@ def SERVER_segment(params, options):
     net_p = _net_params(params, device)
     net_p.setdefault('shape', tuple(x.shape[1:3]))
     net = UNet2D(net_p, 'infer')
-    model = params.get('model')
-    if model:
-        model_dir = model if os.path.isdir(model) else utils.get_latest_model_dir(
-            os.path.join(utils.core.TensorflowConfiguration.MODELDIR, model))
-        if model_dir is None:
-            raise IOError('No saved model found for {0}'.format(model))
-        net.load_state_dict(utils.load_model_weights(model_dir))
-        logger.info('Loaded weights from {0:s}'.format(model_dir))
-    else:
-        net.initialize()
+    _load_net_weights(net, params)
 
     pipe = ImagePipeline.load(params['pipeline']) if params.get('pipeline') else None
     batch = int(params.get('batch', 32))
@@ -298,7 +288,6 @@ def SERVER_segment_volume(params, options):
         raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope")
     import torch
     from .networks.unet import UNet3D
-    from . import utils
 
     if params.get('brick') is not None:
         return _segment_volume_bricks(params, options)
@@ -312,16 +301,7 @@ def SERVER_segment_volume(params, options):
     net_p.setdefault('num_inputs', x.shape[4])
     t_setup = time.time()
     net = UNet3D(net_p, 'infer')
-    model = params.get('model')
-    if model:
-        model_dir = model if os.path.isdir(model) else utils.get_latest_model_dir(
-            os.path.join(utils.core.TensorflowConfiguration.MODELDIR, model))
-        if model_dir is None:
-            raise IOError('No saved model found for {0}'.format(model))
-        net.load_state_dict(utils.load_model_weights(model_dir))
-        logger.info('Loaded weights from {0:s}'.format(model_dir))
-    else:
-        net.initialize()
+    _load_net_weights(net, params)
     want_logits = bool(options.get('save_logits'))
     net.predict(np.ascontiguousarray(x[:1]))                    # warm-up: first-launch costs stay in the set-up time
     torch.cuda.synchronize()
@@ -502,7 +482,6 @@ def SERVER_segment_frames(params, options):
                                                             params.get('neighbor_seeds', 'objects'))
     import torch
     from .networks.unet import UNet2D
-    from . import utils
     from .frontend import segment_frames
 
     device = _resolve_device(params, options)
@@ -519,15 +498,7 @@ def SERVER_segment_frames(params, options):
     net_p.setdefault('shape', (512, 512))
     tile = int(net_p['shape'][0])
     net = UNet2D(net_p, 'infer')
-    model = params.get('model')
-    if model:
-        model_dir = model if os.path.isdir(model) else utils.get_latest_model_dir(
-            os.path.join(utils.core.TensorflowConfiguration.MODELDIR, model))
-        if model_dir is None:
-            raise IOError('No saved model found for {0}'.format(model))
-        net.load_state_dict(utils.load_model_weights(model_dir))
-    else:
-        net.initialize()
+    _load_net_weights(net, params)
     per_frame = {}
     want_measure = bool(options.get('measure')) or want_neighbors
     want_centroids = bool(options.get('centroids')) or want_measure
@@ -639,6 +610,18 @@ def _load_labels(src, key='labels'):
     return labels
 
 
+def _upload_rows(arr, shape, np_dtype, device, out=None):
+    """host array or memmap -> a device tensor of `shape` and `np_dtype` (`out` when it is given), one leading index at a
+    time: the host copies (and casts) one row at a time, never the whole stack -- arr may be a read-only memmap"""
+    import torch
+    from .frontend import NP_TORCH
+    if out is None:
+        out = torch.empty(tuple(shape), dtype=NP_TORCH[np.dtype(np_dtype)], device=device)
+    for i in range(out.shape[0]):
+        out[i].copy_(torch.from_numpy(np.array(arr[i], dtype=np_dtype, order='C')).reshape(out[i].shape))
+    return out
+
+
 class _LabelFeed(object):
     """uint8 labels (N, ...) on their way to the device: the whole stack once when it fits in `resident_bytes`, otherwise
     the rows a batch needs, through two pinned buffers, on the stream the masks are produced on"""
@@ -648,9 +631,7 @@ class _LabelFeed(object):
         from .frontend import _pinned
         self.labels, self.all = labels, None
         if labels.nbytes <= resident_bytes:
-            self.all = torch.empty(tuple(labels.shape), dtype=torch.uint8, device=device)
-            for i in range(labels.shape[0]):                    # row by row: no whole-stack host copy of a memmap
-                self.all[i].copy_(torch.from_numpy(np.array(labels[i], dtype=np.uint8, order='C')))
+            self.all = _upload_rows(labels, labels.shape, np.uint8, device)
             return
         shape = (int(rows_per_batch),) + tuple(labels.shape[1:])
         self.pinned = [_pinned('labels%d' % i, shape, torch.uint8) for i in range(2)]
@@ -817,11 +798,13 @@ def SERVER_test(params, options):
                    'options': {k: repr(v) for k, v in options.items()}}, f, indent=2)
 
 
-def _onehot(labels, num_outputs):
+def _onehot(labels, num_outputs, spatial=2):
     """class-index labels (N,H,W) -> one-hot uint8 (N,H,W,num_outputs); classes >= num_outputs get an
-    all-zero row, as tr_augment's ``concat(...)[..., :outputs]`` does (sequitr/networks/unet.py:396-398)."""
+    all-zero row, as tr_augment's ``concat(...)[..., :outputs]`` does (sequitr/networks/unet.py:396-398).  Labels with
+    one more dimension than the `spatial` ones carry a trailing class axis already and are cut to num_outputs; volumes
+    (N,Z,X,Y[,C]) are spatial = 3."""
     labels = np.asarray(labels)
-    if labels.ndim == 4:
+    if labels.ndim == spatial + 2:
         return np.ascontiguousarray(labels[..., :num_outputs], dtype=np.uint8)
     return np.stack([(labels == c) for c in range(num_outputs)], -1).astype(np.uint8)
 
@@ -887,6 +870,99 @@ class _Validator(object):
         self.log.append({'step': int(done), 'epoch': int(-(-done // self.steps_per_epoch)), 'confusion': counts.tolist(),
                          'ignored': self.meter.ignored(), 'iou': s['iou'], 'dice': s['dice'], 'accuracy': s['accuracy'],
                          'mean_iou': s['mean_iou'], 'seconds': dt})
+
+
+def _make_trainer(params, net_p, config, net_cls=None):
+    """The trainer of the four U-Net training jobs: UNetTrainer on net_p (which gains the jobs' dropout default), the
+    hyper-parameters it uses recorded in `config`, and params['warm_start'] applied"""
+    from . import utils
+    from .train import UNetTrainer
+    net_p['dropout'] = float(params.get('dropout', 0.4))
+    # learning_rate: the job's own value when it gives one; otherwise the trainer's default, NOT NetConfiguration's 0.01
+    # (sequitr/utils.py:289), which diverges on the 5-level net under Adam (train.DEFAULT_LEARNING_RATE, HISTORY.md section 8)
+    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'),
+                          net_cls=net_cls)
+    # net.config must record the hyper-parameters that were USED (it is what a warm start or an audit reads): the
+    # trainer's learning rate and warm-up, not NetConfiguration's untouched defaults
+    config.learning_rate = trainer.lr
+    config.warmup_steps = trainer.warmup_steps
+    if config.warm_start:
+        latest = config.warm_start_from()
+        if latest:
+            trainer.load_state_dict(utils.load_model_weights(latest))
+            logger.info('Warm start from {0:s}'.format(latest))
+    return trainer
+
+
+def _step_budget(params, options, config, steps_per_epoch):
+    """(epochs, total_steps): params['num_epochs'] (else the configuration's) full epochs, cut off at options['max_steps']"""
+    epochs = int(params.get('num_epochs', config.num_epochs))
+    max_steps = options.get('max_steps')
+    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    return epochs, total_steps
+
+
+def _run_steps(trainer, bufs, epochs, steps_per_epoch, total_steps, begin_epoch, fill, use_graph, validator, dev):
+    """The loop of the four U-Net training jobs -> (losses, steps done, seconds, ms_per_step, steady_steps).
+
+    begin_epoch(epoch) makes an epoch's state (its permutation or sampling plan: the job's one random draw per epoch, never
+    made in an epoch that total_steps cuts off) and fill(state, s, bufs) writes step s's batch into the list `bufs` (image,
+    one-hot labels, weights).  With use_graph the first step runs eagerly (it warms every kernel up and sizes the
+    workspaces), then the step is captured -- (zero, forward, loss, backward) + (Adam), the all-reduce between them -- and
+    `bufs` is rebound IN PLACE to the capture's static inputs, so that later batches are written straight into them and
+    step() has nothing to copy.  The loss of every step lands in a device-side log that is read back once, at the end (no
+    per-step .item(): the host runs ahead of the GPU).  ms_per_step is the steady state: the first step carries the
+    first-launch costs (and the capture) and is left out, as are the validator's seconds, all of which fall after it."""
+    import torch
+    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    done = 0
+    t_start = t_steady = time.time()
+    for epoch in range(epochs):
+        if done >= total_steps:
+            break
+        state = begin_epoch(epoch)
+        for s in range(steps_per_epoch):
+            if done >= total_steps:
+                break
+            fill(state, s, bufs)
+            if use_graph and done == 0:
+                trainer.capture(*bufs, warmup=1)
+                bufs[:] = trainer.static_inputs
+                loss_log[0].copy_(trainer.last_loss)
+            else:
+                loss_log[done].copy_(trainer.step(*bufs))
+            done += 1
+            if done == 1:
+                torch.cuda.synchronize()
+                t_steady = time.time()
+            if validator is not None:
+                validator.after_step(done)
+    torch.cuda.synchronize()
+    t_end = time.time()
+    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
+    steady = max(done - 1, 0)
+    val_seconds = validator.seconds if validator is not None else 0.0
+    return (losses, done, t_end - t_start, (t_end - t_steady - val_seconds) * 1e3 / steady if steady > 0 else None, steady)
+
+
+def _finish_training(params, config, trainer, validator, run, batch, path_info, use_graph, dtype, device, message,
+                     after=None, world=1, rank=0):
+    """What follows the loop in the four U-Net training jobs -> info.  `run` is what _run_steps returned; the job's own
+    keys are path_info (they go between batch_size and graph) and `after` (behind device).  Rank 0 saves the model, writes
+    train.json (info, losses and the validation log) and logs `message`."""
+    from . import utils
+    losses, done, seconds, ms_per_step, steady = run
+    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
+            'seconds': seconds, 'ms_per_step': ms_per_step, 'steady_steps': steady, 'batch_size': batch, **path_info,
+            'graph': use_graph, 'dtype': dtype, 'warmup_steps': trainer.warmup_steps, 'learning_rate': trainer.lr,
+            'world': world, 'device': device, **(after or {})}
+    if rank == 0:
+        info['model_dir'] = utils.save_model(trainer.state_dict(), config)
+        extra = {'validation': validator.log} if validator is not None else {}
+        with open(os.path.join(params['output'], 'train.json'), 'w') as f:
+            json.dump(dict(info, losses=losses, **extra), f, indent=2)
+        logger.info(message.format(**info))
+    return info
 
 
 def _train_frame_tiles(params, options):
@@ -966,7 +1042,6 @@ def _train_frame_tiles(params, options):
     import torch
     from . import utils
     from .frontend import TileSampler
-    from .train import UNetTrainer
     from .weightmap import device_weightmaps
 
     cfg_keys = ('name', 'num_outputs', 'num_epochs', 'learning_rate', 'warm_start', 'dropout')
@@ -978,30 +1053,22 @@ def _train_frame_tiles(params, options):
     torch.cuda.set_device(torch.device(device))
     dev = torch.device(device)
 
-    def upload(arr, np_dtype):
-        """host array or memmap -> HBM as it is, one frame at a time (no whole-stack host copy)"""
-        t = torch.empty((F, H, W), dtype=NP_TORCH[np.dtype(np_dtype)], device=dev)
-        for i in range(F):
-            t[i].copy_(torch.from_numpy(np.array(arr[i], dtype=np_dtype, order='C')))   # a copy: arr is a read-only memmap
-        return t
-
     net_p = _net_params(params, device)
     net_p['shape'] = (th, tw)
     net_p['num_inputs'], net_p['num_outputs'] = CI, n_out
-    net_p['dropout'] = float(params.get('dropout', 0.4))
     # before any upload: a trainer that does not take this many input channels says so itself
-    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'))
+    trainer = _make_trainer(params, net_p, config)
 
     if CI == 1:
-        x_dev = upload(x, x.dtype)
+        x_dev = _upload_rows(x, (F, H, W), x.dtype, dev)
     else:                                                      # channel-major planes, resident: (C, F, H, W), plane by plane
         x_dev = torch.empty((CI, F, H, W), dtype=NP_TORCH[np.dtype(x.dtype)], device=dev)
         for c, plane in enumerate(x_planes):
-            for i in range(F):
-                x_dev[c, i].copy_(torch.from_numpy(np.array(plane[i], dtype=x.dtype, order='C')))
-    y_dev = upload(labels, np.uint8)
+            _upload_rows(plane, (F, H, W), x.dtype, dev, out=x_dev[c])
+    y_dev = _upload_rows(labels, (F, H, W), np.uint8, dev)
     if params.get('weights'):
-        w_dev = upload(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((F, H, W)), np.float32)
+        w_dev = _upload_rows(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((F, H, W)), (F, H, W),
+                             np.float32, dev)
     else:
         # once, on the whole frames; the rotation then interpolates the map, as the reference rotates its precomputed TIFFs
         w_dev = device_weightmaps(y_dev, params.get('w0', 10.), params.get('sigma', 5.))
@@ -1009,24 +1076,13 @@ def _train_frame_tiles(params, options):
     normalise = bool(params.get('normalise', True))
     stats = sampler.stats(x_dev) if normalise else None         # ImageNorm of each WHOLE frame, as segment_frames applies it
 
-    config.learning_rate = trainer.lr
-    config.warmup_steps = trainer.warmup_steps
-    if config.warm_start:
-        latest = config.warm_start_from()
-        if latest:
-            trainer.load_state_dict(utils.load_model_weights(latest))
-            logger.info('Warm start from {0:s}'.format(latest))
-
     batch = max(1, min(int(params.get('batch_size', 16)), samples))
     steps_per_epoch = samples // batch
-    epochs = int(params.get('num_epochs', config.num_epochs))
-    max_steps = options.get('max_steps')
-    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    epochs, total_steps = _step_budget(params, options, config, steps_per_epoch)
     bufs = [torch.empty((batch, th, tw, CI), dtype=torch.float32, device=dev),
             torch.empty((batch, th, tw, n_out), dtype=torch.uint8, device=dev),
             torch.empty((batch, th, tw, 1), dtype=torch.float32, device=dev)]
     use_graph = bool(options.get('graph', True))
-    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
     validator = None
     if want_val:
         from .frontend import segment_frames
@@ -1038,50 +1094,22 @@ def _train_frame_tiles(params, options):
                            on_masks=lambda first, m: meter.update(m, val_feed.get(first, m.shape[0])), normalise=normalise)
 
         validator = _Validator(trainer, net_p, run_val, steps_per_epoch, validate_every, total_steps)
-    done, steady_from = 0, 0
-    t_start = t_steady = time.time()
-    for epoch in range(epochs):
-        if done >= total_steps:
-            break
-        plan, coef = (torch.from_numpy(a).to(dev) for a in tile_sample_plan((H, W), (th, tw), F, samples, rng, augment))
-        for s in range(steps_per_epoch):                       # ONE plan upload per epoch; a step takes a slice of it
-            if done >= total_steps:
-                break
-            sl = slice(s * batch, (s + 1) * batch)
-            sampler.sample(x_dev, y_dev, w_dev, plan[sl], coef[sl], n_out, normalise=normalise, stats=stats, out=bufs)
-            if use_graph and done == 0:
-                # as SERVER_train's tile path: the first step is eager, then the step is captured and the sampler writes
-                # straight into the capture's static input buffers
-                trainer.capture(*bufs, warmup=1)
-                bufs[:] = trainer.static_inputs
-                loss_log[0].copy_(trainer.last_loss)
-            else:
-                loss_log[done].copy_(trainer.step(*bufs))
-            done += 1
-            if done == 1:                                      # the first step carries the first-launch costs
-                torch.cuda.synchronize()
-                t_steady, steady_from = time.time(), 1
-            if validator is not None:
-                validator.after_step(done)
-    torch.cuda.synchronize()
-    t_end = time.time()
-    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
-    steady = done - steady_from
-    val_seconds = validator.seconds if validator is not None else 0.0      # all of it falls after t_steady
-    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
-            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady - val_seconds) * 1e3 / steady if steady > 0 else None,
-            'steady_steps': steady, 'batch_size': batch, 'frames': F, 'frame_shape': [H, W], 'tile': [th, tw],
-            **({'channels': CI} if CI > 1 else {}),
-            'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed, 'normalise': normalise,
-            'graph': use_graph, 'dtype': str(net_p.get('dtype', 'f32')), 'warmup_steps': trainer.warmup_steps,
-            'learning_rate': trainer.lr, 'world': 1, 'device': device}
-    info['model_dir'] = utils.save_model(trainer.state_dict(), config)
-    extra = {'validation': validator.log} if validator is not None else {}
-    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
-        json.dump(dict(info, losses=losses, **extra), f, indent=2)
-    logger.info('Trained {steps} steps on rotated tiles of whole frames, loss {first_loss} -> {last_loss}, saved '
-                '{model_dir}'.format(**info))
-    return info
+
+    def begin_epoch(epoch):                                    # ONE plan upload per epoch; a step takes a slice of it
+        return [torch.from_numpy(a).to(dev) for a in tile_sample_plan((H, W), (th, tw), F, samples, rng, augment)]
+
+    def fill(state, s, bufs):
+        plan, coef = state
+        sl = slice(s * batch, (s + 1) * batch)
+        sampler.sample(x_dev, y_dev, w_dev, plan[sl], coef[sl], n_out, normalise=normalise, stats=stats, out=bufs)
+
+    run = _run_steps(trainer, bufs, epochs, steps_per_epoch, total_steps, begin_epoch, fill, use_graph, validator, dev)
+    return _finish_training(
+        params, config, trainer, validator, run, batch,
+        {'frames': F, 'frame_shape': [H, W], 'tile': [th, tw], **({'channels': CI} if CI > 1 else {}),
+         'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed, 'normalise': normalise},
+        use_graph, str(net_p.get('dtype', 'f32')), device,
+        'Trained {steps} steps on rotated tiles of whole frames, loss {first_loss} -> {last_loss}, saved {model_dir}')
 
 
 def SERVER_train(params, options):
@@ -1100,9 +1128,11 @@ def SERVER_train(params, options):
     The data path of a step never leaves the device: tiles, one-hot labels and weight maps are uploaded ONCE and stay
     in HBM (2.6 MB per 512x512 tile against 288 GB; a stack above params['resident_gib'], default 64, is staged batch by
     batch through pinned memory instead), an epoch's permutation is one index tensor, a batch is an index_select
-    straight into the captured step's static input buffers, the loss of every step lands in a device-side log that
-    is read back once per epoch (no per-step .item(): the host runs ahead of the GPU).  Under torchrun
-    (WORLD_SIZE > 1) the tiles shard across ranks and gradients are all-reduced over RCCL once per step, between
+    straight into the captured step's static input buffers.  The loop is _run_steps, which the frame path and both
+    SERVER_train_volume paths share: the loss of every step lands in a device-side log that is read back once, after the
+    last step (no per-step .item(): the host runs ahead of the GPU), and ms_per_step / steady_steps leave the first step
+    out -- it carries the first-launch costs and, with `graph`, the capture -- whether or not the step is captured.
+    Under torchrun (WORLD_SIZE > 1) the tiles shard across ranks and gradients are all-reduced over RCCL once per step, between
     the two graphs.  Rank 0 saves ``weights.npz`` + ``net.config`` into the next numbered folder of MODELDIR/<name>/
     (sequitr/utils.py:143-223 layout) and ``train.json`` (losses, ms_per_step) into params['output'].
 
@@ -1132,7 +1162,6 @@ def SERVER_train(params, options):
     from . import utils
     from .parallel import epoch_schedule
     from .weightmap import device_weightmaps
-    from .train import UNetTrainer
 
     want_val, validate_every = _validation_keys(params)
     device = _resolve_device(params, options)
@@ -1162,19 +1191,7 @@ def SERVER_train(params, options):
 
     net_p = _net_params(params, device)
     net_p.setdefault('shape', tuple(x.shape[1:3]))
-    net_p['dropout'] = float(params.get('dropout', 0.4))
-    # learning_rate: the job's own value when it gives one; otherwise the trainer's default, NOT NetConfiguration's 0.01
-    # (sequitr/utils.py:289), which diverges on the 5-level net under Adam (train.DEFAULT_LEARNING_RATE, HISTORY.md section 8)
-    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'))
-    # net.config must record the hyper-parameters that were USED (it is what a warm start or an audit reads): the
-    # trainer's learning rate and warm-up, not NetConfiguration's untouched defaults
-    config.learning_rate = trainer.lr
-    config.warmup_steps = trainer.warmup_steps
-    if config.warm_start:
-        latest = config.warm_start_from()
-        if latest:
-            trainer.load_state_dict(utils.load_model_weights(latest))
-            logger.info('Warm start from {0:s}'.format(latest))
+    trainer = _make_trainer(params, net_p, config)
 
     # Every rank must issue the SAME number of optimiser steps (each one is a gradient all-reduce), so the step count
     # comes from rank-independent quantities only and every step is a full batch: one seeded permutation of the whole
@@ -1185,9 +1202,7 @@ def SERVER_train(params, options):
     if order_fn.dropped:
         logger.info('{0} of {1} tiles are left out of every epoch ({2} ranks x {3} steps x batch {4}; a different '
                     'remainder each epoch)'.format(order_fn.dropped, n_items, world, steps_per_epoch, batch))
-    epochs = int(params.get('num_epochs', config.num_epochs))
-    max_steps = options.get('max_steps')
-    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    epochs, total_steps = _step_budget(params, options, config, steps_per_epoch)
 
     per_tile = int(np.prod(x.shape[1:])) * 4 + int(np.prod(onehot.shape[1:])) + int(np.prod(onehot.shape[1:3])) * 4
     resident = n_items * per_tile <= float(params.get('resident_gib', 64)) * 2 ** 30
@@ -1200,15 +1215,22 @@ def SERVER_train(params, options):
             torch.empty((batch,) + tuple(onehot.shape[1:]), dtype=torch.uint8, device=dev),
             torch.empty((batch,) + tuple(onehot.shape[1:3]) + (1,), dtype=torch.float32, device=dev)]
 
-    def load_batch(idx_dev, idx_host):
-        """fill the step's static input buffers with the tiles `idx` (device gather, or pinned staging)"""
+    def begin_epoch(epoch):                                    # the epoch's permutation: on the host, and one index tensor
+        order = order_fn(epoch, rank)
+        return order, torch.from_numpy(np.ascontiguousarray(order)).to(dev) if resident else None
+
+    def fill(state, s, bufs):
+        """fill the step's static input buffers with the tiles of step s (device gather, or pinned staging)"""
+        order, order_dev = state
+        sl = slice(s * batch, (s + 1) * batch)
         sx, sy, sw = bufs
         if resident:
-            torch.index_select(x_dev, 0, idx_dev, out=sx)
-            torch.index_select(y_dev, 0, idx_dev, out=sy)
-            torch.index_select(w_dev, 0, idx_dev, out=sw)
+            idx = order_dev[sl]
+            torch.index_select(x_dev, 0, idx, out=sx)
+            torch.index_select(y_dev, 0, idx, out=sy)
+            torch.index_select(w_dev, 0, idx, out=sw)
         else:
-            ih = np.asarray(idx_host)                            # the permutation's own order: the same batch as the resident path
+            ih = np.asarray(order[sl])                           # the permutation's own order: the same batch as the resident path
             sx.copy_(torch.from_numpy(np.ascontiguousarray(x[ih], dtype=np.float32)).pin_memory(), non_blocking=True)
             sy.copy_(torch.from_numpy(np.ascontiguousarray(onehot[ih])).pin_memory(), non_blocking=True)
             if isinstance(wmap, torch.Tensor):
@@ -1217,7 +1239,6 @@ def SERVER_train(params, options):
                 sw.copy_(torch.from_numpy(np.ascontiguousarray(wmap[ih])).pin_memory(), non_blocking=True)
 
     use_graph = bool(options.get('graph', True))
-    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
     validator = None
     if want_val:                                               # tiles and labels in the formats of `images` and `labels`
         vx = np.load(params['val_images'], mmap_mode='r', allow_pickle=False)
@@ -1237,65 +1258,25 @@ def SERVER_train(params, options):
                 meter.update(net.predict(vx_dev[i:i + val_batch]).contiguous(), vy_dev[i:i + val_batch])
 
         validator = _Validator(trainer, net_p, run_val, steps_per_epoch, validate_every, total_steps)
-    losses, done = [], 0
-    t_start = t_steady = time.time()
-    steady_from = 0
-    for epoch in range(epochs):
-        if done >= total_steps:
-            break
-        order = order_fn(epoch, rank)
-        order_dev = torch.from_numpy(np.ascontiguousarray(order)).to(dev) if resident else None
-        first = done
-        for s in range(steps_per_epoch):
-            if done >= total_steps:
-                break
-            sl = slice(s * batch, (s + 1) * batch)
-            load_batch(order_dev[sl] if resident else None, order[sl])
-            if use_graph and done == 0:
-                # the first step runs eagerly (it warms every kernel up and sizes the workspaces), then the step is
-                # captured: (zero, forward, loss, backward) + (Adam), all-reduce between them; later batches are
-                # gathered straight into the capture's static buffers, so step() has nothing to copy
-                trainer.capture(*bufs, warmup=1)
-                bufs[:] = trainer.static_inputs
-                loss_log[0].copy_(trainer.last_loss)
-                torch.cuda.synchronize()
-                t_steady, steady_from = time.time(), 1         # ms_per_step is the replayed steady state
-            else:
-                loss_log[done].copy_(trainer.step(*bufs))
-            done += 1
-            if validator is not None:
-                validator.after_step(done)
-        losses.extend(float(v) for v in loss_log[first:done].cpu().numpy())      # ONE read-back per epoch
-    torch.cuda.synchronize()
-    t_end = time.time()
-    steady = done - steady_from
-    val_seconds = validator.seconds if validator is not None else 0.0      # all of it falls after t_steady
-    info = {'steps': done, 'first_loss': losses[0], 'last_loss': losses[-1], 'seconds': t_end - t_start,
-            'ms_per_step': (t_end - t_steady - val_seconds) * 1e3 / steady if steady > 0 else None,
-            'steady_steps': steady, 'batch_size': batch, 'tiles': n_items, 'resident': bool(resident),
-            'graph': use_graph, 'dtype': str(net_p.get('dtype', 'f32')), 'warmup_steps': trainer.warmup_steps,
-            'learning_rate': trainer.lr, 'world': world, 'device': device}
+    run = _run_steps(trainer, bufs, epochs, steps_per_epoch, total_steps, begin_epoch, fill, use_graph, validator, dev)
     # replica check: data-parallel replicas apply the same all-reduced gradient to the same weights, so their
     # parameters must agree bit for bit; two f64 sums of the flat parameter bucket are compared across the ranks
     flat = trainer.pbucket.flat.double()
     chk = torch.stack([flat.sum(), flat.abs().sum()])
-    info['param_checksum'] = [float(v) for v in chk.cpu()]
+    check = {'param_checksum': [float(v) for v in chk.cpu()]}
     if world > 1:
         import torch.distributed as dist
         hi, lo = chk.clone(), chk.clone()
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-        info['replicas_identical'] = bool(torch.equal(hi, lo))
-        if not info['replicas_identical']:
+        check['replicas_identical'] = bool(torch.equal(hi, lo))
+        if not check['replicas_identical']:
             logger.error('data-parallel replicas have diverged: parameter checksums span {0} .. {1}'.format(
                 [float(v) for v in lo.cpu()], [float(v) for v in hi.cpu()]))
-    if rank == 0:
-        info['model_dir'] = utils.save_model(trainer.state_dict(), config)
-        extra = {'validation': validator.log} if validator is not None else {}
-        with open(os.path.join(params['output'], 'train.json'), 'w') as f:
-            json.dump(dict(info, losses=losses, **extra), f, indent=2)
-        logger.info('Trained {steps} steps, loss {first_loss:.4f} -> {last_loss:.4f}, saved {model_dir}'.format(**info))
-    return info
+    return _finish_training(params, config, trainer, validator, run, batch, {'tiles': n_items, 'resident': bool(resident)},
+                            use_graph, str(net_p.get('dtype', 'f32')), device,
+                            'Trained {steps} steps, loss {first_loss:.4f} -> {last_loss:.4f}, saved {model_dir}',
+                            after=check, world=world, rank=rank)
 
 
 def _train_volume_bricks(params, options):
@@ -1305,7 +1286,6 @@ def _train_volume_bricks(params, options):
     from . import utils
     from .frontend import NP_TORCH, VolumeSampler, sample_plan, volume_bricks, volume_stats
     from .networks.unet import UNet3DTrain
-    from .train import UNetTrainer
 
     wm_kind = params.get('weightmap', 'uniform')
     wm_w0, wm_sigma, wm_spacing = float(params.get('w0', 10.)), float(params.get('sigma', 5.)), float(params.get('spacing', 1.))
@@ -1346,18 +1326,12 @@ def _train_volume_bricks(params, options):
     torch.cuda.set_device(torch.device(device))
     dev = torch.device(device)
 
-    def upload(arr, np_dtype, tail=()):
-        """host array or memmap -> HBM as it is, one volume at a time (no whole-stack host copy)"""
-        t = torch.empty((N, Z, X, Y) + tuple(tail), dtype=NP_TORCH[np.dtype(np_dtype)], device=dev)
-        for i in range(N):
-            t[i].copy_(torch.from_numpy(np.ascontiguousarray(arr[i], dtype=np_dtype)).reshape(t[i].shape))
-        return t
-
-    x_dev = upload(x, x.dtype)
+    x_dev = _upload_rows(x, (N, Z, X, Y), x.dtype, dev)
     index_labels = labels.ndim == 4                             # class indices stay at one byte per voxel
-    y_dev = upload(labels, np.uint8, () if index_labels else (n_out,))
+    y_dev = _upload_rows(labels, (N, Z, X, Y) if index_labels else (N, Z, X, Y, n_out), np.uint8, dev)
     if params.get('weights'):
-        w_dev = upload(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((N, Z, X, Y)), np.float32, (1,))
+        w_dev = _upload_rows(np.load(params['weights'], mmap_mode='r', allow_pickle=False).reshape((N, Z, X, Y)),
+                             (N, Z, X, Y, 1), np.float32, dev)
     elif wm_kind == 'edt':
         # once, on the whole volumes: crop and symmetry commute with the map (the spacing is along z, which no op mixes
         # with x or y)
@@ -1378,64 +1352,36 @@ def _train_volume_bricks(params, options):
     net_p = _net_params(params, device)
     net_p['shape'] = (bx, by, bz)
     net_p['num_inputs'], net_p['num_outputs'] = 1, n_out
-    net_p['dropout'] = float(params.get('dropout', 0.4))
-    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'),
-                          net_cls=UNet3DTrain)
-    config.learning_rate = trainer.lr
-    config.warmup_steps = trainer.warmup_steps
-    if config.warm_start:
-        latest = config.warm_start_from()
-        if latest:
-            trainer.load_state_dict(utils.load_model_weights(latest))
-            logger.info('Warm start from {0:s}'.format(latest))
+    trainer = _make_trainer(params, net_p, config, UNet3DTrain)
 
     batch = max(1, min(int(params.get('batch_size', 1)), samples))
     steps_per_epoch = samples // batch
-    epochs = int(params.get('num_epochs', config.num_epochs))
-    max_steps = options.get('max_steps')
-    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    epochs, total_steps = _step_budget(params, options, config, steps_per_epoch)
     sampler = VolumeSampler((Z, X, Y), (bz, bx, by), dev)
-    bufs = (torch.empty((batch, bz, bx, by, 1), dtype=torch.float32, device=dev),
+    bufs = [torch.empty((batch, bz, bx, by, 1), dtype=torch.float32, device=dev),
             torch.empty((batch, bz, bx, by, n_out), dtype=torch.uint8, device=dev),
-            torch.empty((batch, bz, bx, by, 1), dtype=torch.float32, device=dev))
-    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
-    done = 0
-    t_start = t_steady = time.time()
-    for epoch in range(epochs):
-        if done >= total_steps:
-            break
-        plan = torch.from_numpy(sample_plan((Z, X, Y), (bz, bx, by), N, samples, rng, augment)).to(dev)   # ONE upload per epoch
-        for s in range(steps_per_epoch):
-            if done >= total_steps:
-                break
-            rows = plan[s * batch:(s + 1) * batch]
-            sampler.images(x_dev, rows, normalise=normalise, stats=stats, out=bufs[0])
-            if index_labels:
-                sampler.onehot(y_dev, n_out, rows, out=bufs[1])
-            else:
-                sampler.copy(y_dev, rows, out=bufs[1])
-            sampler.copy(w_dev, rows, out=bufs[2])
-            loss_log[done].copy_(trainer.step(*bufs))
-            done += 1
-            if done == 1:                                      # the first step carries the first-launch costs
-                torch.cuda.synchronize()
-                t_steady = time.time()
-    torch.cuda.synchronize()
-    t_end = time.time()
-    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
-    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
-            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady) * 1e3 / (done - 1) if done > 1 else None,
-            'steady_steps': max(done - 1, 0), 'batch_size': batch, 'volumes': N, 'shape': [Z, X, Y],
-            'brick': [bx, by, bz], 'augment': list(augment), 'samples_per_epoch': samples, 'seed': seed,
-            'normalise': normalise, 'graph': False, 'dtype': 'f32', 'warmup_steps': trainer.warmup_steps,
-            'learning_rate': trainer.lr, 'world': 1, 'device': device}
-    if wm_kind == 'edt' and not params.get('weights'):
-        info.update(weightmap='edt', w0=wm_w0, sigma=wm_sigma, spacing=wm_spacing)
-    info['model_dir'] = utils.save_model(trainer.state_dict(), config)
-    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
-        json.dump(dict(info, losses=losses), f, indent=2)
-    logger.info('Trained {steps} steps on bricks of volumes, loss {first_loss} -> {last_loss}, saved {model_dir}'.format(**info))
-    return info
+            torch.empty((batch, bz, bx, by, 1), dtype=torch.float32, device=dev)]
+
+    def begin_epoch(epoch):                                    # ONE plan upload per epoch; a step takes a slice of it
+        return torch.from_numpy(sample_plan((Z, X, Y), (bz, bx, by), N, samples, rng, augment)).to(dev)
+
+    def fill(plan, s, bufs):
+        rows = plan[s * batch:(s + 1) * batch]
+        sampler.images(x_dev, rows, normalise=normalise, stats=stats, out=bufs[0])
+        if index_labels:
+            sampler.onehot(y_dev, n_out, rows, out=bufs[1])
+        else:
+            sampler.copy(y_dev, rows, out=bufs[1])
+        sampler.copy(w_dev, rows, out=bufs[2])
+
+    run = _run_steps(trainer, bufs, epochs, steps_per_epoch, total_steps, begin_epoch, fill, False, None, dev)
+    edt = wm_kind == 'edt' and not params.get('weights')
+    return _finish_training(
+        params, config, trainer, None, run, batch,
+        {'volumes': N, 'shape': [Z, X, Y], 'brick': [bx, by, bz], 'augment': list(augment), 'samples_per_epoch': samples,
+         'seed': seed, 'normalise': normalise}, False, 'f32', device,
+        'Trained {steps} steps on bricks of volumes, loss {first_loss} -> {last_loss}, saved {model_dir}',
+        after=dict(weightmap='edt', w0=wm_w0, sigma=wm_sigma, spacing=wm_spacing) if edt else None)
 
 
 def SERVER_train_volume(params, options):
@@ -1451,7 +1397,9 @@ def SERVER_train_volume(params, options):
     1), warmup_steps.  Learning-rate defaults are the trainer's (train.DEFAULT_LEARNING_RATE ramped over
     train.DEFAULT_WARMUP_STEPS), as in SERVER_train.  options: gpu, max_steps.
 
-    Single process, eager steps: the volumes, labels and weights are uploaded once, a batch is an index_select.  Writes
+    Single process, eager steps: the volumes, labels and weights are uploaded once, a batch is an index_select into the
+    step's three input buffers.  The loop is _run_steps, SERVER_train's (there: what ms_per_step leaves out and when the
+    losses are read back); both paths here run it without capture and without validation.  Writes
     ``weights.npz`` + ``net.config`` into the next numbered folder of MODELDIR/<name>/ and ``train.json`` (losses,
     ms_per_step) into params['output'].  The model loads strictly into UNet3D (SERVER_segment_volume's ``model``).
 
@@ -1471,7 +1419,6 @@ def SERVER_train_volume(params, options):
     import torch
     from . import utils
     from .networks.unet import UNet3DTrain
-    from .train import UNetTrainer
 
     if int(os.environ.get('WORLD_SIZE', 1)) > 1:
         raise RuntimeError('SERVER_train_volume runs in a single process (data-parallel volume training does not exist)')
@@ -1496,10 +1443,7 @@ def SERVER_train_volume(params, options):
     cfg.setdefault('num_inputs', int(C))
     config = utils.NetConfiguration.from_params(cfg)
     labels = np.load(params['labels'], allow_pickle=False)
-    if labels.ndim == 5:
-        onehot = np.ascontiguousarray(labels[..., :config.num_outputs], dtype=np.uint8)
-    else:
-        onehot = np.stack([(labels == c) for c in range(config.num_outputs)], -1).astype(np.uint8)
+    onehot = _onehot(labels, config.num_outputs, spatial=3)
     if tuple(onehot.shape[:4]) != (N, Z, X, Y):
         raise ValueError('labels %s do not match the images %s' % (labels.shape, x.shape))
     if params.get('weights'):
@@ -1513,58 +1457,31 @@ def SERVER_train_volume(params, options):
     net_p = _net_params(params, device)
     net_p['shape'] = tuple(config.shape)
     net_p['num_inputs'], net_p['num_outputs'] = int(config.num_inputs), int(config.num_outputs)
-    net_p['dropout'] = float(params.get('dropout', 0.4))
-    trainer = UNetTrainer(net_p, learning_rate=params.get('learning_rate'), warmup_steps=params.get('warmup_steps'),
-                          net_cls=UNet3DTrain)
-    config.learning_rate = trainer.lr                          # net.config records what was used
-    config.warmup_steps = trainer.warmup_steps
-    if config.warm_start:
-        latest = config.warm_start_from()
-        if latest:
-            trainer.load_state_dict(utils.load_model_weights(latest))
-            logger.info('Warm start from {0:s}'.format(latest))
+    trainer = _make_trainer(params, net_p, config, UNet3DTrain)
 
     batch = max(1, min(int(params.get('batch_size', 1)), N))
     steps_per_epoch = N // batch
-    epochs = int(params.get('num_epochs', config.num_epochs))
-    max_steps = options.get('max_steps')
-    total_steps = epochs * steps_per_epoch if not max_steps else min(int(max_steps), epochs * steps_per_epoch)
+    epochs, total_steps = _step_budget(params, options, config, steps_per_epoch)
     x_dev = torch.from_numpy(np.array(x, dtype=np.float32, order='C')).to(dev)
     y_dev = torch.from_numpy(np.ascontiguousarray(onehot)).to(dev)
     w_dev = wmap if isinstance(wmap, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(wmap)).to(dev)
-    loss_log = torch.zeros(max(total_steps, 1), dtype=torch.float32, device=dev)
+    bufs = [torch.empty((batch,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in (x_dev, y_dev, w_dev)]
     rng = np.random.default_rng(int(params.get('seed', 0)))
-    done = 0
-    t_start = t_steady = time.time()
-    for epoch in range(epochs):
-        if done >= total_steps:
-            break
-        order = torch.from_numpy(rng.permutation(N)).to(dev)
-        for s in range(steps_per_epoch):
-            if done >= total_steps:
-                break
-            idx = order[s * batch:(s + 1) * batch]
-            loss_log[done].copy_(trainer.step(x_dev.index_select(0, idx), y_dev.index_select(0, idx),
-                                              w_dev.index_select(0, idx)))
-            done += 1
-            if done == 1:                                      # the first step carries the first-launch costs
-                torch.cuda.synchronize()
-                t_steady = time.time()
-    torch.cuda.synchronize()
-    t_end = time.time()
-    losses = [float(v) for v in loss_log[:done].cpu().numpy()]
-    info = {'steps': done, 'first_loss': losses[0] if losses else None, 'last_loss': losses[-1] if losses else None,
-            'seconds': t_end - t_start, 'ms_per_step': (t_end - t_steady) * 1e3 / (done - 1) if done > 1 else None,
-            'steady_steps': max(done - 1, 0), 'batch_size': batch, 'volumes': int(N), 'shape': [int(Z), int(X), int(Y)],
-            'graph': False, 'dtype': 'f32', 'warmup_steps': trainer.warmup_steps, 'learning_rate': trainer.lr,
-            'world': 1, 'device': device}
-    if wm_kind == 'edt' and not params.get('weights'):
-        info.update(weightmap='edt', w0=wm_w0, sigma=wm_sigma, spacing=wm_spacing)
-    info['model_dir'] = utils.save_model(trainer.state_dict(), config)
-    with open(os.path.join(params['output'], 'train.json'), 'w') as f:
-        json.dump(dict(info, losses=losses), f, indent=2)
-    logger.info('Trained {steps} steps on volumes, loss {first_loss} -> {last_loss}, saved {model_dir}'.format(**info))
-    return info
+
+    def begin_epoch(epoch):                                    # the epoch's permutation, one index tensor
+        return torch.from_numpy(rng.permutation(N)).to(dev)
+
+    def fill(order, s, bufs):
+        idx = order[s * batch:(s + 1) * batch]
+        for t, out in zip((x_dev, y_dev, w_dev), bufs):
+            torch.index_select(t, 0, idx, out=out)
+
+    run = _run_steps(trainer, bufs, epochs, steps_per_epoch, total_steps, begin_epoch, fill, False, None, dev)
+    edt = wm_kind == 'edt' and not params.get('weights')
+    return _finish_training(params, config, trainer, None, run, batch,
+                            {'volumes': int(N), 'shape': [int(Z), int(X), int(Y)]}, False, 'f32', device,
+                            'Trained {steps} steps on volumes, loss {first_loss} -> {last_loss}, saved {model_dir}',
+                            after=dict(weightmap='edt', w0=wm_w0, sigma=wm_sigma, spacing=wm_spacing) if edt else None)
 
 
 GAN_KEYS = ('num_outputs', 'batch_size', 'repeat_batch', 'num_levels', 'num_epochs_per_level', 'start_size', 'learning_rate',

@@ -129,6 +129,38 @@ def test_net_configuration_surface(tmp_path, monkeypatch):
     assert c3.warm_start_from() == d2
 
 
+def test_onehot_takes_index_and_onehot_labels_of_tiles_and_volumes():
+    """jobs._onehot against the expressions the training jobs spelled out before they shared it: index labels are
+    expanded class by class (a class >= num_outputs gives an all-zero row), labels that carry a class axis are cut to
+    num_outputs; volumes are told from one-hot tiles by `spatial`."""
+    from sequitr_amd import jobs
+    rng = np.random.default_rng(3)
+    n_out = 2
+    for spatial, shape in ((2, (3, 5, 7)), (3, (2, 3, 5, 7))):
+        idx = rng.integers(0, 4, shape).astype(np.uint8)                   # classes 2 and 3 are >= num_outputs
+        idx.flat[0] = 3
+        want = np.stack([(idx == c) for c in range(n_out)], -1).astype(np.uint8)
+        got = jobs._onehot(idx, n_out, spatial=spatial)
+        assert got.dtype == np.uint8 and got.shape == shape + (n_out,) and np.array_equal(got, want)
+        assert not got.reshape(-1, n_out)[0].any() and not got[idx >= n_out].any()
+        wide = rng.integers(0, 2, shape + (4,)).astype(np.int64)           # one-hot labels wider than num_outputs
+        want = np.ascontiguousarray(wide[..., :n_out], dtype=np.uint8)
+        got = jobs._onehot(wide, n_out, spatial=spatial)
+        assert got.dtype == np.uint8 and got.flags.c_contiguous and np.array_equal(got, want)
+    four = np.ones((1, 2, 2, 3), np.uint8)                                 # tiles are the default: one-hot (N,H,W,C) ...
+    assert jobs._onehot(four, 2).shape == (1, 2, 2, 2) and jobs._onehot(four, 2, spatial=3).shape == (1, 2, 2, 3, 2)
+
+
+def test_step_budget():
+    from sequitr_amd import jobs
+    config = utils.NetConfiguration.from_params({"num_epochs": 7})
+    assert jobs._step_budget({}, {}, config, 5) == (7, 35)                       # max_steps absent: the configuration's epochs
+    assert jobs._step_budget({"num_epochs": 3}, {}, config, 5) == (3, 15)
+    assert jobs._step_budget({"num_epochs": 3}, {"max_steps": 4}, config, 5) == (3, 4)     # cuts the first epoch off
+    assert jobs._step_budget({"num_epochs": 3}, {"max_steps": 40}, config, 5) == (3, 15)   # never more than the epochs hold
+    assert jobs._step_budget({"num_epochs": 3}, {"max_steps": 0}, config, 5) == (3, 15)    # 0 / None: no limit
+
+
 def test_small_helpers():
     assert utils.filter_doubling(8, 7, 512, reverse=True) == [512, 256, 128, 64, 32, 16, 8]
     assert utils.divisible_by_two_n_times(512, 4) and not utils.divisible_by_two_n_times(24, 4)
