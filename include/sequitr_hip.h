@@ -1370,6 +1370,86 @@ int sq_mask_split_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int
                      void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Volume clean-up: 3-D morphology, cavities, faces (sequitr_amd/volumeops.py: morph3d, fill_cavities, clear_border3d,
+ * VolumeCleanup; the volume jobs' `volume_postprocess` key).  The 3-D counterpart of "Mask clean-up" above for the masks
+ * of UNet3D: mask and out are (N, D, H, W) uint8 class labels with C classes, fewer than 2^31 elements; in the jobs
+ * D, H, W = Z, X, Y.  The N volumes are independent: nothing crosses from volume n into n + 1.
+ *
+ * "Mask clean-up" applies word for word, with voxels for pixels: P_c = (mask == c) for c = 1 .. C-1, byte 0 is background,
+ * bytes >= C belong to no class, are copied through and are never written; every operation computes one processed plane
+ * Q_c per class from the INPUT mask and merges with the extensive rule (dilate, close, fill_holes: out = mask wherever
+ * mask > 0, elsewhere the smallest c whose Q_c is set, else 0) or the anti-extensive rule (erode, open, clear_border:
+ * out = c where Q_c is set and mask == c, else 0; bytes >= C stay).  out must not overlap mask.  "An object" is a
+ * 6-connected component of one class > 0: the labelling of sq_ccl.h with planes = D, scipy.ndimage.label's default 3-D
+ * structure.  Every plane is Boolean: every result is exact and the same bits on every run.
+ *
+ * sq_volume_morph_u8 : op = SQ_MORPH_ERODE / DILATE / OPEN / CLOSE, structure = SQ_MORPH3D_CROSS
+ *   (scipy.ndimage.generate_binary_structure(3, 1), 6 neighbours) or SQ_MORPH3D_CUBE ((3, 3), 26 neighbours), iterations
+ *   r = 1 .. SQ_MORPH3D_MAX_ITER.
+ *     Q_c = scipy.ndimage.binary_{erosion,dilation,opening,closing}(P_c, structure, iterations=r)
+ *   with scipy's defaults (border_value = 0, origin 0): every one of the r (or r + r) elementary 3x3x3 steps sees zeros
+ *   outside the volume on all six faces, so erosion eats in from the faces and closing loses voxels near them.
+ *   One launch per call, no workspace.  A block of 256 threads owns a brick of SQ_MORPH3D_TILE_D x SQ_MORPH3D_TILE_H x
+ *   SQ_MORPH3D_TILE_W voxels and keeps the bit plane of one class in LDS for the brick plus a halo of r (erode, dilate) or
+ *   2r (open, close) planes and rows and of 32 columns (the staged row of 192 columns starts at a multiple of 4 and is three
+ *   64-bit words), in two copies.  Per class c = 1 .. C-1 the block reads the bytes of that region once from global memory
+ *   -- only the planes, rows and dword columns inside the halo it needs and inside the volume -- four rows per wave at a
+ *   time through a 6 KiB byte buffer, and packs each 64-voxel row segment with one __ballot of (byte == c); for the default
+ *   C = 2 that is one read of the region.  A class absent from the region skips its steps.  A cross step is the word's
+ *   horizontal triple (shifts with carry from the neighbouring words) AND / OR'ed with the same word of the rows above and
+ *   below and of the planes before and after; a cube step is the horizontal triple of all nine (plane +- 1, row +- 1) rows.
+ *   Dilations are masked to the volume in all three axes.  The block's result is exact on its brick because an error at
+ *   the staged region's rim travels one voxel per step and the halo is as wide as there are steps.  Each class's finished
+ *   plane is merged into the brick in `out` at once: a thread reads its own voxels of the mask again (and, from the second
+ *   class present on, what it wrote to `out` itself) and stores them, with 4-byte accesses where W % 4 == 0 and both
+ *   pointers are 4-byte aligned, byte by byte otherwise; nothing of the brick is kept in registers across the steps
+ *   (107 VGPRs, no spills).  A brick whose region holds no class at all is copied through.
+ *   Why the cap: the halo is as wide as the number of steps in all three axes, so LDS grows with the cube of it.
+ *   SQ_MORPH3D_MAX_ITER = 4 makes the widest halo 8 (open or close at r = 4): (8 + 16) x (32 + 16) rows x 3 words =
+ *   27 KiB per copy, 60 KiB of static LDS per block with the byte buffer -- under 64 KiB, two blocks per CU.
+ *   Larger radii: iterated erosions and iterated dilations of one plane compose exactly (erode 2 then erode 2 = erode 4),
+ *   so for C = 2 two steps in a list equal one larger step.  For C > 2 this holds for erosions only: two extensive steps
+ *   merge between them -- a voxel the first dilation gave to class 1 is no background for class 2 in the second -- so they
+ *   differ from a single larger step.  Open and close do not compose this way at any C (open 2 twice = open 2).
+ *
+ * sq_volume_fill_holes_u8 : a cavity of class c is a 6-connected component of ~P_c with no voxel on any of the volume's six
+ *   faces -- what scipy.ndimage.binary_fill_holes(P_c) fills on a 3-D array.  Q_c = P_c plus the cavities that qualify: all
+ *   of them for max_voxels <= 0, otherwise those of at most max_voxels voxels, counting EVERY voxel of the component,
+ *   voxels of other classes and bytes >= C included.  Extensive merge, the lowest class first.  The steps of
+ *   sq_mask_fill_holes_u8 with rows = N D H in the row scan, planes = D in the merge and the face voxels -- 2 H W + 2 D W +
+ *   2 D H per volume, those on edges more than once -- in place of the edge pixels.  D = 1 (or H = 1, or W = 1) puts every
+ *   voxel on a face: nothing is filled, as with scipy.
+ *   workspace: sq_volume_fill_holes_workspace(N, D, H, W) bytes (-1: too large), 16-B aligned: 9 B per voxel.
+ *
+ * sq_volume_clear_border_u8 : removes every object that has a voxel on a face; the rest is unchanged (anti-extensive merge;
+ *   bytes >= C stay).  faces = SQ_FACES_ALL: all six faces.  faces = SQ_FACES_LATERAL: only the four faces h = 0, h = H-1,
+ *   w = 0, w = W-1 -- a z-stack usually cuts cells at its first and last slice, and the user may want to keep them.
+ *   workspace: sq_volume_clear_border_workspace(N, D, H, W) bytes (-1: too large), 16-B aligned: 8 B per voxel.
+ *
+ * All three return SQ_EINVAL with a message, before any launch and with out untouched, for null pointers, C < 2 or
+ * C > 256, a bad op, structure or faces value, iterations outside 1 .. SQ_MORPH3D_MAX_ITER, N, D, H or W < 1, 2^31 or more
+ * elements, a workspace that is not 16-B aligned, and out overlapping mask.  None reads anything back, and every call is a
+ * chain of kernel launches on `stream` and nothing else (the counts and flags are cleared and the mask is copied by kernels,
+ * not by memset or memcpy calls): each can be captured in a graph and replayed.  Not built: a 3-D split, the 18-neighbour structure, anisotropic structuring elements.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_MORPH3D_CROSS 0
+#define SQ_MORPH3D_CUBE 1
+#define SQ_MORPH3D_MAX_ITER 4
+#define SQ_MORPH3D_TILE_D 8
+#define SQ_MORPH3D_TILE_H 32
+#define SQ_MORPH3D_TILE_W 128
+#define SQ_FACES_ALL 0
+#define SQ_FACES_LATERAL 1
+int sq_volume_morph_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int op, int structure,
+                       int iterations, void *stream);
+int64_t sq_volume_fill_holes_workspace(int N, int D, int H, int W);
+int sq_volume_fill_holes_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int64_t max_voxels,
+                            void *workspace, void *stream);
+int64_t sq_volume_clear_border_workspace(int N, int D, int H, int W);
+int sq_volume_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int faces,
+                              void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Label zones and the zone contact graph (sequitr_amd/analysis/neighbors.py: which cells are next to
  * which).  The reference counts neighbours per frame on the host with scipy's Voronoi / Delaunay of the centroids
  * (sequitr/analysis/neighbors.py); here the per-pixel part -- the zone of influence of every object -- and the per-pixel

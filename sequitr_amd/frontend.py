@@ -836,7 +836,8 @@ class VolumeTiler(object):
         return out
 
 
-def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise=True, want_logits=False, on_masks=None):
+def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise=True, want_logits=False, on_masks=None,
+                    postprocess=None):
     """Segment whole volumes brick by brick: `volumes` is an (N, Z, X, Y) uint8 | uint16 | float32 numpy array or memmap,
     `net` a UNet3D built at the brick shape (brick and margin in the array's (Z, X, Y) order).  Raw volume i+1 goes
     through two pinned Z-slab buffers of bounded size and is uploaded on a side stream while volume i runs: statistics,
@@ -844,8 +845,13 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     arrays in HBM, which drain to the host on a third stream while volume i+1 runs.  Returns (masks (N, Z, X, Y) uint8,
     logits (N, Z, X, Y, n_outputs) float32 or None) on the host.  With on_masks the masks are not downloaded: each
     volume's device mask is handed to on_masks(i, mask (1, Z, X, Y)) instead, valid until volume i+2 is started, and
-    the first value returned is None."""
+    the first value returned is None.  postprocess (a volumeops.VolumeCleanup or a step list) cleans each volume's
+    stitched mask on the compute stream with net.n_outputs classes before anything else sees it: the cleaned mask is
+    what on_masks receives and what drains to the host.  Logits are not touched."""
     arr = volumes
+    if postprocess is not None:
+        from .volumeops import VolumeCleanup
+        postprocess = postprocess if isinstance(postprocess, VolumeCleanup) else VolumeCleanup(postprocess)
     if getattr(arr, 'ndim', 0) != 4:
         raise ValueError('volumes must be (N, Z, X, Y), got shape %s' % (getattr(arr, 'shape', None),))
     N, Z, X, Y = (int(s) for s in arr.shape)
@@ -908,6 +914,8 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
             tiler.scatter(masks, mask_dev[k], first)
             if want_logits:
                 tiler.scatter(net.logits(), logits_dev[k], first)
+        if postprocess is not None:                             # the result lives in the cleaner's buffers: back into
+            mask_dev[k].copy_(postprocess.apply(mask_dev[k], n_out))    # mask_dev[k], which stays valid until volume i+2
         freed[k].record(cur)
         done[k].record(cur)
         if on_masks is not None:

@@ -80,6 +80,7 @@ def SERVER_segment(params, options):
     masks out, PCIe both ways included); ``setup_seconds`` is what comes before it once per job (weights, pinned
     staging buffers, one warm-up batch) and ``mpixels_per_s_with_setup`` the rate with it counted.
     """
+    _refuse_volume_postprocess(params, 'SERVER_segment')
     import torch
     from .networks.unet import UNet2D
     from .pipeline import ImagePipeline
@@ -209,7 +210,7 @@ def _brick_volumes(params, options):
     return device, x, (bz, bx, by), margin, geometry
 
 
-def _segment_volume_bricks(params, options):
+def _segment_volume_bricks(params, options, cleanup=None):
     """SERVER_segment_volume with params['brick']: volumes of any size, raw, brick by brick (frontend.segment_volumes)."""
     device, x, (bz, bx, by), margin, geometry = _brick_volumes(params, options)
     out_dir = params['output']
@@ -243,7 +244,7 @@ def _segment_volume_bricks(params, options):
     t0 = time.time()
     out, logits = segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch,
                                   normalise=bool(params.get('normalise', True)), want_logits=want_logits,
-                                  on_masks=sink if want_centroids else None)
+                                  on_masks=sink if want_centroids else None, **({'postprocess': cleanup} if cleanup else {}))
     if not want_centroids:
         masks = out
     dt = time.time() - t0
@@ -255,6 +256,8 @@ def _segment_volume_bricks(params, options):
             'mvoxels_per_s': float(voxels / max(dt, 1e-9) / 1e6), 'device': device,
             'brick': [bx, by, bz], 'margin': [geometry.margin[1], geometry.margin[2], geometry.margin[0]],
             'bricks_per_volume': int(geometry.per_volume)}
+    if cleanup is not None:
+        info['volume_postprocess'] = cleanup.record()
     if want_centroids:
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
@@ -282,15 +285,23 @@ def SERVER_segment_volume(params, options):
     network launch.  The centroids come from the masks while they are in HBM.  ``segment_volume.json`` gains ``brick``,
     ``margin`` (both (X, Y, Z)) and ``bricks_per_volume``.
 
+    params['volume_postprocess'] (a list of volume clean-up steps, or the path of a JSON file holding one;
+    volumeops.VolumeCleanup, with D, H, W = Z, X, Y) cleans every volume's mask in HBM, with and without ``brick``:
+    ``mask.npy`` and the centroid file describe the cleaned masks and ``segment_volume.json`` records the steps, defaults
+    written out, under ``volume_postprocess``.  A bad step list raises before any input is opened; without the key
+    nothing changes.  params['postprocess'], the planar list, stays refused.
+
     ``segment_volume.json``: ``seconds`` / ``mvoxels_per_s`` cover the volumes (upload, network, download);
     ``setup_seconds`` is weights plus one warm-up volume."""
     if params.get('postprocess') is not None:
-        raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope")
+        raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope "
+                         "(params['volume_postprocess'] cleans them)")
+    cleanup = _parse_volume_postprocess(params)                 # before anything is opened
     import torch
     from .networks.unet import UNet3D
 
     if params.get('brick') is not None:
-        return _segment_volume_bricks(params, options)
+        return _segment_volume_bricks(params, options, cleanup)
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
     out_dir = params['output']
@@ -310,6 +321,8 @@ def SERVER_segment_volume(params, options):
     t0 = time.time()
     for i in range(N):
         m = net.predict(np.ascontiguousarray(x[i:i + 1]))
+        if cleanup is not None:
+            m = cleanup.apply(m.contiguous(), net.n_outputs)   # on the device mask, before the download
         masks[i] = m[0].cpu().numpy()
         if logits is not None:
             logits[i] = net.logits()[0].cpu().numpy()
@@ -321,6 +334,8 @@ def SERVER_segment_volume(params, options):
     voxels = N * Z * X * Y
     info = {'volumes': int(N), 'shape': [int(Z), int(X), int(Y)], 'seconds': dt, 'setup_seconds': t0 - t_setup,
             'mvoxels_per_s': float(voxels / max(dt, 1e-9) / 1e6), 'device': device}
+    if cleanup is not None:
+        info['volume_postprocess'] = cleanup.record()
     if options.get('centroids'):
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
@@ -399,6 +414,23 @@ def _parse_postprocess(params):
     return MaskCleanup(load_steps(spec))
 
 
+def _parse_volume_postprocess(params):
+    """params['volume_postprocess'] -- a list of volume clean-up steps, or the path of a JSON file that holds one -- as a
+    volumeops.VolumeCleanup, before any input is opened; None without the key.  A bad step list raises here."""
+    spec = params.get('volume_postprocess')
+    if spec is None:
+        return None
+    from .volumeops import VolumeCleanup, load_steps
+    return VolumeCleanup(load_steps(spec))
+
+
+def _refuse_volume_postprocess(params, job):
+    """the jobs that produce no (N, Z, X, Y) masks from bricks refuse the key before any input is opened"""
+    if params.get('volume_postprocess') is not None:
+        raise ValueError("params['volume_postprocess'] cleans the masks of SERVER_segment_volume and of SERVER_evaluate with "
+                         "params['brick']: %s does not take it" % job)
+
+
 def _channel_setup(params, C, parsed=None):
     """What the frame jobs derive from params once the number of channels is known, before a pixel is read:
     (clean, normalise, pipeline record or None, num_inputs or None).  params['pipeline'] (`parsed`: what _parse_pipelines
@@ -474,6 +506,7 @@ def SERVER_segment_frames(params, options):
     zones' max_distance, default none) and params['neighbor_seeds'] ('objects' or 'centroids'); a bad value raises before a
     frame is opened.  The table describes the mask after `postprocess` and the size filter: dropped objects are no seeds.
     Without the option every file is what it was."""
+    _refuse_volume_postprocess(params, 'SERVER_segment_frames')
     postprocess = _parse_postprocess(params)                    # before anything is opened
     want_neighbors = bool(options.get('neighbors'))
     if want_neighbors:                                          # a bad value raises here, before a frame is opened
@@ -659,9 +692,9 @@ def _evaluation_record(counts, ignored):
             'per_frame': [dict(json_ready(scores(c)), ignored=int(g)) for c, g in zip(counts, ignored)]}
 
 
-def _evaluate_volume_bricks(params, options):
+def _evaluate_volume_bricks(params, options, cleanup=None):
     """SERVER_evaluate with params['brick']: volumes brick by brick, each stitched mask scored where segment_volumes
-    leaves it"""
+    leaves it (after params['volume_postprocess'], when given)"""
     labels = _load_labels(params.get('labels'))
     device, x, (bz, bx, by), margin, geometry = _brick_volumes(params, options)
     N, Z, X, Y = (int(s) for s in x.shape)
@@ -695,7 +728,7 @@ def _evaluate_volume_bricks(params, options):
 
     t0 = time.time()
     segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch, normalise=bool(params.get('normalise', True)),
-                    on_masks=sink)
+                    on_masks=sink, **({'postprocess': cleanup} if cleanup else {}))
     counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
@@ -705,6 +738,8 @@ def _evaluate_volume_bricks(params, options):
             'mpixels_per_s': float(N * Z * X * Y / max(dt, 1e-9) / 1e6), 'device': device, 'brick': [bx, by, bz],
             'margin': [geometry.margin[1], geometry.margin[2], geometry.margin[0]],
             'bricks_per_volume': int(geometry.per_volume)}
+    if cleanup is not None:
+        info['volume_postprocess'] = cleanup.record()
     info.update(_evaluation_record(counts_h, ignored_h))
     with open(os.path.join(out_dir, 'evaluate.json'), 'w') as f:
         json.dump(info, f, indent=2)
@@ -730,10 +765,14 @@ def SERVER_evaluate(params, options):
 
     params['postprocess'] (as SERVER_segment_frames takes it, the ``split`` step included) cleans each batch's masks in HBM first: ``confusion.npy``, the
     scores and ``mask.npy`` describe the cleaned masks and evaluate.json records the steps under 'postprocess'.  It covers
-    frames only: together with params['brick'] it is refused."""
+    frames only: together with params['brick'] it is refused.  params['volume_postprocess'] (as SERVER_segment_volume takes
+    it) does the same for volumes: it needs params['brick'] and is refused without it; evaluate.json records the steps
+    under 'volume_postprocess'."""
     postprocess = _parse_postprocess(params)                    # before anything is opened
+    cleanup = _parse_volume_postprocess(params)
     if params.get('brick') is not None:
-        return _evaluate_volume_bricks(params, options)
+        return _evaluate_volume_bricks(params, options, cleanup)
+    _refuse_volume_postprocess(params, 'SERVER_evaluate without it')
     labels = _load_labels(params.get('labels'))
     frames, F, H, W, C_in = _open_channels(params)
     if tuple(labels.shape) != (F, H, W):
@@ -1156,6 +1195,7 @@ def SERVER_train(params, options):
     (row = truth, column = prediction), ignored, iou, dice, accuracy, mean_iou, seconds}; ms_per_step leaves the
     validation time out.  Single process only: with WORLD_SIZE > 1 the keys raise.
     """
+    _refuse_volume_postprocess(params, 'SERVER_train')
     if params.get('tile') is not None:
         return _train_frame_tiles(params, options)
     import torch
@@ -1416,6 +1456,7 @@ def SERVER_train_volume(params, options):
     ``samples_per_epoch``, ``seed``; net.config's ``shape`` is the brick, so the model loads into SERVER_segment_volume
     with the same ``brick``.
     """
+    _refuse_volume_postprocess(params, 'SERVER_train_volume')
     import torch
     from . import utils
     from .networks.unet import UNet3DTrain
@@ -1503,6 +1544,7 @@ def SERVER_train_gan(params, options):
     Single process.  After the last level the highest checkpoint is exported with convert_checkpoint_to_model().  Returns
     (and writes to ``train.json``) levels, sizes, steps, d_loss and g_loss of the last discriminator step, graph, dtype,
     crop, images, seconds, export_dir."""
+    _refuse_volume_postprocess(params, 'SERVER_train_gan')
     import torch
     from .networks import gan
 

@@ -6,6 +6,7 @@ filling, removal of objects cut by the frame edge.  The reference has no counter
 sq_mask_fill_holes_u8, sq_mask_clear_border_u8, sq_mask_split_u8; include/sequitr_hip.h, "Mask clean-up" and "Mask
 clean-up: splitting", is the contract: classes, merge rules, scipy's definitions).  ``MaskCleanup`` is a validated list of such steps that runs on a batch of device masks between two cached
 buffers; the frame jobs take one as ``params['postprocess']``.  Planar (N, H, W) uint8 masks only; there is no CPU path.
+The (N, D, H, W) masks of UNet3D are cleaned by sequitr_amd.volumeops (3-D morphology, cavities, faces).
 Every result equals the scipy restatement in tests/mask_cleanup_cases.py and tests/mask_split_cases.py exactly
 (tests/test_gpu_mask_cleanup.py, tests/test_gpu_mask_split.py).
 
