@@ -1210,7 +1210,8 @@ def wgan_losses_bwd(Dz, Dx, gn2, g_dloss, g_gloss, out_dz=None, out_dx=None):
 
 
 def wgrad1x1_small(a, b):
-    """(Ca,Cb) = sum_p a[p,:]^T b[p,:]; a (...,Ca<=4), b (...,Cb%4==0) over the same pixels."""
+    """(Ca,Cb) = sum_p a[p,:]^T b[p,:] over the same pixels.  f32: a (...,Ca) with Ca 1..7, b (...,Cb%4==0).
+    bf16 b (C%8==0): Ca 1..4, or a None for the per-channel sums of b (ops_gan_bf16.wgrad1x1_small)."""
     if b.dtype == _BF16:
         return _gb().wgrad1x1_small(a, b)
     _chk(a, "a"), _chk(b, "b")

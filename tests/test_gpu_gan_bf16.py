@@ -92,7 +92,7 @@ def test_pool_and_broadcast_bf16(shape):
     one_ulp(leak, torch.where(x > 0, x, x.float().mul(np.float32(0.2)).double()), "leaky forward")
 
 
-@pytest.mark.parametrize("C,Ci", [(8, 2), (16, 2), (64, 1), (512, 2), (32, 4)])
+@pytest.mark.parametrize("C,Ci", [(8, 2), (16, 2), (64, 1), (512, 2), (32, 4), (24, 2), (40, 3), (48, 2), (56, 1), (72, 4)])
 def test_image_side_convolutions_bf16(C, Ci):
     """from_image (f32 image -> bf16 features), to_image (features -> image) and their weight gradients"""
     rng = np.random.default_rng(C + Ci)
