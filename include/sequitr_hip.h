@@ -631,6 +631,8 @@ int sq_objects_relabel(const uint8_t *mask, int N, int planes, int H, int W, con
  *   d = distance_transform_edt(1 - image);  out = w0*(1-image)*exp(-(d*d)/(2 sigma^2 + 1e-99)) + image + 1
  * img (N,H,W) f32 binary label images (values 0 / 1; a pixel is a feature iff 1 - image == 0), one map per
  * image.  workspace: sq_weightmap_workspace bytes, 16-B aligned.  H, W < 30000.
+ * Types as in numpy: the reference's image is float32 and w0 a Python scalar, so w0*(1-image) is the FLOAT32 product
+ * fl32(fl32(w0) * fl32(1 - image)); it is widened where it meets the float64 exp(...), the rest is float64.
  *   sq_edt_sq_f32        : d2 (N,H,W) int32 = EXACT squared Euclidean distance to the nearest feature
  *                          (an image with no feature reproduces scipy's artefact: distance to index (-1, 0))
  *   sq_weightmap_edt_f32 : out64 (N,H,W) f64 as the reference computes it and / or out32 (N,H,W) f32, the
@@ -650,7 +652,8 @@ int sq_weightmap_edt_f32(const float *img, double *out64, float *out32, void *wo
  *   squared distance of slice z' (infinite for a slice without a feature); a volume without any feature reproduces
  *   scipy's artefact, the distance to index (-1, 0, 0): D3 = fl(fl(((z+1) dz)^2 + x^2) + y^2).
  *   sq_edt3d_sq_f64        : d2 (N,D,H,W) f64 = D3 (for dz == 1 an exact integer)
- *   sq_weightmap3d_edt_f32 : d = sqrt(D3); out = w0*(1-image)*exp(-(d*d)/(2 sigma^2 + 1e-99)) + image + 1 in float64,
+ *   sq_weightmap3d_edt_f32 : d = sqrt(D3); out = w0*(1-image)*exp(-(d*d)/(2 sigma^2 + 1e-99)) + image + 1 in float64
+ *                            except the float32 product w0*(1-image) (the reference on a float32 volume, as above),
  *                            written to out64 (N,D,H,W) and / or rounded once to out32, the `weights` tensor of the loss
  * SQ_EDT3D_LDS=0 (read per launch) runs the depth pass on global memory instead of LDS: the same result, bit for bit. */
 int64_t sq_weightmap3d_workspace(int N, int D, int H, int W);
@@ -663,7 +666,8 @@ int sq_weightmap3d_edt_f32(const float *img, double *out64, float *out32, void *
  * longest edge of each simplex, from scipy.spatial.Delaunay of the boundary points (host); img (N,H,W) binary f32.
  * Rasterises the simplices (point location; a pixel covered by several takes the largest value), builds the
  * pre-filter map (1024 where uncovered, 0 on foreground), applies scipy's gaussian_filter(sigma = 1) and the
- * reference's float64 expression.  out64 (N,H,W) and / or out32; workspace of sq_weightmap2_workspace bytes. */
+ * reference's expression: float64 except w0*(1-mask), a float32 product because mask is mask.astype('float32').
+ * out64 (N,H,W) and / or out32; workspace of sq_weightmap2_workspace bytes. */
 int64_t sq_weightmap2_workspace(int N, int H, int W);
 /* ImageWeightMap2's boundary points on the device (sequitr/pipeline.py:516-528: erosion outline of the label XOR the
  * outline of the label dilated three times, von Neumann element, border value 0): points (N,H,W) uint8, 1 = a vertex

@@ -1,7 +1,10 @@
 // EDT weight maps on the GPU (the step in front of the training hot path).
 // ImageWeightMap.pipe, sequitr/pipeline.py:475-479:
 //     d   = scipy.ndimage.distance_transform_edt(1 - image)        (distance to the nearest pixel == 1)
-//     out = w0 * (1 - image) * exp(-(d*d) / (2 sigma^2 + 1e-99)) + image + 1          (float64)
+//     out = w0 * (1 - image) * exp(-(d*d) / (2 sigma^2 + 1e-99)) + image + 1
+// ImagePipe.__call__ hands pipe() a FLOAT32 image and w0 is a Python scalar, so numpy forms w0 * (1 - image) in float32:
+// fl32(fl32(w0) * fl32(1 - image)).  The product is widened only where it meets the float64 exp(...); everything from there
+// on is float64.  For a w0 that is a float32 number (10, 30) on a binary image both readings give the same bits.
 //
 // Exact Euclidean distance transform, separable:
 //   pass 1 (rows)   : g(y,x) = distance along the row to the nearest feature pixel; one wave per row,
@@ -11,7 +14,7 @@
 //                     as soon as (y-y')^2 >= the best so far; lanes run along x => every read of g is a
 //                     coalesced row segment
 // D2 is an exact integer, d = sqrt((double)D2) is correctly rounded => identical to scipy's
-// sqrt(sum(delta^2)).  The map then follows the reference's float64 expression operation by operation.
+// sqrt(sum(delta^2)).  The map then follows the reference's expression operation by operation, each in numpy's type.
 // Integer / streaming work: 4 B/pixel in, 2 B/pixel of g written and re-read, 8 (+4) B/pixel out.
 #include "sq_common.h"
 
@@ -110,11 +113,12 @@ __global__ __launch_bounds__(256) void edt_cols_weight_kernel(const float *__res
         if (WANT_D2) {
             d2out[p] = best;
         } else {
-            const double image = (double)img[p];
-            const double bg = 1.0 - image;
+            const float imf = img[p];
+            const double image = (double)imf;
+            const float wb = (float)w0 * (1.0f - imf);          // float32, as numpy forms it (see the head of the file)
             const double d = sqrt((double)best);
             // self.w0 * (1.-image) * np.exp(-(d*d) / (2.*sigma**2 + 1e-99)) + image + 1.
-            const double v = w0 * bg * exp(-(d * d) / denom) + image + 1.0;
+            const double v = (double)wb * exp(-(d * d) / denom) + image + 1.0;
             if (out64) out64[p] = v;
             if (out32) out32[p] = (float)v;
         }
@@ -260,10 +264,11 @@ __global__ __launch_bounds__(256) void edt_cols_weight_v2_kernel(const float *__
         if (WANT_D2) {
             d2out[p] = best;
         } else {
-            const double image = (double)img[p];
-            const double bg = 1.0 - image;
+            const float imf = img[p];
+            const double image = (double)imf;
+            const float wb = (float)w0 * (1.0f - imf);          // float32, as numpy forms it
             const double d = sqrt((double)best);
-            const double v = w0 * bg * exp(-(d * d) / denom) + image + 1.0;   // the reference's expression, as above
+            const double v = (double)wb * exp(-(d * d) / denom) + image + 1.0;   // the reference's expression, as above
             if (out64) out64[p] = v;
             if (out32) out32[p] = (float)v;
         }
@@ -411,10 +416,11 @@ __device__ __forceinline__ void edt3d_store(const float *__restrict__ img, doubl
     if (WANT_D2) {
         d2out[p] = best;
     } else {
-        const double image = (double)img[p];
-        const double bg = 1.0 - image;
+        const float imf = img[p];
+        const double image = (double)imf;
+        const float wb = (float)w0 * (1.0f - imf);              // float32, as numpy forms it on a float32 volume
         const double d = sqrt(best);
-        const double v = w0 * bg * exp(-(d * d) / denom) + image + 1.0;       // the reference's expression, as above
+        const double v = (double)wb * exp(-(d * d) / denom) + image + 1.0;    // the reference's expression, as above
         if (out64) out64[p] = v;
         if (out32) out32[p] = (float)v;
     }
@@ -572,7 +578,8 @@ extern "C" int sq_weightmap3d_edt_f32(const float *img, double *out64, float *ou
 //      the largest longest-edge wins (atomicMax on the bit pattern of a positive double: order-independent);
 //   2. weight_map = longest edge on background pixels (1024 where no simplex covers, :556), 0 on foreground;
 //      gaussian_filter(sigma = 1) as scipy applies it: 9 taps (truncate 4), 'reflect' borders, axis 0 then axis 1;
-//   3. w0 * (1 - mask) * exp(-(wm * wm) / (2 sigma^2 + 1e-99)) + 1 + mask, float64, operation by operation.
+//   3. w0 * (1 - mask) * exp(-(wm * wm) / (2 sigma^2 + 1e-99)) + 1 + mask, operation by operation: mask is
+//      mask.astype('float32'), so w0 * (1 - mask) is a float32 product as in the EDT map; the rest is float64.
 namespace {
 
 __global__ __launch_bounds__(256) void wm2_raster_kernel(const int *__restrict__ simp, const double *__restrict__ longest,
@@ -640,8 +647,10 @@ __global__ __launch_bounds__(256) void wm2_gauss1_weight_kernel(const float *__r
         double acc = tmp[i] * wk[0];
         for (int k = 4; k >= 1; --k) acc += (tmp[row + wm2_reflect(y - k, W)] + tmp[row + wm2_reflect(y + k, W)]) * wk[k];
         const double wm = acc * wsum;                           // the singleton channel axis: every tap reads the same value
-        const double mask = (double)(img[i] != 0.f ? 1.0f : 0.0f);
-        const double r = w0 * (1.0 - mask) * exp(-(wm * wm) / denom) + 1.0 + mask;
+        const float maskf = img[i] != 0.f ? 1.0f : 0.0f;        // mask.astype('float32')
+        const double mask = (double)maskf;
+        const float wb = (float)w0 * (1.0f - maskf);            // float32, as numpy forms it
+        const double r = (double)wb * exp(-(wm * wm) / denom) + 1.0 + mask;
         if (out64) out64[i] = r;
         if (out32) out32[i] = (float)r;
     }

@@ -22,6 +22,7 @@ from tests import weightmap3d_cases as wc
 pytestmark = pytest.mark.gpu
 GUARD = 256
 W0, SIGMA = 10., 5.
+W0_F64, SIGMA_F64 = 12.3, 3.                                # a w0 that is not a float32 number
 
 
 def dev(a):
@@ -60,12 +61,12 @@ def raw_sq(img, dz):
     return out.take(shape)
 
 
-def raw_map(img, dz):
+def raw_map(img, dz, w0=W0, sigma=SIGMA):
     """both outputs of one launch: (float64 map, float32 map)"""
     lib, shape = _lib.load(), tuple(img.shape)
     ws, nbytes = _workspace(shape)
     o64, o32 = Guarded(img.numel(), torch.float64, -7.0), Guarded(img.numel(), torch.float32, -7.0)
-    _lib.check(lib.sq_weightmap3d_edt_f32(img.data_ptr(), o64.ptr, o32.ptr, ws.data_ptr(), *shape, W0, SIGMA, dz,
+    _lib.check(lib.sq_weightmap3d_edt_f32(img.data_ptr(), o64.ptr, o32.ptr, ws.data_ptr(), *shape, w0, sigma, dz,
                                           ops._stream()), "sq_weightmap3d_edt_f32")
     torch.cuda.synchronize()
     assert bool((ws[nbytes:] == 0xFF).all()), "wrote past the workspace"
@@ -92,12 +93,21 @@ def check_case(name):
         assert np.array_equal(m32, ref.astype(np.float32)), (name, dz, np.abs(m32 - ref).max())
         assert torch.equal(ops.weightmap_edt3d(img, W0, SIGMA, dz, dtype=torch.float64), dev(m64))
         assert torch.equal(ops.weightmap_edt3d(img.reshape(img.shape + (1,)), W0, SIGMA, dz), dev(m32))
-    # the reference's own call on the 3-D array
-    w = device_weightmaps3d(lab, W0, SIGMA, device="cuda:0")
-    assert w.dtype == torch.float32 and tuple(w.shape) == lab.shape + (1,) and w.is_cuda
-    wn = w.cpu().numpy()[..., 0]
-    for i, v in enumerate(lab):
-        assert np.array_equal(wn[i], weightmap_ref.image_weight_map(v, W0, SIGMA).astype(np.float32)), (name, i)
+    # the reference's own call on the 3-D array; W0_F64 is not a float32 number, so there the float32 product of
+    # w0 * (1. - image) on a float32 volume differs from a double one in every background voxel near a feature
+    for w0, sigma in ((W0, SIGMA), (W0_F64, SIGMA_F64)):
+        w = device_weightmaps3d(lab, w0, sigma, device="cuda:0")
+        assert w.dtype == torch.float32 and tuple(w.shape) == lab.shape + (1,) and w.is_cuda
+        wn = w.cpu().numpy()[..., 0]
+        for i, v in enumerate(lab):
+            assert np.array_equal(wn[i], weightmap_ref.image_weight_map(v, w0, sigma).astype(np.float32)), (name, w0, i)
+    ref = np.stack([weightmap_ref.image_weight_map(v, W0_F64, SIGMA_F64) for v in lab])
+    assert wc.ulps64(wc.weight_expr(lab, np.sqrt(wc.reference_sq(name, 1.0)), W0_F64, SIGMA_F64), ref) == 0
+    m64, m32 = raw_map(img, 1.0, W0_F64, SIGMA_F64)
+    u = wc.ulps64(m64, ref)
+    print("%s w0=%g: float64 map %d ulp from the reference" % (name, W0_F64, u))
+    assert u <= 2, (name, W0_F64, u)
+    assert np.array_equal(m32, ref.astype(np.float32)), (name, W0_F64)
     return img
 
 

@@ -69,6 +69,24 @@ def test_case_list_is_what_the_sweep_needs():
     assert not e[0].any() and e[1].sum() == 1
     for name in wc.CASE_NAMES:
         assert set(np.unique(wc.labels(name))) <= {0.0, 1.0}
+    # slices outside the 1024 x 2048 box of the second form of the planar passes, each volume with one featureless slice
+    for name, outside in (("wideplane_1x2x3x1030", lambda H, W: W > 1024 and H <= 2048),
+                          ("tallplane_1x3x2050x3", lambda H, W: H > 2048 and W <= 1024)):
+        v = wc.labels(name)
+        assert outside(*v.shape[2:]) and [bool(z.any()) for z in v[0]].count(False) == 1 and v.dtype == np.float32
+
+
+def test_map_expression_follows_numpy_types():
+    """on a float32 volume the reference forms w0 * (1. - image) in float32 (w0 is a Python scalar): weight_expr equals the
+    reference's call bit for bit at a w0 that is not a float32 number, and the all-double product does not"""
+    for name in ("odd_1x5x9x11", "gap_2x12x20x24", "wideplane_1x2x3x1030", "tallplane_1x3x2050x3"):
+        lab = wc.labels(name)
+        d = np.sqrt(wc.reference_sq(name, 1.0))
+        for w0, sigma in ((10., 5.), (12.3, 3.)):
+            ref = np.stack([weightmap_ref.image_weight_map(v, w0, sigma) for v in lab])
+            assert ref.dtype == np.float64 and wc.ulps64(wc.weight_expr(lab, d, w0, sigma), ref) == 0, (name, w0)
+            double = wc.weight_expr(lab.astype(np.float64), d, w0, sigma)
+            assert (double != ref).any() == (w0 == 12.3), (name, w0)
 
 
 def test_host_side_validation_of_the_volumetric_entries_needs_no_gpu():

@@ -48,9 +48,16 @@ def edt3d_sq_def(vol, dz=1.0):
 
 
 def weight_expr(vol, d, w0=10., sigma=5.):
-    """pipeline.py:477-479 on a given distance array, float64"""
-    image = np.asarray(vol, np.float64)
-    return w0 * (1. - image) * np.exp(-(d * d) / (2. * sigma ** 2 + 1e-99)) + image + 1.
+    """pipeline.py:477-479 on a given distance array, with numpy's types: on a float32 volume (what the device takes) w0 is a
+    Python scalar and w0 * (1. - image) the float32 product fl32(fl32(w0) * fl32(1 - image)), widened where it meets the
+    float64 exp(...); on a float64 volume everything is float64"""
+    image = np.asarray(vol)
+    if image.dtype == np.float32:
+        wb = (np.float32(w0) * (np.float32(1.) - image)).astype(np.float64)
+    else:
+        image = image.astype(np.float64)
+        wb = w0 * (1. - image)
+    return wb * np.exp(-(d * d) / (2. * sigma ** 2 + 1e-99)) + image + 1.
 
 
 def weightmap3d_def(vol, w0=10., sigma=5., dz=1.0):
@@ -85,6 +92,12 @@ def _empty_and_corner():
     return v
 
 
+def _featureless_slice(seed, shape, p, z):
+    v = _random(seed, shape, p)
+    v[0, z] = 0                                              # P_INF from the first form of the planar passes
+    return v
+
+
 # name -> labels (N, D, H, W) float32; the shapes and densities of the sweep
 _CASES = {
     "planar_1x1x6x6": lambda: _random(1, (1, 1, 6, 6), 0.1),
@@ -96,6 +109,9 @@ _CASES = {
     "gap_2x12x20x24": _gap,
     "empty_2x4x10x10": _empty_and_corner,
     "deep_1x300x4x40": lambda: _random(6, (1, 300, 4, 40), 0.002),
+    # slices wider than 1024 / taller than 2048: the planar half runs edt_rows_kernel + edt_cols_weight_kernel<true, true>
+    "wideplane_1x2x3x1030": lambda: _featureless_slice(8, (1, 2, 3, 1030), 0.004, 1),
+    "tallplane_1x3x2050x3": lambda: _featureless_slice(9, (1, 3, 2050, 3), 0.004, 1),
 }
 CASE_NAMES = tuple(_CASES)
 
