@@ -1513,6 +1513,77 @@ int64_t sq_zone_graph_workspace(int max_pairs);
 int sq_zone_graph(const int32_t *zones, int N, int H, int W, int max_label, int64_t *stats, int32_t *pairs, int max_pairs,
                   int32_t *count, int32_t *dropped, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Label zones and the contact graph in volumes (sequitr_amd/analysis/neighbors.py: which cells of a z-stack are next
+ * to which -- cells stacked along z are neighbours, and no slice-by-slice run shows it).  The volumetric counterpart of
+ * the section above: (N, D, H, W) int32 arrays, fewer than 2^31 voxels, `dz` the depth spacing in in-plane pixels
+ * (scipy's sampling = (dz, 1, 1)).  The zones are a minimum of fixed floating-point expressions, the graph is integer
+ * work: the same bits on every run.  Neither call reads anything back, waits on a flag or lets one block wait on
+ * another: each is a linear chain of kernels that can be captured in a graph, and whatever is cleared is cleared by a
+ * kernel of the chain.
+ *
+ * sq_label_zones3d_i32.  labels (N,D,H,W) int32: a voxel is a SEED of object L iff 1 <= L <= max_label; every other value
+ * is background and not an error.  max_distance R >= 0, 0 = unbounded.
+ *   For every slice (n, z') let (P, L)(n, z', h, w) be what sq_label_zones_i32 defines for that slice alone: P the exact
+ *   integer squared distance to the slice's nearest seed, L the smallest label among the slice's seeds at that distance.
+ *   A slice without a seed contributes nothing.
+ *   A(k) = fl(fl(k dz) fl(k dz)) in double: exactly sq_edt3d_sq_f64's A.
+ *   (D3, zone)(n, z, h, w) = the lexicographic minimum over z' of (fl(A(z - z') + P(n, z', h, w)), L(n, z', h, w)),
+ *   the sum being one double add.  The search never crosses from volume n into n +- 1.
+ *   zones(n,p) = zone, or 0 where R > 0 and D3 > (double)R * R;   d2(n,p) = D3 everywhere (float64; d2 may be NULL).
+ *   A volume without a seed gets zone 0 and d2 = +inf everywhere (scipy's feature transform points such a volume at index
+ *   (-1, 0, 0), and sq_edt3d_sq_f64 reproduces that; this call does not -- the same decision as in the planar call).
+ * Consequences: a seed voxel lies in its own zone; without a reach the zones of a volume with a seed cover it; for a
+ * volume with a seed d2 equals sq_edt3d_sq_f64 of the seed indicator bit for bit, for every dz (the minimum of the first
+ * components is the same minimum); at dz = 1, and at every dz at which each A + P is exact, the result is the all-pairs
+ * definition -- the nearest seed in 3-D, the smallest label at a tie.  Where A + P rounds, ties are ties of the ROUNDED
+ * sums, as written above.
+ * The kernels:
+ *   planar half : the row and column passes of sq_label_zones_i32 over the N*D slices, always unbounded and with d2, so
+ *                 that they deliver P (0x7fffffff in a slice without a seed) and L for every voxel.  No reach bounds them.
+ *   depth pass  : a block owns a strip of 32 columns of one (n, h) row with P and L of all D slices in LDS, as two arrays
+ *                 of [D][32] int32 (8 B x D x 32: a 32-lane LDS group reads 32 consecutive dwords of one slice, which is
+ *                 free of bank conflicts); lanes run along w and the search outwards in k runs on LDS.  A side is finished
+ *                 when A(k) > best -- not sq_edt3d_sq_f64's >=: an equidistant seed with a smaller label further out must
+ *                 still be seen -- and, without d2 and with R > 0, also when A(k) > R*R.  L is read only where the
+ *                 candidate's distance is <= best.  Depths whose strip exceeds the device's LDS per block
+ *                 (hipDeviceAttributeMaxSharedMemoryPerBlock: D > 640 at 160 KiB) take the same search on global memory;
+ *                 the environment variable SQ_ZONES3D_LDS=0, read per launch, selects that form for every depth.  Both
+ *                 give the same bits.
+ * workspace: sq_label_zones3d_workspace(N, D, H, W) bytes = 16 ceil(N D / 4) [per-slice flags] + 3 x 16 ceil(V / 4) [P, L and
+ * the row pass's labels, int32 each] + 2 V [the row pass's distances, u16] rounded up to 16, V = N D H W; -1 under
+ * sq_weightmap3d_workspace's conditions (a dimension < 1, D, H or W >= 30000, or 2^31 or more voxels).  16-B aligned.
+ * SQ_EINVAL with a message, before any launch: null labels, zones or workspace; a dimension < 1; D, H or W >= 30000; 2^31
+ * or more voxels; max_label outside 1 .. 2^21 - 1; max_distance outside 0 .. 46340; dz not finite or <= 0; a workspace that
+ * is not 16-B aligned or overlaps labels, zones or d2; zones overlapping d2; d2 not 8-B aligned.
+ *
+ * sq_zone_graph3d.  zones (N,D,H,W) int32; values outside 1 .. max_label count as 0.
+ *   stats (N, max_label + 1, 2) int64, [voxels, face] per label: voxels = the number of voxels of the zone, face = the
+ *       number of those on any of the volume's six faces (a voxel on an edge or a corner counts once).  Row 0 stays 0.
+ *   pairs (max_pairs, 5) int32 [volume, a, b, lateral, axial], a < b, in no particular order: lateral = the number of voxel
+ *       pairs (p, p + 1 along w) and (p, p + 1 along h) inside the volume in which one voxel has zone a and the other zone
+ *       b, both > 0; axial = the same for (p, p + 1 along d).  One row per distinct (volume, a, b) with lateral + axial > 0.
+ *       The two are kept apart because in an anisotropic stack a lateral face has area dz and an axial face area 1.
+ *   count, dropped (device int32): as in sq_zone_graph.
+ * The call clears stats, count, dropped and its table itself.  One wave per (n, d, h) row, one lane per voxel: the right
+ * neighbour comes by a shuffle, the lower and the deeper one by one coalesced load each; runs of equal (a, b) per direction
+ * are found with a ballot and their leader lane makes one insert-and-add into an open-addressing table in the workspace (a
+ * 64-bit key of (volume, a, b) claimed with a compare-and-swap, two 32-bit integer adds per slot -- 16 B -- the smallest
+ * power of two >= 2 max_pairs slots); voxels and face get one 64-bit add per run of equal zone.  A second kernel writes
+ * the rows.  Plain atomics on vector memory; sums of integers: the set of rows and every count are independent of the
+ * order in which the atomics arrive.
+ * workspace: sq_zone_graph3d_workspace(max_pairs) bytes = 16 per slot (-1: max_pairs outside 1 .. 2^28), 16-B aligned.
+ * SQ_EINVAL with a message, before any launch: a null pointer; N, D, H or W < 1; N >= 2^21; 2^31 or more voxels; max_label
+ * outside 1 .. 2^21 - 1; max_pairs outside 1 .. 2^28; a workspace that is not 16-B aligned or overlaps zones or an output;
+ * stats not 8-B aligned.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_label_zones3d_workspace(int N, int D, int H, int W);
+int sq_label_zones3d_i32(const int32_t *labels, int32_t *zones, double *d2, int N, int D, int H, int W, int max_label,
+                         int max_distance, double dz, void *workspace, void *stream);
+int64_t sq_zone_graph3d_workspace(int max_pairs);
+int sq_zone_graph3d(const int32_t *zones, int N, int D, int H, int W, int max_label, int64_t *stats, int32_t *pairs,
+                    int max_pairs, int32_t *count, int32_t *dropped, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -837,7 +837,7 @@ class VolumeTiler(object):
 
 
 def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise=True, want_logits=False, on_masks=None,
-                    postprocess=None):
+                    postprocess=None, on_volume=None):
     """Segment whole volumes brick by brick: `volumes` is an (N, Z, X, Y) uint8 | uint16 | float32 numpy array or memmap,
     `net` a UNet3D built at the brick shape (brick and margin in the array's (Z, X, Y) order).  Raw volume i+1 goes
     through two pinned Z-slab buffers of bounded size and is uploaded on a side stream while volume i runs: statistics,
@@ -847,7 +847,11 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     volume's device mask is handed to on_masks(i, mask (1, Z, X, Y)) instead, valid until volume i+2 is started, and
     the first value returned is None.  postprocess (a volumeops.VolumeCleanup or a step list) cleans each volume's
     stitched mask on the compute stream with net.n_outputs classes before anything else sees it: the cleaned mask is
-    what on_masks receives and what drains to the host.  Logits are not touched."""
+    what on_masks receives and what drains to the host.  Logits are not touched.  on_volume(i, raw, mask) is on_masks with
+    the raw volume (1, Z, X, Y) as it was uploaded, still in HBM, next to the mask -- segment_frames' on_batch for volumes;
+    the upload of volume i+2 waits for what the sink has queued on the current stream.  Pass one of the two sinks."""
+    if on_masks is not None and on_volume is not None:
+        raise ValueError('on_masks and on_volume are two forms of the same sink: pass one of them')
     arr = volumes
     if postprocess is not None:
         from .volumeops import VolumeCleanup
@@ -872,7 +876,7 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     ready = [torch.cuda.Event(), torch.cuda.Event()]            # volume k is complete in staged[k]
     freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[k]
     done = [torch.cuda.Event(), torch.cuda.Event()]             # mask_dev[k] / logits_dev[k] are complete
-    out_masks = None if on_masks is not None else np.empty((N, Z, X, Y), np.uint8)
+    out_masks = None if on_masks is not None or on_volume is not None else np.empty((N, Z, X, Y), np.uint8)
     out_logits = np.empty((N, Z, X, Y, n_out), np.float32) if want_logits else None
     cur = torch.cuda.current_stream(dev)
     for e in slab_sent + freed:
@@ -916,6 +920,8 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
                 tiler.scatter(net.logits(), logits_dev[k], first)
         if postprocess is not None:                             # the result lives in the cleaner's buffers: back into
             mask_dev[k].copy_(postprocess.apply(mask_dev[k], n_out))    # mask_dev[k], which stays valid until volume i+2
+        if on_volume is not None:                               # the sink reads staged[k]: it is free once its work is queued
+            on_volume(i, staged[k], mask_dev[k])
         freed[k].record(cur)
         done[k].record(cur)
         if on_masks is not None:

@@ -210,7 +210,35 @@ def _brick_volumes(params, options):
     return device, x, (bz, bx, by), margin, geometry
 
 
-def _segment_volume_bricks(params, options, cleanup=None):
+VOLUME_ANALYSIS_OPTIONS = ('measure', 'save_labels', 'neighbors', 'save_zones')
+
+
+def _parse_volume_analysis(params, options):
+    """options['measure'] / ['save_labels'] / ['neighbors'] / ['save_zones'] of SERVER_segment_volume, before any input is
+    opened: None without them, else a dict of what they ask for with the neighbour parameters checked and their defaults
+    filled in.  They need params['brick']; a bad value raises here."""
+    asked = [k for k in VOLUME_ANALYSIS_OPTIONS if options.get(k)]
+    if not asked:
+        return None
+    if params.get('brick') is None:
+        raise ValueError("options %s measure the volumes while they are in HBM, which the brick front end keeps them in: "
+                         "they need params['brick']" % ', '.join(repr(k) for k in asked))
+    want_neighbors = bool(options.get('neighbors'))
+    a = {'neighbors': want_neighbors, 'save_labels': bool(options.get('save_labels')),
+         'save_zones': want_neighbors and bool(options.get('save_zones')),
+         'min_area': int(params.get('min_area') or 1), 'max_area': params.get('max_area')}
+    if a['min_area'] < 1 or (a['max_area'] is not None and int(a['max_area']) < a['min_area']):
+        raise ValueError("params['min_area'] / params['max_area'] must satisfy 1 <= min_area <= max_area, got %r / %r"
+                         % (params.get('min_area'), params.get('max_area')))
+    if want_neighbors:
+        from .analysis.neighbors import check_params, check_spacing
+        a['d_thresh'], a['zone_reach'], a['neighbor_seeds'] = check_params(
+            params.get('d_thresh', 100.0), params.get('zone_reach'), params.get('neighbor_seeds', 'objects'))
+        a['spacing'] = check_spacing(params.get('spacing', 1.0))
+    return a
+
+
+def _segment_volume_bricks(params, options, cleanup=None, analysis=None):
     """SERVER_segment_volume with params['brick']: volumes of any size, raw, brick by brick (frontend.segment_volumes)."""
     device, x, (bz, bx, by), margin, geometry = _brick_volumes(params, options)
     out_dir = params['output']
@@ -232,7 +260,7 @@ def _segment_volume_bricks(params, options, cleanup=None):
     net.predict(torch.zeros((min(batch, geometry.per_volume), bz, bx, by, 1), device=device))   # first-launch costs
     torch.cuda.synchronize()
     per_volume = {}
-    masks = np.zeros((N, Z, X, Y), np.uint8) if want_centroids else None
+    masks = np.zeros((N, Z, X, Y), np.uint8) if want_centroids or analysis else None
 
     def sink(i, m):                                            # centroids straight from the mask in HBM: no second upload
         from .centroids import mask_centroids
@@ -241,11 +269,43 @@ def _segment_volume_bricks(params, options, cleanup=None):
         coords[:, 0] = i
         per_volume[i] = coords
 
+    tables, neighbor_tables = {}, {}
+    num_classes = int(net_p.get('num_outputs', 2))
+    if analysis:
+        bounded = analysis['min_area'] != 1 or analysis['max_area'] is not None
+        label_stack = np.empty((N, Z, X, Y), np.int32) if analysis['save_labels'] else None
+        zone_stack = np.empty((N, Z, X, Y), np.int32) if analysis['save_zones'] else None
+
+    def measure_sink(i, raw, m):                               # objects against the raw volume, both in HBM as they lie
+        from .objects import measure_objects
+        t = measure_objects(m, image=raw, min_area=analysis['min_area'], max_area=analysis['max_area'],
+                            labels=label_stack is not None or analysis['neighbors'], filtered_mask=bounded)
+        if label_stack is not None:
+            label_stack[i] = t.labels[0].cpu().numpy()
+        if analysis['neighbors']:                               # on the kept objects' labels, while the volume is in HBM
+            from .analysis.neighbors import neighbors_from_objects
+            nt = neighbors_from_objects(t, num_classes, analysis['d_thresh'], analysis['zone_reach'],
+                                        analysis['neighbor_seeds'], return_zones=zone_stack is not None,
+                                        spacing=analysis['spacing'])
+            if zone_stack is not None:
+                zone_stack[i] = nt.zones[0].cpu().numpy()
+                nt.zones = None
+            neighbor_tables[i] = nt
+        kept = t.mask if bounded else m                         # what mask.npy and the centroid path see
+        t.labels = t.mask = None
+        tables[i] = t
+        if want_centroids:
+            sink(i, kept)
+        else:
+            masks[i] = kept[0].cpu().numpy()
+
     t0 = time.time()
     out, logits = segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch,
                                   normalise=bool(params.get('normalise', True)), want_logits=want_logits,
-                                  on_masks=sink if want_centroids else None, **({'postprocess': cleanup} if cleanup else {}))
-    if not want_centroids:
+                                  on_masks=sink if want_centroids and not analysis else None,
+                                  **({'postprocess': cleanup} if cleanup else {}),
+                                  **({'on_volume': measure_sink} if analysis else {}))
+    if not (want_centroids or analysis):
         masks = out
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'mask.npy'), masks)
@@ -264,6 +324,25 @@ def _segment_volume_bricks(params, options, cleanup=None):
             for i in sorted(per_volume):
                 cw.add_frame(i, per_volume[i])
         info['centroids'] = {'file': os.path.basename(cw.filename), 'objects': int(sum(len(v) for v in per_volume.values()))}
+    if analysis:
+        from .objects import ObjectTable
+        table = ObjectTable.concatenate([tables[i] for i in range(N)], list(range(N)), N)
+        np.savez(os.path.join(out_dir, 'objects.npz'), **table.columns())
+        if label_stack is not None:
+            np.save(os.path.join(out_dir, 'labels.npy'), label_stack)
+        info['objects'] = {'count': len(table), 'found': int(table.found), 'min_area': analysis['min_area'],
+                           'max_area': None if analysis['max_area'] is None else int(analysis['max_area']),
+                           'with_intensity': True}
+        if analysis['neighbors']:
+            from .analysis.neighbors import NeighborTable
+            ntable = NeighborTable.concatenate([neighbor_tables[i] for i in range(N)], list(range(N)), N)
+            np.savez(os.path.join(out_dir, 'neighbors.npz'), **ntable.columns())
+            if zone_stack is not None:
+                np.save(os.path.join(out_dir, 'zones.npy'), zone_stack)
+            info['neighbors'] = {'objects': len(ntable), 'pairs': int(ntable.n_pairs),
+                                 'pairs_removed': int(ntable.n_pairs_removed), 'num_classes': num_classes,
+                                 'd_thresh': analysis['d_thresh'], 'zone_reach': analysis['zone_reach'],
+                                 'neighbor_seeds': analysis['neighbor_seeds'], 'spacing': analysis['spacing']}
     with open(os.path.join(out_dir, 'segment_volume.json'), 'w') as f:
         json.dump(info, f, indent=2)
     logger.info('Segmented {volumes} volumes in {seconds:.3f}s on {device}, {bricks_per_volume} bricks each'.format(**info))
@@ -291,17 +370,30 @@ def SERVER_segment_volume(params, options):
     written out, under ``volume_postprocess``.  A bad step list raises before any input is opened; without the key
     nothing changes.  params['postprocess'], the planar list, stays refused.
 
+    With ``brick``, options['measure'] measures every volume's objects in HBM (objects.measure_objects on the cleaned mask as
+    it lies, D0, D1, D2 = Z, X, Y, 6-connected, against the RAW volume): ``objects.npz`` holds ObjectTable.columns() with
+    ``frame`` the volume index, ``segment_volume.json`` an ``objects`` record, options['save_labels'] adds ``labels.npy``
+    (N,Z,X,Y) int32.  params['min_area'] / params['max_area'] (inclusive, in voxels) drop objects outside the range, and
+    ``mask.npy`` and the centroid file then describe the mask without them.  options['neighbors'] (implies measure) finds
+    every object's neighbours in 3-D (analysis/neighbors.py, neighbors3d: touching zones of influence in the z-stack):
+    ``neighbors.npz`` holds the volumetric NeighborTable.columns(), the json a ``neighbors`` record with the defaults filled
+    in, options['save_zones'] adds ``zones.npy`` (N,Z,X,Y) int32.  params['d_thresh'] (100.0, in in-plane pixels),
+    params['zone_reach'] (none), params['neighbor_seeds'] ('objects') and params['spacing'] (1.0: the slice spacing in
+    in-plane pixels, SERVER_train_volume's key); a bad value raises before any input is opened, and so do these four options
+    without ``brick``.  Without them every file is what it was.
+
     ``segment_volume.json``: ``seconds`` / ``mvoxels_per_s`` cover the volumes (upload, network, download);
     ``setup_seconds`` is weights plus one warm-up volume."""
     if params.get('postprocess') is not None:
         raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope "
                          "(params['volume_postprocess'] cleans them)")
     cleanup = _parse_volume_postprocess(params)                 # before anything is opened
+    analysis = _parse_volume_analysis(params, options)          # likewise
     import torch
     from .networks.unet import UNet3D
 
     if params.get('brick') is not None:
-        return _segment_volume_bricks(params, options, cleanup)
+        return _segment_volume_bricks(params, options, cleanup, analysis)
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
     out_dir = params['output']

@@ -13,9 +13,10 @@ are not covered under replay.  Every result equals the scipy restatement in
 tests/volume_cleanup_cases.py exactly (tests/test_gpu_volume_cleanup.py).
 
 Not built, each on purpose: a 3-D ``split`` (the planar regrowth cut has no volume kernel); the 18-neighbour structure
-(generate_binary_structure(3, 2)); ``measure`` and ``neighbors`` for volumes in the jobs (objects.measure_objects accepts 4-D
-masks, the job wiring is a follow-up); more than MORPH3D_MAX_ITER iterations in one launch (use two steps, see the header
-for when they compose); anisotropic, spacing-aware structuring elements.
+(generate_binary_structure(3, 2)); more than MORPH3D_MAX_ITER iterations in one launch (use two steps, see the header
+for when they compose); anisotropic, spacing-aware structuring elements.  What follows the clean-up -- ``measure`` and
+``neighbors`` for volumes -- is SERVER_segment_volume's options of those names with ``brick`` (objects.measure_objects and
+analysis/neighbors.py's neighbors3d on each cleaned mask in HBM).
 """
 import torch
 
