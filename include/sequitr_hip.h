@@ -768,6 +768,45 @@ int sq_conv2d_nhwc_mosaic_bf16(const void *x, const void *wp, const float *bias,
 #define SQ_PLAN_WSCALE 1
 int sq_conv_plan(int family, int form, int N, int H, int W, int Cin, int Cout, int K, int act, int flags, const int *mosaic,
                  int64_t workspace_bytes, int *out);
+/* Tile walk of the persistent f32 inference kernels, computed on the host without a HIP call from the functions the launchers
+ * take their grids from.  Block b of a grid of G takes item b, b + G, b + 2G, ... (a 16 x 16 pixel tile; for the transpose
+ * conv a (row tile, pixel tile) pair), so the busiest block walks ceil(items / G) of them and the idlest floor(items / G).
+ * form: SQ_PLAN_PLAIN (sq_conv2d_nhwc_fwd_f32), _POOL (sq_conv3x3_pool_fwd_f32), _CONCAT (sq_conv2d_concat_nhwc_fwd_f32,
+ *       Cin = both sources' channels), _FIRSTBLOCK (sq_conv3x3_first_block_fwd_f32: Cin 1, Cout 16; flags SQ_PLAN_POOLED when
+ *       it also pools), _UP (sq_convT_conv3x3_fwd_f32: Cin 16, Cout 16, (N, H, W) of the output), _HEAD
+ *       (sq_conv3x3_head_fwd_f32: Cout 16, head_c classes), _CONVT (sq_convT2x2s2_nhwc_fwd_f32: (N, H, W) of the input, K unused).
+ * flags: SQ_PLAN_WSCALE as for sq_conv_plan, SQ_PLAN_POOLED.  The switches SQ_CONV_L0, SQ_CONV_STAGE32, SQ_CONVT_V2 and
+ * SQ_CONVT_WNI act as on the launchers.
+ * out[SQ_WALK_N]: [SQ_WALK_KERNEL] SQ_WALK_L0 (level-0 kernel), SQ_WALK_V2 (generic kernel), SQ_WALK_CONVT (transpose conv v2)
+ * or SQ_WALK_NONE (a transpose conv the v2 kernel declines: no walk, everything else 0); [SQ_WALK_G] blocks along the walk;
+ * [SQ_WALK_TMIN], [SQ_WALK_TMAX] items of the idlest / busiest block; [SQ_WALK_GX], [_GY], [_GN] the stride in tile
+ * coordinates, G = gn tiles_x tiles_y + gy tiles_x + gx (the level-0 kernel is handed the triple; the generic kernel derives
+ * the same one); [SQ_WALK_MTILES] row tiles of the transpose conv (4 Cout / 128); [SQ_WALK_CBLOCKS] channel blocks, each
+ * walking the same tiles (gridDim.y of the generic kernel, else 1); [SQ_WALK_ITEMS] items of the walk (pixel tiles; for the
+ * transpose conv row tiles x pixel tiles, item = pixel tile * mtiles + row tile); [SQ_WALK_TILEPX] pixels of a pixel tile
+ * (256; transpose conv: 32, 64 or 128 consecutive input pixels).  Returns SQ_OK, or SQ_EINVAL for a call the entry point
+ * would refuse. */
+#define SQ_PLAN_UP 11
+#define SQ_PLAN_HEAD 12
+#define SQ_PLAN_CONVT 13
+#define SQ_PLAN_POOLED 2
+#define SQ_WALK_NONE 0
+#define SQ_WALK_L0 1
+#define SQ_WALK_V2 2
+#define SQ_WALK_CONVT 3
+#define SQ_WALK_KERNEL 0
+#define SQ_WALK_G 1
+#define SQ_WALK_TMIN 2
+#define SQ_WALK_TMAX 3
+#define SQ_WALK_GX 4
+#define SQ_WALK_GY 5
+#define SQ_WALK_GN 6
+#define SQ_WALK_MTILES 7
+#define SQ_WALK_CBLOCKS 8
+#define SQ_WALK_ITEMS 9
+#define SQ_WALK_TILEPX 10
+#define SQ_WALK_N 11
+int sq_conv_walk_plan(int form, int N, int H, int W, int Cin, int Cout, int K, int act, int flags, int head_c, int *out);
 int sq_conv2d_nhwc_wgrad_scaled_bf16(const void *x, const void *dy, float *dw, float *db, float *workspace, int N, int H,
                                      int W, int Cin, int Cout, int K, float dw_scale, void *stream);
 int sq_conv2d_nhwc_wgrad_mosaic_bf16(const void *x, const void *dy, float *dw, float *db, float *workspace, int Nimg, int h,

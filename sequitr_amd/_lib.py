@@ -227,6 +227,7 @@ SIGNATURES = {
     "sq_conv2d_nhwc_dgrad_actgate_bf16": (c_int, [c_void_p] * 3 + [c_int, c_void_p] + [c_int] * 6 + [c_void_p]),
     "sq_conv2d_nhwc_mosaic_bf16": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p, c_int64, c_void_p]),
     "sq_conv_plan": (c_int, [c_int] * 10 + [c_void_p, c_int64, c_void_p]),
+    "sq_conv_walk_plan": (c_int, [c_int] * 10 + [c_void_p]),
     "sq_conv2d_nhwc_wgrad_scaled_bf16": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float, c_void_p]),
     "sq_conv2d_nhwc_wgrad_mosaic_bf16": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_float, c_void_p]),
     "sq_conv2d_nhwc_wgrad_group_workspace_bf16": (c_int64, [c_void_p, c_int]),

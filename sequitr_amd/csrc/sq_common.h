@@ -26,6 +26,28 @@ int sq_plan_mosaic_splitk(int Nimg, int h, int w, int Cin, int Cout, int R, int 
 int sq_plan_f32_bn(int64_t ntiles, int Cout);
 bool sq_plan_f32_stage32(int bn, int KS, int KC, int Cin, bool concat);
 bool sq_plan_l0_takes(int mode, int cout, int act, int H, int W, bool concat, int head_c, bool pooled);
+// persistent grids of the f32 inference kernels (sq_conv_f32_l0.hip, sq_conv_f32_v2.hip, sq_convt_f32_v2.hip): block b takes
+// item b, b + G, b + 2G, ...  The resident blocks per CU of every form and the grid G, shared by launch_l0 / launch_v2 /
+// launch_ct and sq_conv_walk_plan
+#ifndef SQ_L0_OCC
+#define SQ_L0_OCC 4                  // resident blocks per CU of the plain / FIRST forms (A/B switch)
+#endif
+#ifndef SQ_L0_UP_OCC
+#define SQ_L0_UP_OCC 2               // resident blocks per CU of the UP form: 190 registers unspilled; at 3 (168) the prefetch registers spill: 625 vs 486 us
+#endif
+#ifndef SQ_CT_WNI
+#define SQ_CT_WNI 1                 // default pixel-tile width / 32 (env SQ_CONVT_WNI overrides; 1: 5.133, 2: 5.140, 4: 5.162 ms per inference step)
+#endif
+constexpr int SQ_CT_BM = 128;        // rows (4 Cout) of a transpose-conv block tile
+constexpr int sq_l0_occ(bool up, int nb) { return up ? SQ_L0_UP_OCC : (nb == 2 ? 2 : SQ_L0_OCC); }
+constexpr int sq_v2_occ(int bn, int kc, bool up) { return up ? 3 : ((bn >= 64 || kc == 32) ? 2 : (bn >= 32 ? 3 : 4)); }   // LDS-limited
+constexpr int sq_ct_occ(int wni) { return wni == 4 ? 2 : (wni == 2 ? 3 : 4); }
+int sq_plan_l0_grid(int ntiles, int occ);                                   // G of the level-0 kernel
+void sq_plan_tile_stride(int G, int tiles_x, int tiles_y, int *gx, int *gy, int *gn);   // G = gn tiles_x tiles_y + gy tiles_x + gx
+int sq_plan_v2_grid(int ntiles, int cblocks, int occ, int *tiles_per_block); // gridDim.x of the generic kernel (cblocks = gridDim.y)
+int sq_plan_ct_wni();                                                       // pixel-tile width / 32 of the transpose conv (1, 2 or 4)
+bool sq_plan_ct_takes(int N, int H, int W, int Cin, int Cout);              // shapes sq_convT_v2_launch keeps
+int sq_plan_ct_grid(int total, int mtiles, int occ);                        // G of the transpose conv over mtiles x ntiles work items
 // the plan of sq_conv2d_nhwc_wgrad_f32 (sq_conv_wgrad_f32.hip) as sq_wgrad_plan reports it; SQ_EINVAL: no kernel takes the shape
 int sq_wgrad_f32_plan(int N, int H, int W, int Cin, int Cout, int K, int64_t *out);
 

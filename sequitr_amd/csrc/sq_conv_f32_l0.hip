@@ -32,12 +32,7 @@
 #ifndef SQ_L0_SETPRIO
 #define SQ_L0_SETPRIO 1              // wave priority low while feeding the matrix pipe, high while staging / storing (A/B switch)
 #endif
-#ifndef SQ_L0_OCC
-#define SQ_L0_OCC 4                  // resident blocks per CU of the plain / FIRST forms (A/B switch)
-#endif
-#ifndef SQ_L0_UP_OCC
-#define SQ_L0_UP_OCC 2               // resident blocks per CU of the UP form: 190 registers unspilled; at 3 (168) the prefetch registers spill: 625 vs 486 us
-#endif
+// SQ_L0_OCC, SQ_L0_UP_OCC (resident blocks per CU): sq_common.h, with the grid rules the walk plan shares
 
 namespace {
 
@@ -79,7 +74,7 @@ __device__ __forceinline__ void row_transpose(float &a0, float &a1, float &a2, f
 __device__ __forceinline__ float relu(float v) { return __builtin_fmaxf(v, 0.0f); }   // NaN -> 0, -0 -> +0 like (v > 0 ? v : 0)
 
 template <int MODE, int EPI, int BRIDGE, int NB>            // NB: output channels / 16 (2: the 16 -> 32 first conv of level 1)
-__global__ __launch_bounds__(256, (MODE == M_UP ? SQ_L0_UP_OCC : (NB == 2 ? 2 : SQ_L0_OCC))) void conv_l0_kernel(const L0Args a) {
+__global__ __launch_bounds__(256, sq_l0_occ(MODE == M_UP, NB)) void conv_l0_kernel(const L0Args a) {
     static_assert(NB == 1 || (NB == 2 && MODE == M_PLAIN && EPI == EPI_STORE), "32 output channels: the plain form only");
     constexpr int CO = 16 * NB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -604,12 +599,9 @@ int launch_l0(const L0Args &a0, hipStream_t st) {
     a.tiles_x = a.W / TW;
     a.tiles_y = a.H / TH;
     a.ntiles = a.tiles_x * a.tiles_y * a.N;
-    const int want = 256 * (MODE == M_UP ? SQ_L0_UP_OCC : (NB == 2 ? 2 : SQ_L0_OCC));
-    const int G = a.ntiles < want ? a.ntiles : want;
-    const int per_image = a.tiles_x * a.tiles_y;
-    a.gn = G / per_image;
-    a.gy = (G % per_image) / a.tiles_x;
-    a.gx = (G % per_image) % a.tiles_x;
+    // the grid and its stride in tile coordinates: sq_plan_l0_grid / sq_plan_tile_stride, shared with sq_conv_walk_plan
+    const int G = sq_plan_l0_grid(a.ntiles, sq_l0_occ(MODE == M_UP, NB));
+    sq_plan_tile_stride(G, a.tiles_x, a.tiles_y, &a.gx, &a.gy, &a.gn);
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, a);
     return sq_check_launch("conv_l0");
 }

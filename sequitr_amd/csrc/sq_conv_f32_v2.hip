@@ -75,14 +75,14 @@ struct Cfg2 {
     static constexpr int WITEMS = WROWS * (BN / 4);
     static constexpr int WSLOTS = (WITEMS + 255) / 256;
     static constexpr int NSTEP = KS * KS * (KC / 4);
-    static constexpr int OCC = (BN >= 64 || KC == 32) ? 2 : (BN >= 32 ? 3 : 4);  // blocks per CU (LDS-limited)
+    static constexpr int OCC = sq_v2_occ(BN, KC, false);     // blocks per CU (LDS-limited)
     static_assert(KC <= 16 || (KC == 32 && BN == 32), "the 32-channel stage exists for the 32 -> 32 layers (LDS: 2 blocks per CU)");
     static_assert((XS_FLOATS * 4) % 16 == 0, "weight slab must start 16-B aligned");
     static_assert((WS_FLOATS * 4) % 16 == 0, "input patch must start 16-B aligned");
 };
 
 template <int BN, int KS, int KC, int MODE>            // MODE 0 plain, 1 FIRST, 2 UP
-__global__ __launch_bounds__(256, (MODE == 2 ? 3 : Cfg2<BN, KS, KC>::OCC)) void conv_mfma_f32_v2_kernel(
+__global__ __launch_bounds__(256, sq_v2_occ(BN, KC, MODE == 2)) void conv_mfma_f32_v2_kernel(
     const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
     float *__restrict__ y, int N, int H, int W, int Cin, int Cout, float wscale, int act,
     int tiles_x, int tiles_y, int ntiles, int tiles_per_block, SqConvEpi epi) {
@@ -703,12 +703,9 @@ int launch_v2(const float *x, const float *w, const float *bias, float *y, int N
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     const int ntiles = tiles_x * tiles_y * N;
     const int gy = (Cout + BN - 1) / BN;
-    // persistent grid: about OCC resident blocks per CU over both grid dimensions
-    int want = (256 * (MODE == 2 ? 3 : C::OCC) + gy - 1) / gy;
-    if (want < 1) want = 1;
-    int tpb = (ntiles + want - 1) / want;
-    if (tpb < 1) tpb = 1;
-    const int gx = (ntiles + tpb - 1) / tpb;
+    // persistent grid: about OCC resident blocks per CU over both grid dimensions (sq_plan_v2_grid, shared with sq_conv_walk_plan)
+    int tpb;
+    const int gx = sq_plan_v2_grid(ntiles, gy, sq_v2_occ(BN, KC, MODE == 2), &tpb);
     hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, st, x, w, bias, y, N, H, W, Cin, Cout,
                        wscale, act, tiles_x, tiles_y, ntiles, tpb, epi);
     return sq_check_launch("sq_conv2d_nhwc_fwd_f32(v2)");

@@ -2,6 +2,8 @@
 // and the split-K factor a call would launch with, as plain host functions.  The launchers of sq_conv_bf16.hip,
 // sq_conv_f32_v2.hip and sq_conv_f32_l0.hip take their choices from here; sq_conv_plan reports the same choices without a HIP
 // call, so that the CPU suite can pin the plans of the real workloads and check that the kernel tests reach every one.
+// sq_conv_walk_plan does the same for the persistent grids of the f32 inference kernels (the level-0 and generic convs, the
+// transpose conv): the grid and how many tiles a block walks, from the helpers launch_l0 / launch_v2 / launch_ct call.
 #include "sq_conv_epi.h"
 #include <stdlib.h>
 
@@ -64,6 +66,133 @@ bool sq_plan_l0_takes(int mode, int cout, int act, int H, int W, bool concat, in
     if (head_c && head_c != 2) return false;
     if (head_c && pooled) return false;
     return true;
+}
+
+int sq_plan_l0_grid(int ntiles, int occ) {
+    const int want = 256 * occ;
+    return ntiles < want ? ntiles : want;
+}
+
+void sq_plan_tile_stride(int G, int tiles_x, int tiles_y, int *gx, int *gy, int *gn) {
+    const int per_image = tiles_x * tiles_y;
+    *gn = G / per_image;
+    *gy = (G % per_image) / tiles_x;
+    *gx = (G % per_image) % tiles_x;
+}
+
+int sq_plan_v2_grid(int ntiles, int cblocks, int occ, int *tiles_per_block) {
+    int want = (256 * occ + cblocks - 1) / cblocks;
+    if (want < 1) want = 1;
+    int tpb = (ntiles + want - 1) / want;
+    if (tpb < 1) tpb = 1;
+    *tiles_per_block = tpb;
+    return (ntiles + tpb - 1) / tpb;
+}
+
+int sq_plan_ct_wni() {
+    static const int wni = [] { const char *v = getenv("SQ_CONVT_WNI"); return v ? atoi(v) : SQ_CT_WNI; }();   // read once per process
+    return wni == 4 || wni == 1 ? wni : 2;
+}
+
+bool sq_plan_ct_takes(int N, int H, int W, int Cin, int Cout) {
+    const char *e = getenv("SQ_CONVT_V2");                          // SQ_CONVT_V2=0: A/B switch back to the 64 x 64 kernel
+    if (e && e[0] == '0') return false;
+    const size_t P = (size_t)N * H * W;
+    if (Cin % 32 != 0 || Cout % 32 != 0) return false;
+    if (P * 4 * Cout * 4 >= ((size_t)1 << 31) || P * Cin * 4 >= ((size_t)1 << 31)) return false;
+    return true;
+}
+
+int sq_plan_ct_grid(int total, int mtiles, int occ) {
+    const int want = 256 * occ;
+    int G = total < want ? total : want;
+    if (G > mtiles) G -= G % mtiles;                                // the row tiles of one pixel tile start together
+    return G;
+}
+
+// The walk of the persistent f32 inference kernels: which kernel takes the call, its grid, and how many items the busiest and the
+// idlest block take (block b takes item b, b + G, ...: ceil and floor of items / G).  The dispatch conditions are those of the
+// entry points (sq_conv_mfma_v2, sq_conv3x3_pool_fwd_f32, ..., sq_convT_v2_launch); the grids come from the launchers' helpers.
+extern "C" int sq_conv_walk_plan(int form, int N, int H, int W, int Cin, int Cout, int K, int act, int flags, int head_c,
+                                 int *out) {
+    SQ_REQUIRE(out, "sq_conv_walk_plan: null out");
+    SQ_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "sq_conv_walk_plan: bad shape");
+    SQ_REQUIRE(act >= SQ_ACT_NONE && act <= SQ_ACT_LEAKY, "sq_conv_walk_plan: bad activation %d", act);
+    for (int i = 0; i < SQ_WALK_N; ++i) out[i] = 0;
+    if (form == SQ_PLAN_CONVT) {                                    // (N, H, W): the low-resolution input
+        if (!sq_plan_ct_takes(N, H, W, Cin, Cout)) return SQ_OK;    // SQ_WALK_NONE: the 64 x 64 kernel, no walk
+        const int wni = sq_plan_ct_wni();
+        const int mtiles = 4 * Cout / SQ_CT_BM, ntiles = (N * H * W + 32 * wni - 1) / (32 * wni);
+        const int total = mtiles * ntiles, G = sq_plan_ct_grid(total, mtiles, sq_ct_occ(wni));
+        out[SQ_WALK_KERNEL] = SQ_WALK_CONVT;
+        out[SQ_WALK_G] = G;
+        out[SQ_WALK_TMIN] = total / G;
+        out[SQ_WALK_TMAX] = (total + G - 1) / G;
+        out[SQ_WALK_MTILES] = mtiles;
+        out[SQ_WALK_CBLOCKS] = 1;
+        out[SQ_WALK_ITEMS] = total;
+        out[SQ_WALK_TILEPX] = 32 * wni;
+        return SQ_OK;
+    }
+    const bool pooled = form == SQ_PLAN_POOL || (form == SQ_PLAN_FIRSTBLOCK && (flags & SQ_PLAN_POOLED));
+    SQ_REQUIRE(!pooled || (H % 2 == 0 && W % 2 == 0), "sq_conv_walk_plan: pooling needs even H, W");
+    int mode = 0, bn = 16, kc = 16;                                 // of the generic kernel's instantiation
+    bool offer = false;                                             // the entry point asks the level-0 kernel first
+    switch (form) {
+    case SQ_PLAN_PLAIN:
+        SQ_REQUIRE((K == 1 || K == 3) && Cout % 4 == 0 && (Cin % 16 == 0 || Cin == 8),
+                   "sq_conv_walk_plan: the f32 v2 kernels take Cin %% 16 == 0 (or 8), Cout %% 4 == 0");
+        offer = Cin == 16 && (Cout == 16 || Cout == 32) && K == 3 && !(flags & SQ_PLAN_WSCALE);
+        break;
+    case SQ_PLAN_POOL:
+        SQ_REQUIRE(K == 3 && Cin % 16 == 0 && Cout % 4 == 0, "sq_conv_walk_plan: the pooled form is 3x3, Cin %% 16 == 0, Cout %% 4 == 0");
+        offer = Cin == 16 && Cout == 16;
+        break;
+    case SQ_PLAN_CONCAT:
+        SQ_REQUIRE((K == 1 || K == 3) && Cin % 32 == 0 && Cout % 4 == 0, "sq_conv_walk_plan: concat takes Cin = 2 Ca, Ca %% 16 == 0");
+        break;
+    case SQ_PLAN_FIRSTBLOCK:
+        SQ_REQUIRE(K == 3 && Cin == 1 && Cout == 16 && act == SQ_ACT_RELU, "sq_conv_walk_plan: the first block is 1 -> 16 -> 16, ReLU");
+        offer = true;
+        mode = 1;
+        break;
+    case SQ_PLAN_UP:                                                // (N, H, W): the output
+        SQ_REQUIRE(K == 3 && Cin == 16 && Cout == 16 && H % 2 == 0 && W % 2 == 0, "sq_conv_walk_plan: the up block is 16 -> 16 at even H, W");
+        offer = true;
+        mode = 2;
+        break;
+    case SQ_PLAN_HEAD:
+        SQ_REQUIRE(K == 3 && Cin % 16 == 0 && Cout == 16 && head_c >= 1 && head_c <= 4, "sq_conv_walk_plan: the head is Cin -> 16 -> head_c (1..4)");
+        offer = Cin == 16;
+        break;
+    default:
+        SQ_REQUIRE(false, "sq_conv_walk_plan: form %d has no persistent f32 kernel", form);
+    }
+    SQ_REQUIRE((size_t)N * H * W * (size_t)(Cin > Cout ? Cin : Cout) * 4 < ((size_t)1 << 31), "sq_conv_walk_plan: tensors must be < 2 GiB");
+    const int tiles_x = (W + TILE - 1) / TILE, tiles_y = (H + TILE - 1) / TILE, ntiles = (int)ntiles_of(N, H, W);
+    int G, cblocks = 1;
+    if (offer && sq_plan_l0_takes(mode, Cout, act, H, W, false, form == SQ_PLAN_HEAD ? head_c : 0, pooled)) {
+        out[SQ_WALK_KERNEL] = SQ_WALK_L0;
+        G = sq_plan_l0_grid(ntiles, sq_l0_occ(mode == 2, Cout / 16));
+    } else {
+        if (form == SQ_PLAN_PLAIN || form == SQ_PLAN_POOL || form == SQ_PLAN_CONCAT) {   // dispatch_bn
+            kc = Cin % 16 == 0 ? 16 : 8;
+            bn = sq_plan_f32_bn(ntiles, Cout);
+            if (sq_plan_f32_stage32(bn, K, kc, Cin, form == SQ_PLAN_CONCAT)) kc = 32;
+        }
+        cblocks = (Cout + bn - 1) / bn;
+        int tpb;
+        out[SQ_WALK_KERNEL] = SQ_WALK_V2;
+        G = sq_plan_v2_grid(ntiles, cblocks, sq_v2_occ(bn, kc, mode == 2), &tpb);
+    }
+    out[SQ_WALK_G] = G;
+    out[SQ_WALK_TMIN] = ntiles / G;
+    out[SQ_WALK_TMAX] = (ntiles + G - 1) / G;
+    sq_plan_tile_stride(G, tiles_x, tiles_y, &out[SQ_WALK_GX], &out[SQ_WALK_GY], &out[SQ_WALK_GN]);
+    out[SQ_WALK_CBLOCKS] = cblocks;
+    out[SQ_WALK_ITEMS] = ntiles;
+    out[SQ_WALK_TILEPX] = TILE * TILE;
+    return SQ_OK;
 }
 
 extern "C" int sq_conv_plan(int family, int form, int N, int H, int W, int Cin, int Cout, int K, int act, int flags,

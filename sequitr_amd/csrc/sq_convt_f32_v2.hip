@@ -19,16 +19,14 @@
 #include <stdlib.h>
 #include "sq_common.h"
 
-#ifndef SQ_CT_WNI
-#define SQ_CT_WNI 1                 // default pixel-tile width / 32 (env SQ_CONVT_WNI overrides; 1: 5.133, 2: 5.140, 4: 5.162 ms per inference step)
-#endif
+// SQ_CT_WNI (default pixel-tile width / 32): sq_common.h, with the grid rules the walk plan shares
 #ifndef SQ_CT_FRAG_DBUF
 #define SQ_CT_FRAG_DBUF 0
 #endif
 
 namespace {
 
-constexpr int BM = 128, KCH = 32;             // the pixel tile is 32 * WNI wide (template): 128 or 64
+constexpr int BM = SQ_CT_BM, KCH = 32;        // the pixel tile is 32 * WNI wide (template): 128 or 64
 constexpr int RS = 40;                          // floats per staged row: [half][kk][s] + 8 of padding
 constexpr int AS_FLOATS = BM * RS;
 constexpr unsigned OOB = 0x80000000u;
@@ -46,7 +44,7 @@ struct CtArgs {
 // 2: 128 x 64 tiles, 64 x 32 per wave -- half the accumulators and bridge operands, three blocks per CU: a block's epilogue
 // (its share of the bridge + output traffic) then overlaps two other blocks' MFMAs instead of one
 template <int BRIDGE, int WNI>
-__global__ __launch_bounds__(256, (WNI == 4 ? 2 : (WNI == 2 ? 3 : 4))) void convT2x2_v2_kernel(const CtArgs a) {
+__global__ __launch_bounds__(256, sq_ct_occ(WNI)) void convT2x2_v2_kernel(const CtArgs a) {
     constexpr int BN = 32 * WNI;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *as = smem;
@@ -274,9 +272,7 @@ int launch_ct(const CtArgs &a0, hipStream_t st) {
         attr_set = true;
     }
     const int total = a.mtiles * a.ntiles;
-    const int want = 256 * (WNI == 4 ? 2 : (WNI == 2 ? 3 : 4));
-    int G = total < want ? total : want;
-    if (G > a.mtiles) G -= G % a.mtiles;                            // the row tiles of one pixel tile start together
+    const int G = sq_plan_ct_grid(total, a.mtiles, sq_ct_occ(WNI));   // shared with sq_conv_walk_plan
     hipLaunchKernelGGL(kern, dim3(G), dim3(256), lds, st, a);
     return sq_check_launch("sq_convT2x2s2_nhwc_fwd_f32(v2)");
 }
@@ -286,16 +282,13 @@ int launch_ct(const CtArgs &a0, hipStream_t st) {
 // internal entry used by sq_convT2x2s2_nhwc_fwd_f32 (sq_convt_loss.hip); SQ_NOT_MINE when the shape is not this kernel's
 int sq_convT_v2_launch(const float *x, const float *w, const float *bias, const float *skip, float *y, int N, int H,
                        int W, int Cin, int Cout, int bridge, hipStream_t st) {
-    const char *e = getenv("SQ_CONVT_V2");
-    if (e && e[0] == '0') return SQ_NOT_MINE;
+    if (!sq_plan_ct_takes(N, H, W, Cin, Cout)) return SQ_NOT_MINE;  // SQ_CONVT_V2=0 and the shapes; shared with sq_conv_walk_plan
     const size_t P = (size_t)N * H * W;
-    if (Cin % 32 != 0 || Cout % 32 != 0) return SQ_NOT_MINE;
-    if (P * 4 * Cout * 4 >= ((size_t)1 << 31) || P * Cin * 4 >= ((size_t)1 << 31)) return SQ_NOT_MINE;
     CtArgs a = {};
     a.x = x; a.w = w; a.bias = bias; a.skip = skip; a.y = y;
     a.P = (int)P; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.mtiles = 4 * Cout / BM;
-    static const int wni = [] { const char *v = getenv("SQ_CONVT_WNI"); return v ? atoi(v) : SQ_CT_WNI; }();   // A/B switch: 4 or 2
+    const int wni = sq_plan_ct_wni();                               // A/B switch SQ_CONVT_WNI: 4 or 2
     if (wni == 4) {
         switch (bridge) {
             case SQ_BRIDGE_ADD: return launch_ct<SQ_BRIDGE_ADD, 4>(a, st);

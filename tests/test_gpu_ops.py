@@ -88,9 +88,11 @@ def test_convT_bridge_bit_exact(Cin, Cout, bridge):
 
 @pytest.mark.parametrize("Cin,Cout,N,H,W", [(64, 32, 2, 192, 192), (128, 64, 1, 192, 192), (256, 128, 1, 72, 100)])
 def test_convT_persistent_kernel_many_tiles_bit_exact(Cin, Cout, N, H, W):
-    """sq_convt_f32_v2.hip (128 x 128 block tiles, channel-transposed operands, persistent blocks): more tiles than
-    blocks (a block walks several tiles and prefetches across the seam), one / two / four row tiles per pixel tile, a
-    ragged last pixel tile -- against the C oracle, bit for bit."""
+    """sq_convt_f32_v2.hip (128-row block tiles, channel-transposed operands, persistent blocks) against the C oracle, bit for
+    bit.  At the default 32-pixel tiles (1024 blocks) the one- and two-row-tile cases are 2304 work items -- a block walks two
+    or three and prefetches across the seam -- and the four-row-tile case is 900 items on 900 blocks with a full last pixel
+    tile.  Walks of three items at every row-tile count (1 .. 5), every bridge and a ragged last pixel tile:
+    tests/test_gpu_f32_walk_sweep.py, whose table tests/test_f32_walk_plan.py holds to those regimes."""
     x = tiles(14, N, H, W, Cin)
     w = rand_weights(15, (2, 2, Cout, Cin), 0.2)
     b = rand_weights(16, (Cout,), 0.1)

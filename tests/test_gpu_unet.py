@@ -234,10 +234,11 @@ def test_up_kernel_3x3_transpose_conv_bit_exact_and_trainable():
 
 
 @pytest.mark.parametrize("bridge", ["eltwise_mul", "eltwise_add", "eltwise_sub", None])
-@pytest.mark.parametrize("shape", [(2, 32, 32), (1, 48, 80), (3, 16, 16)])
+@pytest.mark.parametrize("shape", [(2, 32, 32), (1, 48, 80), (3, 16, 16), (2, 34, 50)])
 def test_convT_bridge_conv_fused_kernel_bit_exact(bridge, shape):
     """sq_convT_conv3x3_fwd_f32 (up0: transpose conv + bridge inside the conv's staging) vs the oracle's
-    convT -> bridge -> conv, bit for bit, incl. ragged tiles and image borders."""
+    convT -> bridge -> conv, bit for bit, incl. image borders.  The multiples of 16 run the level-0 kernel's UP form; (2, 34, 50),
+    even but ragged against the 16 x 16 tile, runs the generic kernel's."""
     from oracle import c_oracle as co
     from tests.util import rand_weights
     N, H, W = shape
