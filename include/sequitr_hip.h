@@ -1329,6 +1329,10 @@ int sq_confusion(const void *pred, int pred_kind, const uint8_t *truth, int trut
  *
  * All three return SQ_EINVAL with a message, before any launch, for null pointers, C < 2 or C > 256, a bad op, structure
  * or iterations, N, H or W < 1, 2^31 or more elements, a workspace that is not 16-B aligned, and out overlapping mask.
+ * None reads anything back, and every call is a chain of kernel launches on `stream` and nothing else (the counts and flags
+ * are cleared and the mask is copied by kernels, not by memset or memcpy calls): each can be captured in a graph and
+ * replayed.  fill_holes and clear_border are the volume entries' implementation ("Volume clean-up" below) with D = 1 and
+ * the four lateral faces as the border.
  * ---------------------------------------------------------------------------------------- */
 #define SQ_MORPH_ERODE 0
 #define SQ_MORPH_DILATE 1

@@ -1,11 +1,9 @@
 // Mask clean-up between "mask" and "objects" (include/sequitr_hip.h, "Mask clean-up"): binary morphology per class on
-// bit planes in LDS, hole filling and border-object removal on the labelling of sq_ccl.h.  Planar (N, H, W) uint8 masks.
+// bit planes in LDS.  Planar (N, H, W) uint8 masks.  Hole filling and border-object removal are sq_component_ops.hip.
 //   morph        : one block per 64 x 192 tile.  The tile and its halo are staged as bytes in LDS once; per class one
 //                  __ballot per 64-pixel row segment packs a row into 64-bit words, every 3x3 step is shifts, carries and
 //                  AND / OR between two LDS copies of the plane, the classes are merged in registers, the tile is stored.
-//   fill_holes   : per class, label the complement plane; a root that owns a frame-edge pixel is no hole
-//   clear_border : label the mask itself; a root that owns a frame-edge pixel goes
-#include "sq_ccl.h"
+#include "sq_cleanup.h"
 
 namespace {
 
@@ -177,75 +175,12 @@ __global__ __launch_bounds__(256) void morph_kernel(const uint8_t *__restrict__ 
     }
 }
 
-__global__ __launch_bounds__(256) void fh_complement_kernel(const uint8_t *__restrict__ mask, uint8_t *__restrict__ comp,
-                                                            int64_t total, int c) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x)
-        comp[g] = (int)mask[g] != c ? (uint8_t)1 : (uint8_t)0;
-}
-
-// the k-th pixel of a frame's outer rows and columns (2W + 2H of them; corners come twice)
-__device__ __forceinline__ int edge_pixel(int k, int H, int W) {
-    if (k < W) return k;
-    if (k < 2 * W) return (H - 1) * W + (k - W);
-    if (k < 2 * W + H) return (k - 2 * W) * W;
-    return (k - 2 * W - H) * W + (W - 1);
-}
-
-// plane != 0 on a frame-edge pixel: its root gets `value` (every writer stores the same value)
-__global__ __launch_bounds__(256) void edge_roots_kernel(const uint8_t *__restrict__ plane, const int *__restrict__ parent,
-                                                         int *__restrict__ info, int N, int H, int W, int value) {
-    const int per = 2 * W + 2 * H;
-    const int64_t items = (int64_t)N * per, HW = (int64_t)H * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t g = (i / per) * HW + edge_pixel((int)(i % per), H, W);
-        if (plane[g]) info[parent[g]] = value;
-    }
-}
-
-__global__ __launch_bounds__(256) void fh_area_kernel(const int *__restrict__ parent, int *__restrict__ info, int64_t total) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        const int p = parent[g];
-        if (p >= 0 && info[p] >= 0) atomicAdd(&info[p], 1);     // -1: reached from the frame edge, stays -1
-    }
-}
-
-__global__ __launch_bounds__(256) void fh_fill_kernel(const uint8_t *__restrict__ mask, const int *__restrict__ parent,
-                                                      const int *__restrict__ info, uint8_t *__restrict__ out, int64_t total,
-                                                      int c, int max_area) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        if (mask[g] != 0 || out[g] != 0) continue;              // only background that no smaller class has taken
-        const int a = info[parent[g]];                          // background is in the complement of every class
-        if (a >= 0 && (max_area <= 0 || a <= max_area)) out[g] = (uint8_t)c;
-    }
-}
-
-__global__ __launch_bounds__(256) void cb_apply_kernel(const uint8_t *__restrict__ mask, const int *__restrict__ parent,
-                                                       const int *__restrict__ flag, uint8_t *__restrict__ out, int64_t total,
-                                                       int C) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        const int v = mask[g];
-        out[g] = (v != 0 && v < C && flag[parent[g]]) ? (uint8_t)0 : (uint8_t)v;
-    }
-}
-
-inline bool ranges_overlap(const void *a, const void *b, int64_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
-}
-
 }  // namespace
-
-#define SQ_MASK_COMMON(who)                                                                                              \
-    SQ_REQUIRE(mask && out, "%s: null pointer", who);                                                                    \
-    SQ_REQUIRE(C >= 2 && C <= 256, "%s: C must be 2 .. 256 classes, got %d", who, C);                                    \
-    SQ_REQUIRE(N > 0 && H > 0 && W > 0 && (int64_t)N * H * W < ((int64_t)1 << 31),                                       \
-               "%s: the mask must have at least one and fewer than 2^31 elements, got (%d,%d,%d)", who, N, H, W);        \
-    SQ_REQUIRE(!ranges_overlap(mask, out, (int64_t)N * H * W), "%s: out must not overlap mask", who)
 
 extern "C" int sq_mask_morph_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, int op, int structure,
                                 int iterations, void *stream) {
     const char *who = "sq_mask_morph_u8";
-    SQ_MASK_COMMON(who);
+    SQ_CLEANUP_COMMON(who, 1, "(%d,%d,%d)", N, H, W);
     SQ_REQUIRE(op == SQ_MORPH_ERODE || op == SQ_MORPH_DILATE || op == SQ_MORPH_OPEN || op == SQ_MORPH_CLOSE,
                "%s: op must be SQ_MORPH_ERODE, DILATE, OPEN or CLOSE, got %d", who, op);
     SQ_REQUIRE(structure == SQ_MORPH_CROSS || structure == SQ_MORPH_SQUARE,
@@ -261,78 +196,5 @@ extern "C" int sq_mask_morph_u8(const uint8_t *mask, uint8_t *out, int N, int H,
     else
         hipLaunchKernelGGL(morph_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mask, out, H, W, C, op,
                            structure == SQ_MORPH_SQUARE, iterations, tiles_x, tiles_y);
-    return sq_check_launch(who);
-}
-
-extern "C" int64_t sq_mask_fill_holes_workspace(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0) return -1;
-    const int64_t total = (int64_t)N * H * W;
-    if (total >= ((int64_t)1 << 31)) return -1;
-    return (total * 9 + 15) / 16 * 16;                         // parent, info, the complement plane
-}
-
-extern "C" int sq_mask_fill_holes_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, int64_t max_area,
-                                     void *workspace, void *stream) {
-    const char *who = "sq_mask_fill_holes_u8";
-    SQ_MASK_COMMON(who);
-    SQ_REQUIRE(workspace, "%s: null pointer", who);
-    SQ_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t total = (int64_t)N * H * W;
-    int *parent = reinterpret_cast<int *>(workspace);
-    int *info = parent + total;
-    uint8_t *comp = reinterpret_cast<uint8_t *>(info + total);
-    const int limit = max_area <= 0 || max_area >= total ? 0 : (int)max_area;   // no component is larger than the mask
-    const int rows = N * H;
-    const dim3 rgrid((rows + 3) / 4), tgrid(cc_grid(total)), egrid(cc_grid((int64_t)N * (2 * W + 2 * H))), blk(256);
-    if (hipMemcpyAsync(out, mask, (size_t)total, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        sq_set_error("%s: cannot copy the mask", who);
-        return SQ_ELAUNCH;
-    }
-    for (int c = 1; c < C; ++c) {
-        hipLaunchKernelGGL(fh_complement_kernel, tgrid, blk, 0, st, mask, comp, total, c);
-        hipLaunchKernelGGL(cc_rowscan_kernel<false>, rgrid, blk, 0, st, (const uint8_t *)comp, parent, (unsigned *)nullptr,
-                           (u64 *)nullptr, rows, W);
-        hipLaunchKernelGGL(cc_merge_kernel, tgrid, blk, 0, st, (const uint8_t *)comp, parent, total, 1, H, W);
-        hipLaunchKernelGGL(cc_compress_kernel, tgrid, blk, 0, st, parent, total);
-        if (hipMemsetAsync(info, 0, (size_t)total * sizeof(int), st) != hipSuccess) {
-            sq_set_error("%s: cannot clear the areas", who);
-            return SQ_ELAUNCH;
-        }
-        hipLaunchKernelGGL(edge_roots_kernel, egrid, blk, 0, st, (const uint8_t *)comp, (const int *)parent, info, N, H, W, -1);
-        if (limit > 0) hipLaunchKernelGGL(fh_area_kernel, tgrid, blk, 0, st, (const int *)parent, info, total);
-        hipLaunchKernelGGL(fh_fill_kernel, tgrid, blk, 0, st, mask, (const int *)parent, (const int *)info, out, total, c, limit);
-    }
-    return sq_check_launch(who);
-}
-
-extern "C" int64_t sq_mask_clear_border_workspace(int N, int H, int W) {
-    if (N <= 0 || H <= 0 || W <= 0) return -1;
-    const int64_t total = (int64_t)N * H * W;
-    if (total >= ((int64_t)1 << 31)) return -1;
-    return (total * 8 + 15) / 16 * 16;                         // parent, flag
-}
-
-extern "C" int sq_mask_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int C, void *workspace,
-                                       void *stream) {
-    const char *who = "sq_mask_clear_border_u8";
-    SQ_MASK_COMMON(who);
-    SQ_REQUIRE(workspace, "%s: null pointer", who);
-    SQ_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t total = (int64_t)N * H * W;
-    int *parent = reinterpret_cast<int *>(workspace);
-    int *flag = parent + total;
-    const int rows = N * H;
-    const dim3 rgrid((rows + 3) / 4), tgrid(cc_grid(total)), egrid(cc_grid((int64_t)N * (2 * W + 2 * H))), blk(256);
-    hipLaunchKernelGGL(cc_rowscan_kernel<false>, rgrid, blk, 0, st, mask, parent, (unsigned *)nullptr, (u64 *)nullptr, rows, W);
-    hipLaunchKernelGGL(cc_merge_kernel, tgrid, blk, 0, st, mask, parent, total, 1, H, W);
-    hipLaunchKernelGGL(cc_compress_kernel, tgrid, blk, 0, st, parent, total);
-    if (hipMemsetAsync(flag, 0, (size_t)total * sizeof(int), st) != hipSuccess) {
-        sq_set_error("%s: cannot clear the flags", who);
-        return SQ_ELAUNCH;
-    }
-    hipLaunchKernelGGL(edge_roots_kernel, egrid, blk, 0, st, mask, (const int *)parent, flag, N, H, W, 1);
-    hipLaunchKernelGGL(cb_apply_kernel, tgrid, blk, 0, st, mask, (const int *)parent, (const int *)flag, out, total, C);
     return sq_check_launch(who);
 }

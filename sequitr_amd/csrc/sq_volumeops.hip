@@ -1,13 +1,11 @@
 // Volume clean-up between "mask" and "objects" (include/sequitr_hip.h, "Volume clean-up"): the 3-D counterpart of
-// sq_maskops.hip for (N, D, H, W) uint8 masks.
+// sq_maskops.hip for (N, D, H, W) uint8 masks.  Cavity filling and border-object removal are sq_component_ops.hip.
 //   morph        : one block per 8 x 32 x 128 brick.  Per class the bit plane of the brick and its halo is built straight
 //                  from global memory -- a wave loads four rows as dwords into its own small LDS buffer and packs each
 //                  64-voxel row segment with one __ballot -- every elementary step is shifts, carries and AND / OR with the
 //                  rows and planes around it between two LDS copies of the plane, and each class's plane is merged into the
 //                  brick in `out` against the brick's own bytes of the mask.
-//   fill_holes   : per class, label the complement plane (6-connected); a root that owns a face voxel is no cavity
-//   clear_border : label the mask itself; a root that owns a voxel of the chosen faces goes
-#include "sq_ccl.h"
+#include "sq_cleanup.h"
 
 namespace {
 
@@ -233,111 +231,12 @@ __global__ __launch_bounds__(256, 2) void volume_morph_kernel(const uint8_t *__r
     if (fresh) merge(nullptr, 0, true);                         // no class in the region: the brick is copied through
 }
 
-// The complement plane of class c, and the per-voxel counts cleared; the first class also copies the mask to `out`.  Plain
-// kernels instead of memset and memcpy calls: a captured call is a chain of kernel nodes and nothing else.
-__global__ __launch_bounds__(256) void vfh_complement_kernel(const uint8_t *__restrict__ mask, uint8_t *__restrict__ comp,
-                                                             int *__restrict__ info, uint8_t *__restrict__ out, int64_t total,
-                                                             int c, int copy) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        const uint8_t v = mask[g];
-        comp[g] = (int)v != c ? (uint8_t)1 : (uint8_t)0;
-        info[g] = 0;
-        if (copy) out[g] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void vclear_kernel(int *__restrict__ flag, int64_t total) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) flag[g] = 0;
-}
-
-// voxels of a volume's faces the enumerator visits: 2 D W + 2 D H on the four lateral faces, plus 2 H W on the first and
-// last plane unless `lateral`; voxels on edges come twice or three times
-__device__ __forceinline__ int64_t face_count(int D, int H, int W, bool lateral) {
-    return 2 * (int64_t)D * W + 2 * (int64_t)D * H + (lateral ? 0 : 2 * (int64_t)H * W);
-}
-
-// the k-th of them as a linear index into the (D, H, W) volume
-__device__ __forceinline__ int64_t face_voxel(int64_t k, int D, int H, int W, bool lateral) {
-    const int64_t HW = (int64_t)H * W, DW = (int64_t)D * W, DH = (int64_t)D * H;
-    if (!lateral) {
-        if (k < HW) return k;                                   // z = 0
-        if (k < 2 * HW) return (D - 1) * HW + (k - HW);         // z = D - 1
-        k -= 2 * HW;
-    }
-    if (k < DW) return (k / W) * HW + k % W;                    // h = 0
-    if (k < 2 * DW) return ((k - DW) / W) * HW + (int64_t)(H - 1) * W + (k - DW) % W;   // h = H - 1
-    k -= 2 * DW;
-    if (k < DH) return (k / H) * HW + (k % H) * W;              // w = 0
-    k -= DH;
-    return (k / H) * HW + (k % H) * W + (W - 1);                // w = W - 1
-}
-
-// plane != 0 on a face voxel: its root gets `value` (every writer stores the same value)
-__global__ __launch_bounds__(256) void face_roots_kernel(const uint8_t *__restrict__ plane, const int *__restrict__ parent,
-                                                         int *__restrict__ info, int N, int D, int H, int W, int lateral,
-                                                         int value) {
-    const int64_t per = face_count(D, H, W, lateral != 0), items = (int64_t)N * per, DHW = (int64_t)D * H * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t g = (i / per) * DHW + face_voxel(i % per, D, H, W, lateral != 0);
-        if (plane[g]) info[parent[g]] = value;
-    }
-}
-
-__global__ __launch_bounds__(256) void vfh_count_kernel(const int *__restrict__ parent, int *__restrict__ info, int64_t total) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        const int p = parent[g];
-        if (p >= 0 && info[p] >= 0) atomicAdd(&info[p], 1);     // -1: reached from a face, stays -1
-    }
-}
-
-__global__ __launch_bounds__(256) void vfh_fill_kernel(const uint8_t *__restrict__ mask, const int *__restrict__ parent,
-                                                       const int *__restrict__ info, uint8_t *__restrict__ out, int64_t total,
-                                                       int c, int max_voxels) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        if (mask[g] != 0 || out[g] != 0) continue;              // only background that no smaller class has taken
-        const int a = info[parent[g]];                          // background is in the complement of every class
-        if (a >= 0 && (max_voxels <= 0 || a <= max_voxels)) out[g] = (uint8_t)c;
-    }
-}
-
-__global__ __launch_bounds__(256) void vcb_apply_kernel(const uint8_t *__restrict__ mask, const int *__restrict__ parent,
-                                                        const int *__restrict__ flag, uint8_t *__restrict__ out, int64_t total,
-                                                        int C) {
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
-        const int v = mask[g];
-        out[g] = (v != 0 && v < C && flag[parent[g]]) ? (uint8_t)0 : (uint8_t)v;
-    }
-}
-
-inline bool vranges_overlap(const void *a, const void *b, int64_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
-}
-
-inline int64_t volume_elements(int N, int D, int H, int W) {   // -1: an extent < 1, or 2^31 or more elements
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return -1;
-    const int64_t lim = (int64_t)1 << 31;
-    int64_t total = (int64_t)N * D;                             // < 2^62
-    if (total >= lim) return -1;
-    total *= H;
-    if (total >= lim) return -1;
-    total *= W;
-    return total >= lim ? -1 : total;
-}
-
 }  // namespace
-
-#define SQ_VOLUME_COMMON(who)                                                                                            \
-    SQ_REQUIRE(mask && out, "%s: null pointer", who);                                                                    \
-    SQ_REQUIRE(C >= 2 && C <= 256, "%s: C must be 2 .. 256 classes, got %d", who, C);                                    \
-    SQ_REQUIRE(volume_elements(N, D, H, W) > 0,                                                                          \
-               "%s: the mask must have at least one and fewer than 2^31 elements, got (%d,%d,%d,%d)", who, N, D, H, W);  \
-    SQ_REQUIRE(!vranges_overlap(mask, out, volume_elements(N, D, H, W)), "%s: out must not overlap mask", who)
 
 extern "C" int sq_volume_morph_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int op, int structure,
                                   int iterations, void *stream) {
     const char *who = "sq_volume_morph_u8";
-    SQ_VOLUME_COMMON(who);
+    SQ_CLEANUP_COMMON(who, D, "(%d,%d,%d,%d)", N, D, H, W);
     SQ_REQUIRE(op == SQ_MORPH_ERODE || op == SQ_MORPH_DILATE || op == SQ_MORPH_OPEN || op == SQ_MORPH_CLOSE,
                "%s: op must be SQ_MORPH_ERODE, DILATE, OPEN or CLOSE, got %d", who, op);
     SQ_REQUIRE(structure == SQ_MORPH3D_CROSS || structure == SQ_MORPH3D_CUBE,
@@ -353,68 +252,5 @@ extern "C" int sq_volume_morph_u8(const uint8_t *mask, uint8_t *out, int N, int 
     else
         hipLaunchKernelGGL(volume_morph_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mask, out, D, H,
                            W, C, op, structure == SQ_MORPH3D_CUBE, iterations, tiles_x, tiles_y, tiles_z);
-    return sq_check_launch(who);
-}
-
-extern "C" int64_t sq_volume_fill_holes_workspace(int N, int D, int H, int W) {
-    const int64_t total = volume_elements(N, D, H, W);
-    return total < 0 ? -1 : (total * 9 + 15) / 16 * 16;        // parent, info, the complement plane
-}
-
-extern "C" int sq_volume_fill_holes_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int64_t max_voxels,
-                                       void *workspace, void *stream) {
-    const char *who = "sq_volume_fill_holes_u8";
-    SQ_VOLUME_COMMON(who);
-    SQ_REQUIRE(workspace, "%s: null pointer", who);
-    SQ_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t total = volume_elements(N, D, H, W);
-    int *parent = reinterpret_cast<int *>(workspace);
-    int *info = parent + total;
-    uint8_t *comp = reinterpret_cast<uint8_t *>(info + total);
-    const int limit = max_voxels <= 0 || max_voxels >= total ? 0 : (int)max_voxels;   // no component is larger than the mask
-    const int rows = N * D * H;
-    const int64_t faces = (int64_t)N * (2 * (int64_t)H * W + 2 * (int64_t)D * W + 2 * (int64_t)D * H);
-    const dim3 rgrid((rows + 3) / 4), tgrid(cc_grid(total)), fgrid(cc_grid(faces)), blk(256);
-    for (int c = 1; c < C; ++c) {
-        hipLaunchKernelGGL(vfh_complement_kernel, tgrid, blk, 0, st, mask, comp, info, out, total, c, c == 1);
-        hipLaunchKernelGGL(cc_rowscan_kernel<false>, rgrid, blk, 0, st, (const uint8_t *)comp, parent, (unsigned *)nullptr,
-                           (u64 *)nullptr, rows, W);
-        hipLaunchKernelGGL(cc_merge_kernel, tgrid, blk, 0, st, (const uint8_t *)comp, parent, total, D, H, W);
-        hipLaunchKernelGGL(cc_compress_kernel, tgrid, blk, 0, st, parent, total);
-        hipLaunchKernelGGL(face_roots_kernel, fgrid, blk, 0, st, (const uint8_t *)comp, (const int *)parent, info, N, D, H, W, 0, -1);
-        if (limit > 0) hipLaunchKernelGGL(vfh_count_kernel, tgrid, blk, 0, st, (const int *)parent, info, total);
-        hipLaunchKernelGGL(vfh_fill_kernel, tgrid, blk, 0, st, mask, (const int *)parent, (const int *)info, out, total, c, limit);
-    }
-    return sq_check_launch(who);
-}
-
-extern "C" int64_t sq_volume_clear_border_workspace(int N, int D, int H, int W) {
-    const int64_t total = volume_elements(N, D, H, W);
-    return total < 0 ? -1 : (total * 8 + 15) / 16 * 16;        // parent, flag
-}
-
-extern "C" int sq_volume_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int faces,
-                                         void *workspace, void *stream) {
-    const char *who = "sq_volume_clear_border_u8";
-    SQ_VOLUME_COMMON(who);
-    SQ_REQUIRE(faces == SQ_FACES_ALL || faces == SQ_FACES_LATERAL, "%s: faces must be SQ_FACES_ALL or SQ_FACES_LATERAL, got %d",
-               who, faces);
-    SQ_REQUIRE(workspace, "%s: null pointer", who);
-    SQ_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t total = volume_elements(N, D, H, W);
-    int *parent = reinterpret_cast<int *>(workspace);
-    int *flag = parent + total;
-    const int rows = N * D * H;
-    const int lateral = faces == SQ_FACES_LATERAL;
-    const int64_t nfaces = (int64_t)N * (2 * (int64_t)D * W + 2 * (int64_t)D * H + (lateral ? 0 : 2 * (int64_t)H * W));
-    const dim3 rgrid((rows + 3) / 4), tgrid(cc_grid(total)), fgrid(cc_grid(nfaces)), blk(256);
-    hipLaunchKernelGGL(cc_rowscan_kernel<false>, rgrid, blk, 0, st, mask, parent, (unsigned *)nullptr, (u64 *)nullptr, rows, W);
-    hipLaunchKernelGGL(cc_merge_kernel, tgrid, blk, 0, st, mask, parent, total, D, H, W);
-    hipLaunchKernelGGL(cc_compress_kernel, tgrid, blk, 0, st, parent, total);
-    hipLaunchKernelGGL(vclear_kernel, tgrid, blk, 0, st, flag, total);
-    hipLaunchKernelGGL(face_roots_kernel, fgrid, blk, 0, st, mask, (const int *)parent, flag, N, D, H, W, lateral, 1);
-    hipLaunchKernelGGL(vcb_apply_kernel, tgrid, blk, 0, st, mask, (const int *)parent, (const int *)flag, out, total, C);
     return sq_check_launch(who);
 }

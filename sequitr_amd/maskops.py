@@ -37,16 +37,22 @@ _STEP_KEYS = dict({op: {'iterations': 1, 'structure': 'cross'} for op in MORPH_O
                   split={'erosions': None, 'structure': 'cross', 'reach': None})
 
 
-def _check_mask(mask, classes):
+def _check_mask(mask, classes, rank=3):
+    """rank 3: a planar (N,H,W) mask; 4: the (N,D,H,W) mask of sequitr_amd.volumeops"""
     if not isinstance(mask, torch.Tensor):
         raise TypeError("mask must be a torch.Tensor in GPU memory")
     if not mask.is_cuda:
         raise _lib.SequitrHipError("mask must live in GPU memory (no CPU fallback exists)")
     if mask.dtype != torch.uint8:
         raise ValueError("mask must be uint8 class labels, got %s" % mask.dtype)
-    if mask.dim() != 3:
-        raise ValueError("mask clean-up covers planar (N,H,W) masks only, got shape %s: volumes are out of scope"
-                         % (tuple(mask.shape),))
+    if mask.dim() != rank:
+        if rank == 3:
+            raise ValueError("mask clean-up covers planar (N,H,W) masks only, got shape %s: volumes are out of scope"
+                             % (tuple(mask.shape),))
+        if mask.dim() == 3:
+            raise ValueError("volume clean-up covers (N,D,H,W) masks, got the planar shape %s: use sequitr_amd.maskops"
+                             % (tuple(mask.shape),))
+        raise ValueError("volume clean-up covers (N,D,H,W) masks, got shape %s" % (tuple(mask.shape),))
     if not mask.is_contiguous():
         raise ValueError("mask must be contiguous: pass a packed copy of a view")
     if mask.numel() == 0:
@@ -66,7 +72,7 @@ def _check_out(out, mask):
 
 
 def _dims(mask):
-    return int(mask.shape[0]), int(mask.shape[1]), int(mask.shape[2])
+    return tuple(int(s) for s in mask.shape)
 
 
 def _stream(mask):
@@ -164,52 +170,35 @@ def load_steps(spec):
     return spec
 
 
-class MaskCleanup(object):
-    """A validated list of clean-up steps, e.g. [{"op": "open", "iterations": 2, "structure": "cross"},
-    {"op": "fill_holes", "max_area": 400}, {"op": "split", "erosions": 8}, {"op": "clear_border"}].  Unknown ops, unknown keys and bad values raise a
-    ValueError that names them, at construction.  ``apply`` runs the steps in order on a batch of device masks."""
+class _Cleanup(object):
+    """What MaskCleanup and VolumeCleanup share: a validated list of steps that runs between two cached buffers.  A
+    subclass gives LABEL (the job parameter its messages name), RANK (of its masks), STEP_KEYS (op -> the keys a step may
+    carry besides 'op', with their defaults), NOT_BUILT (op -> why it is no step here) and three methods:
+    _check_step(where, op, full) raises a ValueError that starts with `where` for a bad value,
+    _step_workspace(lib, step, dims) is the bytes of workspace a step needs (0: none, < 0: too large),
+    _run(step, src, classes, dst, ws) runs one step."""
+    NOT_BUILT = {}
 
     def __init__(self, steps):
-        if isinstance(steps, MaskCleanup):
+        label, keys = self.LABEL, self.STEP_KEYS
+        if isinstance(steps, type(self)):
             steps = steps.record()
         if not isinstance(steps, (list, tuple)) or not steps:
-            raise ValueError("postprocess steps must be a non-empty list of {'op': ...} dicts, got %r" % (steps,))
+            raise ValueError("%s steps must be a non-empty list of {'op': ...} dicts, got %r" % (label, steps))
         self.steps = []
         for i, step in enumerate(steps):
             if not isinstance(step, dict) or 'op' not in step:
-                raise ValueError("postprocess step %d must be a dict with an 'op', got %r" % (i, step))
+                raise ValueError("%s step %d must be a dict with an 'op', got %r" % (label, i, step))
             op = step['op']
-            if not isinstance(op, str) or op not in _STEP_KEYS:
-                raise ValueError("postprocess step %d: unknown op %r (known: %s)" % (i, op, ', '.join(sorted(_STEP_KEYS))))
-            unknown = sorted(k for k in step if k != 'op' and k not in _STEP_KEYS[op])
+            if not isinstance(op, str) or op not in keys:
+                why = self.NOT_BUILT[op] if isinstance(op, str) and op in self.NOT_BUILT else "unknown op %r" % (op,)
+                raise ValueError("%s step %d: %s (known: %s)" % (label, i, why, ', '.join(sorted(keys))))
+            unknown = sorted(k for k in step if k != 'op' and k not in keys[op])
             if unknown:
-                raise ValueError("postprocess step %d (%s): unknown key(s) %s (allowed: %s)"
-                                 % (i, op, ', '.join(map(repr, unknown)), ', '.join(sorted(_STEP_KEYS[op])) or 'none'))
-            full = dict(_STEP_KEYS[op], **step)
-            if op in MORPH_OPS:
-                r = full['iterations']
-                if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= MORPH_MAX_ITER:
-                    raise ValueError("postprocess step %d (%s): iterations must be an integer 1 .. %d, got %r"
-                                     % (i, op, MORPH_MAX_ITER, r))
-                if full['structure'] not in STRUCTURES:
-                    raise ValueError("postprocess step %d (%s): structure must be one of %s, got %r"
-                                     % (i, op, sorted(STRUCTURES), full['structure']))
-            elif op == 'fill_holes':
-                a = full['max_area']
-                if a is not None and (isinstance(a, bool) or not isinstance(a, int) or a < 1):
-                    raise ValueError("postprocess step %d (fill_holes): max_area must be a positive integer or null, got %r"
-                                     % (i, a))
-            elif op == 'split':
-                r, t = full['erosions'], full['reach']
-                if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= MORPH_MAX_ITER:
-                    raise ValueError("postprocess step %d (split): erosions must be an integer 1 .. %d, got %r"
-                                     % (i, MORPH_MAX_ITER, r))
-                if full['structure'] not in STRUCTURES:
-                    raise ValueError("postprocess step %d (split): structure must be one of %s, got %r"
-                                     % (i, sorted(STRUCTURES), full['structure']))
-                if t is not None and (isinstance(t, bool) or not isinstance(t, int) or not 1 <= t <= SPLIT_MAX_REACH):
-                    raise ValueError("postprocess step %d (split): reach must be an integer 1 .. %d or null, got %r"
-                                     % (i, SPLIT_MAX_REACH, t))
+                raise ValueError("%s step %d (%s): unknown key(s) %s (allowed: %s)"
+                                 % (label, i, op, ', '.join(map(repr, unknown)), ', '.join(sorted(keys[op])) or 'none'))
+            full = dict(keys[op], **step)
+            self._check_step("%s step %d (%s)" % (label, i, op), op, full)
             self.steps.append(full)
         self._cache = {}
 
@@ -223,36 +212,64 @@ class MaskCleanup(object):
             lib = _lib.load()
             need = 0
             for s in self.steps:
-                fn = {'fill_holes': lib.sq_mask_fill_holes_workspace, 'clear_border': lib.sq_mask_clear_border_workspace,
-                      'split': lib.sq_mask_split_workspace}.get(s['op'])
-                if fn is not None:
-                    nbytes = fn(*_dims(mask))
-                    if nbytes < 0:
-                        raise ValueError("mask %s is too large for one call" % (tuple(mask.shape),))
-                    need = max(need, nbytes)
+                nbytes = self._step_workspace(lib, s, _dims(mask))
+                if nbytes < 0:
+                    raise ValueError("mask %s is too large for one call" % (tuple(mask.shape),))
+                need = max(need, nbytes)
             ws = torch.empty(need // 4, dtype=torch.int32, device=mask.device) if need else None
             self._cache[key] = (torch.empty_like(mask), torch.empty_like(mask), ws)
         return self._cache[key]
 
     def apply(self, mask, classes):
-        """Run the steps on `mask` ((N,H,W) uint8 on the GPU, `classes` classes) on the current stream.  The input is not
+        """Run the steps on `mask` (uint8 on the GPU, `classes` classes) on the current stream.  The input is not
         written; the result is one of two buffers this object caches per shape (nothing is allocated after the first call
         for a shape), valid until the next apply()."""
         classes = int(classes)
         if classes < 2:
             raise ValueError("classes must be at least 2, got %d" % classes)
-        _check_mask(mask, classes)
+        _check_mask(mask, classes, self.RANK)
         a, b, ws = self._buffers(mask)
         src = mask
         for s in self.steps:
             dst = a if src is not a else b
-            if s['op'] in MORPH_OPS:
-                morph(src, s['op'], s['iterations'], s['structure'], classes, out=dst)
-            elif s['op'] == 'fill_holes':
-                fill_holes(src, s['max_area'], classes, out=dst, workspace=ws)
-            elif s['op'] == 'split':
-                split(src, s['erosions'], s['structure'], s['reach'], classes, out=dst, workspace=ws)
-            else:
-                clear_border(src, classes, out=dst, workspace=ws)
+            self._run(s, src, classes, dst, ws)
             src = dst
         return src
+
+
+def _is_int(v, lo, hi=None):
+    return not isinstance(v, bool) and isinstance(v, int) and v >= lo and (hi is None or v <= hi)
+
+
+class MaskCleanup(_Cleanup):
+    """A validated list of clean-up steps, e.g. [{"op": "open", "iterations": 2, "structure": "cross"},
+    {"op": "fill_holes", "max_area": 400}, {"op": "split", "erosions": 8}, {"op": "clear_border"}].  Unknown ops, unknown keys and bad values raise a
+    ValueError that names them, at construction.  ``apply`` runs the steps in order on a batch of (N,H,W) device masks."""
+    LABEL, RANK, STEP_KEYS = 'postprocess', 3, _STEP_KEYS
+
+    def _check_step(self, where, op, full):
+        if op in MORPH_OPS and not _is_int(full['iterations'], 1, MORPH_MAX_ITER):
+            raise ValueError("%s: iterations must be an integer 1 .. %d, got %r" % (where, MORPH_MAX_ITER, full['iterations']))
+        if op == 'fill_holes' and full['max_area'] is not None and not _is_int(full['max_area'], 1):
+            raise ValueError("%s: max_area must be a positive integer or null, got %r" % (where, full['max_area']))
+        if op == 'split' and not _is_int(full['erosions'], 1, MORPH_MAX_ITER):
+            raise ValueError("%s: erosions must be an integer 1 .. %d, got %r" % (where, MORPH_MAX_ITER, full['erosions']))
+        if 'structure' in full and full['structure'] not in STRUCTURES:
+            raise ValueError("%s: structure must be one of %s, got %r" % (where, sorted(STRUCTURES), full['structure']))
+        if op == 'split' and full['reach'] is not None and not _is_int(full['reach'], 1, SPLIT_MAX_REACH):
+            raise ValueError("%s: reach must be an integer 1 .. %d or null, got %r" % (where, SPLIT_MAX_REACH, full['reach']))
+
+    def _step_workspace(self, lib, s, dims):
+        fn = {'fill_holes': lib.sq_mask_fill_holes_workspace, 'clear_border': lib.sq_mask_clear_border_workspace,
+              'split': lib.sq_mask_split_workspace}.get(s['op'])
+        return fn(*dims) if fn is not None else 0
+
+    def _run(self, s, src, classes, dst, ws):
+        if s['op'] in MORPH_OPS:
+            morph(src, s['op'], s['iterations'], s['structure'], classes, out=dst)
+        elif s['op'] == 'fill_holes':
+            fill_holes(src, s['max_area'], classes, out=dst, workspace=ws)
+        elif s['op'] == 'split':
+            split(src, s['erosions'], s['structure'], s['reach'], classes, out=dst, workspace=ws)
+        else:
+            clear_border(src, classes, out=dst, workspace=ws)

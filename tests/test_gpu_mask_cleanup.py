@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from sequitr_amd import maskops
+from sequitr_amd import maskops, volumeops
 from tests import mask_cleanup_cases as mc
 from tests import objects_cases as oc
 
@@ -118,6 +118,8 @@ def test_clear_border(case):
     want = mc.clear_border_ref(mask, C)
     assert np.array_equal(got.cpu().numpy(), want), "%s: %d pixels differ" % (name, int((got.cpu().numpy() != want).sum()))
     assert torch.equal(got, maskops.clear_border(d, classes=C)) and np.array_equal(d.cpu().numpy(), mask)
+    # a frame is a volume of one plane whose border is its four lateral faces
+    assert torch.equal(got, volumeops.clear_border3d(d[:, None].contiguous(), "lateral", classes=C)[:, 0])
     if name == "one row":
         assert not got.any()                                    # every pixel of a one-row frame is on the edge
 
@@ -129,7 +131,7 @@ def test_component_ops_guard_and_default_classes():
     for fn, ref in ((lambda o: maskops.fill_holes(d, 6, out=o), mc.fill_holes_ref(mask, 6, 3)),
                     (lambda o: maskops.clear_border(d, out=o), mc.clear_border_ref(mask, 3))):
         buf = torch.full((k + 64,), 0xAB, dtype=torch.uint8, device="cuda")
-        out = buf[13:13 + k].view(mask.shape)
+        out = buf[13:13 + k].view(mask.shape)                   # unaligned: the kernel that copies the mask stays inside k bytes
         assert fn(out) is out and np.array_equal(out.cpu().numpy(), ref)   # classes default to the largest byte + 1
         guard = buf.cpu().numpy()
         assert np.all(guard[:13] == 0xAB) and np.all(guard[13 + k:] == 0xAB)

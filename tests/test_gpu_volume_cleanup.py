@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from sequitr_amd import maskops, volumeops
+from tests import mask_cleanup_cases as mc
 from tests import volume_cleanup_cases as vc
 
 pytestmark = pytest.mark.gpu
@@ -239,9 +240,16 @@ def test_volume_cleanup_apply_is_the_steps_in_sequence():
 def test_graph_replay_equals_eager():
     mask = _cleanup_volume()
     d = dev(mask)
-    vcl = volumeops.VolumeCleanup(STEPS)
+    steps = STEPS + [{"op": "fill_holes", "planar": True}]
+    vcl = volumeops.VolumeCleanup(steps)
+    frames = mask.reshape((-1,) + mask.shape[2:])               # 33 frames of 21 x 47: W no multiple of 4 or of 64
+    dframes = d.view(frames.shape)
+    planar_steps = [{"op": "open", "iterations": 1, "structure": "cross"}, {"op": "fill_holes", "max_area": 6},
+                    {"op": "clear_border"}]
+    mcl = maskops.MaskCleanup(planar_steps)
     eager_morph = volumeops.morph3d(d, "open", 2, "cube", classes=3).clone()
     eager_steps = vcl.apply(d, 3).clone()
+    eager_planar = mcl.apply(dframes, 3).clone()
     out = torch.empty_like(d)
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
@@ -249,18 +257,24 @@ def test_graph_replay_equals_eager():
     with torch.cuda.stream(stream):
         volumeops.morph3d(d, "open", 2, "cube", classes=3, out=out)   # warm up on the side stream
         vcl.apply(d, 3)
+        mcl.apply(dframes, 3)
     torch.cuda.current_stream().wait_stream(stream)
     torch.cuda.synchronize()
-    g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
     with torch.cuda.graph(g1):
         volumeops.morph3d(d, "open", 2, "cube", classes=3, out=out)
     with torch.cuda.graph(g2):
         res = vcl.apply(d, 3)
+    with torch.cuda.graph(g3):
+        pres = mcl.apply(dframes, 3)
     for _ in range(2):
         out.zero_()
         res.zero_()
+        pres.zero_()
         g1.replay()
         g2.replay()
+        g3.replay()
         torch.cuda.synchronize()
-        assert torch.equal(out, eager_morph) and torch.equal(res, eager_steps)
-    assert np.array_equal(eager_steps.cpu().numpy(), vc.steps_ref(mask, STEPS, 3))
+        assert torch.equal(out, eager_morph) and torch.equal(res, eager_steps) and torch.equal(pres, eager_planar)
+    assert np.array_equal(eager_steps.cpu().numpy(), vc.steps_ref(mask, steps, 3))
+    assert np.array_equal(eager_planar.cpu().numpy(), mc.steps_ref(frames, planar_steps, 3))
