@@ -1477,7 +1477,7 @@ int sq_mask_split_u8(const uint8_t *mask, uint8_t *out, int N, int H, int W, int
  * C > 256, a bad op, structure or faces value, iterations outside 1 .. SQ_MORPH3D_MAX_ITER, N, D, H or W < 1, 2^31 or more
  * elements, a workspace that is not 16-B aligned, and out overlapping mask.  None reads anything back, and every call is a
  * chain of kernel launches on `stream` and nothing else (the counts and flags are cleared and the mask is copied by kernels,
- * not by memset or memcpy calls): each can be captured in a graph and replayed.  Not built: a 3-D split, the 18-neighbour structure, anisotropic structuring elements.
+ * not by memset or memcpy calls): each can be captured in a graph and replayed.  Not built: the 18-neighbour structure, anisotropic structuring elements.
  * ---------------------------------------------------------------------------------------- */
 #define SQ_MORPH3D_CROSS 0
 #define SQ_MORPH3D_CUBE 1
@@ -1495,6 +1495,89 @@ int sq_volume_fill_holes_u8(const uint8_t *mask, uint8_t *out, int N, int D, int
 int64_t sq_volume_clear_border_workspace(int N, int D, int H, int W);
 int sq_volume_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int faces,
                               void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Volume clean-up: splitting (sequitr_amd/volumeops.py: split3d, the `split3d` step of VolumeCleanup and of the volume
+ * jobs' `volume_postprocess` key).  Everything downstream of the volume mask calls a 6-connected component of one class
+ * "an object", so two cells that touch are one object with one centroid, one row, one zone.  sq_volume_split_u8 cuts a
+ * one-voxel sheet of background between the parts of an object; the mask format does not change.
+ *
+ * "Mask clean-up: splitting" applies word for word with voxels for pixels, except as follows.  mask and out are
+ * (N, D, H, W) uint8 with C classes, fewer than 2^31 elements, the N volumes independent.  P_c, bytes >= C and "an object"
+ * are those of "Volume clean-up": bytes >= C belong to no class, are copied through, are never written and conduct
+ * nothing.  Only integer and Boolean arithmetic: the same bits on every run.
+ *
+ * Definition.  erosions r = 1 .. SQ_SPLIT3D_MAX_EROSIONS, structure = SQ_MORPH3D_CROSS, SQ_MORPH3D_CUBE,
+ * SQ_SPLIT3D_PLANE_CROSS or SQ_SPLIT3D_PLANE_SQUARE, reach T = 1 .. SQ_SPLIT3D_MAX_REACH.  Per class c = 1 .. C-1:
+ *   1. Seeds.   S_c = scipy.ndimage.binary_erosion(P_c, structure, iterations=r) with scipy's defaults (border value 0 on
+ *               all six faces).  The structure is generate_binary_structure(3, 1) for cross and (3, 3) for cube; for the
+ *               two plane structures it is generate_binary_structure(2, 1 | 2)[None], the planar erosion slice by slice
+ *               (no face in z eats anything): what a z-stack with few, thick slices needs.
+ *   2. Labels.  The 6-connected components of S_c, numbered in the raster order of their first voxel
+ *               (scipy.ndimage.label's default 3-D structure, the labelling of sq_ccl.h with planes = D) -- also when the
+ *               seeds came from a plane structure: seeds stacked along z are one seed.  L_0 = that number on seed voxels,
+ *               0 ("none") elsewhere.  Labels of different classes are never compared.
+ *   3. Regrowth.  T synchronous steps with the 6 neighbours inside the volume.  A voxel p with mask(p) = c and
+ *               L_{t-1}(p) = 0 takes the smallest non-zero L_{t-1}(q) over its neighbours q with mask(q) = c, or stays 0
+ *               when there is none.  Everything else keeps its label.  All reads of step t see step t-1.
+ *   4. Cut.     out(p) = 0 iff L_T(p) > 0 and some 6-neighbour q inside the volume with mask(q) = mask(p) has
+ *               0 < L_T(q) < L_T(p); otherwise out(p) = mask(p).
+ * Consequences (tests/test_volume_split_cpu.py asserts them on the restatement, tests/volume_split_cases.py):
+ *   - two surviving voxels with different non-zero labels are never 6-adjacent;
+ *   - a component with at most one seed comes back unchanged;
+ *   - voxels that T steps do not reach keep their class and may still bridge two parts;
+ *   - row H-1 of slice z and row 0 of slice z+1 are not neighbours, nor are the last voxel of a row and the first of the
+ *     next, nor volume n and volume n+1.
+ * The Python default reach (None) is 3 r for cube and 2 r for the other three structures: a cube erosion removes a
+ * Chebyshev ball, and the 6-neighbour growth needs up to 3 r steps to refill it (two touching balls of radius 8, centres 14
+ * apart, r = 4: cube at reach 8 leaves a bridge, at reach 12 it splits; the other structures split at reach 8).
+ * Not built: growth until nothing changes (it would need a readback inside the stream), EDT or h-maxima seeds,
+ * spacing-aware (anisotropic) growth, the 18-neighbour structure.
+ *
+ * Kernels (sq_volume_split.hip).  A fixed chain of launches on `stream`, no host readback, no memset or memcpy calls, no
+ * block waits on another, no flag is polled: the call can be captured in a graph.
+ *   seeds    : plane structures: one sq_mask_morph_u8 erosion launch on the (N D, H, W) view into the workspace's byte
+ *              plane.  cross and cube: ceil(r / SQ_MORPH3D_MAX_ITER) launches of sq_volume_morph_u8 (erosions compose
+ *              exactly at every C, see "Volume clean-up") that ping-pong between the workspace's byte plane and `out`,
+ *              which is free until the cut; the chain is ordered so that the last launch lands in the workspace plane.
+ *   labels   : sq_ccl.h's row scan (rows = N D H), merge with planes = D, compress; a label is the root's linear index + 1.
+ *              The first regrowth launch turns roots into labels as it reads.
+ *   regrowth : SQ_SPLIT3D_LDS=1 (environment, read per call): a block of 512 threads owns a brick of SQ_SPLIT3D_TILE_D x
+ *              SQ_SPLIT3D_TILE_H x SQ_SPLIT3D_TILE_W voxels and stages the class bytes and the int32 labels of the brick
+ *              and a halo of as many voxels as the launch runs steps, at most SQ_SPLIT3D_STEPS, on all three axes in LDS;
+ *              beyond the halo and the volume there is nothing.  Every thread owns up to 17 staged cells and precomputes
+ *              once which of them can still take a label and which of their 6 neighbours conduct (6 bits per cell); per
+ *              step it computes their new labels from LDS into registers -- the second copy a synchronous step needs --
+ *              and writes them after a barrier.  A step that changes nothing in the staged region ends the block's loop by
+ *              a block-uniform vote.  The brick's labels go to the other global plane; ceil(T / SQ_SPLIT3D_STEPS) launches
+ *              ping-pong between the two planes, the last one runs the remainder.  (8 + 4) x (16 + 4) x (32 + 4) = 8 640
+ *              staged cells for 4 096 useful (47 %) x 5 B = 43 200 B of static LDS (43 456 allocated), 66 VGPRs, no
+ *              spills: 3 blocks = 24 waves per CU (tools/resource_report.py: 6 waves per SIMD).  Measured against a halo
+ *              of 4 (15 360 cells, 76 800 B, 2 blocks per CU): 2 steps per launch are 0.75-0.82x its time.
+ *              SQ_SPLIT3D_LDS=0: one synchronous step per launch on the global planes, trivially the definition, the
+ *              in-tree cross-check and the A/B baseline of tools/volume_split_bench.py.  Same bits.  With the variable
+ *              unset the form is SQ_SPLIT3D_LDS_DEFAULT: the one that A/B measured faster (README.md has the figures).
+ *   cut      : one pointwise pass, labels + mask -> out.
+ *
+ * workspace: sq_volume_split_workspace(N, D, H, W) = 9 N D H W rounded up to 16 bytes (-1: a dimension < 1, or 2^31 or
+ * more elements): two int32 label planes and the seed plane; 16-B aligned, overlapping neither mask nor out.
+ * sq_volume_split_u8 returns SQ_EINVAL with a message, before any launch and with out and the workspace untouched, for
+ * null pointers, C < 2 or C > 256, a structure outside 0 .. 3, erosions outside 1 .. 16, reach outside 1 .. 64, a
+ * dimension < 1, 2^31 or more elements, a workspace that is not 16-B aligned or overlaps mask or out, and out overlapping
+ * mask.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_SPLIT3D_PLANE_CROSS 2
+#define SQ_SPLIT3D_PLANE_SQUARE 3
+#define SQ_SPLIT3D_MAX_EROSIONS 16
+#define SQ_SPLIT3D_MAX_REACH 64
+#define SQ_SPLIT3D_TILE_D 8
+#define SQ_SPLIT3D_TILE_H 16
+#define SQ_SPLIT3D_TILE_W 32
+#define SQ_SPLIT3D_STEPS 2
+#define SQ_SPLIT3D_LDS_DEFAULT 1
+int64_t sq_volume_split_workspace(int N, int D, int H, int W);
+int sq_volume_split_u8(const uint8_t *mask, uint8_t *out, int N, int D, int H, int W, int C, int erosions, int structure,
+                       int reach, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Label zones and the zone contact graph (sequitr_amd/analysis/neighbors.py: which cells are next to

@@ -109,6 +109,8 @@ SIGNATURES = {
     "sq_volume_fill_holes_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_int64, c_void_p, c_void_p]),
     "sq_volume_clear_border_workspace": (c_int64, [c_int] * 4),
     "sq_volume_clear_border_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p]),
+    "sq_volume_split_workspace": (c_int64, [c_int] * 4),
+    "sq_volume_split_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]),
     "sq_label_zones_workspace": (c_int64, [c_int, c_int, c_int]),
     "sq_label_zones_i32": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p]),
     "sq_zone_graph_workspace": (c_int64, [c_int]),

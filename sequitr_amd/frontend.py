@@ -845,7 +845,8 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     arrays in HBM, which drain to the host on a third stream while volume i+1 runs.  Returns (masks (N, Z, X, Y) uint8,
     logits (N, Z, X, Y, n_outputs) float32 or None) on the host.  With on_masks the masks are not downloaded: each
     volume's device mask is handed to on_masks(i, mask (1, Z, X, Y)) instead, valid until volume i+2 is started, and
-    the first value returned is None.  postprocess (a volumeops.VolumeCleanup or a step list) cleans each volume's
+    the first value returned is None.  postprocess (a volumeops.VolumeCleanup or a step list: 3-D morphology, fill_holes,
+    split3d, clear_border) cleans each volume's
     stitched mask on the compute stream with net.n_outputs classes before anything else sees it: the cleaned mask is
     what on_masks receives and what drains to the host.  Logits are not touched.  on_volume(i, raw, mask) is on_masks with
     the raw volume (1, Z, X, Y) as it was uploaded, still in HBM, next to the mask -- segment_frames' on_batch for volumes;

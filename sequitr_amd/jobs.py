@@ -368,7 +368,8 @@ def SERVER_segment_volume(params, options):
     volumeops.VolumeCleanup, with D, H, W = Z, X, Y) cleans every volume's mask in HBM, with and without ``brick``:
     ``mask.npy`` and the centroid file describe the cleaned masks and ``segment_volume.json`` records the steps, defaults
     written out, under ``volume_postprocess``.  A bad step list raises before any input is opened; without the key
-    nothing changes.  params['postprocess'], the planar list, stays refused.
+    nothing changes.  The steps: 3-D morphology, fill_holes, split3d (touching cells cut apart; ``split`` is the planar
+    step's name and is refused here), clear_border.  params['postprocess'], the planar list, stays refused.
 
     With ``brick``, options['measure'] measures every volume's objects in HBM (objects.measure_objects on the cleaned mask as
     it lies, D0, D1, D2 = Z, X, Y, 6-connected, against the RAW volume): ``objects.npz`` holds ObjectTable.columns() with

@@ -2,16 +2,23 @@
 UNet3D -- binary morphology per class with the 6- and 26-neighbour structures, filling of enclosed cavities, removal of
 objects cut by the volume's faces.  The reference has no counterpart; its users ran scipy.ndimage on a downloaded mask.npy.
 
-``morph3d``, ``fill_cavities`` and ``clear_border3d`` are one C-ABI call each (sq_volume_morph_u8, sq_volume_fill_holes_u8,
-sq_volume_clear_border_u8; include/sequitr_hip.h, "Volume clean-up", is the contract: classes, merge rules, scipy's
-definitions), or -- for the slice-by-slice variants, ``structure='plane_cross' | 'plane_square'`` and ``planar=True`` -- the
+``morph3d``, ``fill_cavities``, ``clear_border3d`` and ``split3d`` are one C-ABI call each (sq_volume_morph_u8,
+sq_volume_fill_holes_u8, sq_volume_clear_border_u8, sq_volume_split_u8; include/sequitr_hip.h, "Volume clean-up" and "Volume
+clean-up: splitting", is the contract: classes, merge rules, scipy's definitions), or -- for the slice-by-slice variants, ``structure='plane_cross' | 'plane_square'`` and ``planar=True`` -- the
 planar call of maskops on the zero-copy (N*D, H, W) view of the mask.  ``VolumeCleanup`` is a validated list of such steps
 that runs between two cached buffers; the volume jobs take one as ``params['volume_postprocess']`` and
 ``frontend.segment_volumes`` as ``postprocess``.  There is no CPU path.  Every call, the planar ones included, is a chain
 of kernel launches and can be captured in a graph and replayed.  Every result equals the scipy restatement in
-tests/volume_cleanup_cases.py exactly (tests/test_gpu_volume_cleanup.py).
+tests/volume_cleanup_cases.py and tests/volume_split_cases.py exactly (tests/test_gpu_volume_cleanup.py,
+tests/test_gpu_volume_split.py).
 
-Not built, each on purpose: a 3-D ``split`` (the planar regrowth cut has no volume kernel); the 18-neighbour structure
+``split3d`` separates touching cells: seeds are the 6-connected components of the eroded class planes (3-D erosions, or the
+planar ones slice by slice for z-stacks with few, thick slices), they grow back through their class for a bounded number of
+synchronous 6-neighbour steps, and a one-voxel sheet of background is cut where two different seeds' growths meet.  The step
+of a VolumeCleanup list is called ``split3d``; ``split`` is the planar step's name and stays refused in a volume list.
+
+Not built, each on purpose: growth until nothing changes, EDT or h-maxima seeds and spacing-aware growth for ``split3d``
+(voxels beyond ``reach`` keep their class and may still bridge two parts); the 18-neighbour structure
 (generate_binary_structure(3, 2)); more than MORPH3D_MAX_ITER iterations in one launch (use two steps, see the header
 for when they compose); anisotropic, spacing-aware structuring elements.  What follows the clean-up -- ``measure`` and
 ``neighbors`` for volumes -- is SERVER_segment_volume's options of those names with ``brick`` (objects.measure_objects and
@@ -27,10 +34,17 @@ MORPH3D_MAX_ITER = 4                                            # SQ_MORPH3D_MAX
 STRUCTURES3D = {'cross': 0, 'cube': 1}                          # generate_binary_structure(3, 1) / (3, 3)
 PLANE_STRUCTURES = {'plane_cross': 'cross', 'plane_square': 'square'}   # generate_binary_structure(2, k)[None]: per slice
 FACES = {'all': 0, 'lateral': 1}                                # SQ_FACES_ALL, SQ_FACES_LATERAL
+SPLIT3D_TILE = (8, 16, 32)                                      # SQ_SPLIT3D_TILE_D, _H, _W: a block's brick
+SPLIT3D_STEPS = 2                                               # SQ_SPLIT3D_STEPS: synchronous steps per launch = halo
+SPLIT3D_LDS_DEFAULT = 1                                         # SQ_SPLIT3D_LDS_DEFAULT: the form when SQ_SPLIT3D_LDS is unset
+SPLIT3D_MAX_REACH = 64                                          # SQ_SPLIT3D_MAX_REACH
+SPLIT3D_MAX_EROSIONS = 16                                       # SQ_SPLIT3D_MAX_EROSIONS
+SPLIT3D_STRUCTURES = {'cross': 0, 'cube': 1, 'plane_cross': 2, 'plane_square': 3}   # SQ_MORPH3D_*, SQ_SPLIT3D_PLANE_*
 
 # op -> the keys a step may carry besides 'op', with their defaults
 _STEP_KEYS = dict({op: {'iterations': 1, 'structure': 'cross'} for op in MORPH_OPS},
-                  fill_holes={'max_voxels': None, 'planar': False}, clear_border={'faces': 'all'})
+                  fill_holes={'max_voxels': None, 'planar': False}, clear_border={'faces': 'all'},
+                  split3d={'erosions': None, 'structure': 'cross', 'reach': None})
 
 
 def _slices(t):
@@ -102,13 +116,45 @@ def clear_border3d(mask, faces='all', classes=None, out=None, workspace=None):
     return out
 
 
+def default_reach3d(erosions, structure):
+    """the reach that None stands for: a cube erosion removes a Chebyshev ball, which the 6-neighbour growth needs up to
+    3 r steps to refill; the other structures' balls refill in 2 r"""
+    return (3 if structure == 'cube' else 2) * erosions
+
+
+def split3d(mask, erosions, structure='cross', reach=None, classes=None, out=None, workspace=None):
+    """Cut a one-voxel sheet of background between the parts of an object (include/sequitr_hip.h, "Volume clean-up:
+    splitting").  Seeds are the 6-connected components of every class plane eroded `erosions` = 1 .. SPLIT3D_MAX_EROSIONS
+    times with `structure` ('cross', 'cube', or 'plane_cross' / 'plane_square': the planar erosion slice by slice); they
+    grow back through their class for `reach` = 1 .. SPLIT3D_MAX_REACH synchronous 6-neighbour steps (None: 3 * erosions
+    for 'cube', 2 * erosions otherwise), the smallest label winning where several arrive together, and a labelled voxel
+    with a same-class neighbour of a smaller label becomes background.  Everything else is unchanged; bytes >= classes
+    pass through."""
+    if structure not in SPLIT3D_STRUCTURES:
+        raise ValueError("structure must be one of %s, got %r" % (sorted(SPLIT3D_STRUCTURES), structure))
+    erosions = int(erosions)
+    if not 1 <= erosions <= SPLIT3D_MAX_EROSIONS:
+        raise ValueError("erosions must be 1 .. %d, got %d" % (SPLIT3D_MAX_EROSIONS, erosions))
+    reach = default_reach3d(erosions, structure) if reach is None else int(reach)
+    if not 1 <= reach <= SPLIT3D_MAX_REACH:
+        raise ValueError("reach must be 1 .. %d, got %d" % (SPLIT3D_MAX_REACH, reach))
+    classes = maskops._check_mask(mask, classes, 4)
+    out = maskops._check_out(out, mask)
+    lib = _lib.load()
+    ws = maskops._workspace(lib.sq_volume_split_workspace, mask, workspace)
+    _lib.check(lib.sq_volume_split_u8(mask.data_ptr(), out.data_ptr(), *(maskops._dims(mask) + (
+        classes, erosions, SPLIT3D_STRUCTURES[structure], reach, ws.data_ptr(), maskops._stream(mask)))), "sq_volume_split_u8")
+    return out
+
+
 class VolumeCleanup(maskops._Cleanup):
     """A validated list of clean-up steps for volumes, e.g. [{"op": "open", "iterations": 1, "structure": "cross"},
-    {"op": "fill_holes", "max_voxels": 500}, {"op": "clear_border", "faces": "lateral"}].  Unknown ops, unknown keys and
+    {"op": "fill_holes", "max_voxels": 500}, {"op": "split3d", "erosions": 4}, {"op": "clear_border", "faces": "lateral"}].  Unknown ops, unknown keys and
     bad values raise a ValueError that names them, at construction.  ``apply`` runs the steps in order on a batch of
     (N,D,H,W) device masks."""
     LABEL, RANK, STEP_KEYS = 'volume_postprocess', 4, _STEP_KEYS
-    NOT_BUILT = {'split': "'split' is not a step for volumes: a 3-D split is not built"}
+    NOT_BUILT = {'split': "'split' is not a step for volumes: a 3-D split is not built under that name, "
+                          "the volume step is called 'split3d'"}
 
     def _check_step(self, where, op, full):
         if op in MORPH_OPS:
@@ -124,6 +170,13 @@ class VolumeCleanup(maskops._Cleanup):
                 raise ValueError("%s: max_voxels must be a positive integer or null, got %r" % (where, full['max_voxels']))
             if not isinstance(full['planar'], bool):
                 raise ValueError("%s: planar must be true or false, got %r" % (where, full['planar']))
+        elif op == 'split3d':
+            if not maskops._is_int(full['erosions'], 1, SPLIT3D_MAX_EROSIONS):
+                raise ValueError("%s: erosions must be an integer 1 .. %d, got %r" % (where, SPLIT3D_MAX_EROSIONS, full['erosions']))
+            if not isinstance(full['structure'], str) or full['structure'] not in SPLIT3D_STRUCTURES:
+                raise ValueError("%s: structure must be one of %s, got %r" % (where, sorted(SPLIT3D_STRUCTURES), full['structure']))
+            if full['reach'] is not None and not maskops._is_int(full['reach'], 1, SPLIT3D_MAX_REACH):
+                raise ValueError("%s: reach must be an integer 1 .. %d or null, got %r" % (where, SPLIT3D_MAX_REACH, full['reach']))
         elif not isinstance(full['faces'], str) or full['faces'] not in FACES:
             raise ValueError("%s: faces must be one of %s, got %r" % (where, sorted(FACES), full['faces']))
 
@@ -131,6 +184,8 @@ class VolumeCleanup(maskops._Cleanup):
         if s['op'] == 'fill_holes':
             return lib.sq_mask_fill_holes_workspace(dims[0] * dims[1], *dims[2:]) if s['planar'] \
                 else lib.sq_volume_fill_holes_workspace(*dims)
+        if s['op'] == 'split3d':
+            return lib.sq_volume_split_workspace(*dims)
         return lib.sq_volume_clear_border_workspace(*dims) if s['op'] == 'clear_border' else 0
 
     def _run(self, s, src, classes, dst, ws):
@@ -138,5 +193,7 @@ class VolumeCleanup(maskops._Cleanup):
             morph3d(src, s['op'], s['iterations'], s['structure'], classes, out=dst)
         elif s['op'] == 'fill_holes':
             fill_cavities(src, s['max_voxels'], s['planar'], classes, out=dst, workspace=ws)
+        elif s['op'] == 'split3d':
+            split3d(src, s['erosions'], s['structure'], s['reach'], classes, out=dst, workspace=ws)
         else:
             clear_border3d(src, s['faces'], classes, out=dst, workspace=ws)
