@@ -1710,6 +1710,63 @@ int64_t sq_zone_graph3d_workspace(int max_pairs);
 int sq_zone_graph3d(const int32_t *zones, int N, int D, int H, int W, int max_label, int64_t *stats, int32_t *pairs,
                     int max_pairs, int32_t *count, int32_t *dropped, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Label overlap and relabelling (sequitr_amd/analysis/linking.py: which object of frame t + 1 is the same cell as which
+ * object of frame t).  The reference hands tracking to an external program; here the per-position part of linking by
+ * overlap -- the contingency table of two label stacks -- and the rewriting of per-frame ranks into track IDs run on the
+ * device.  A frame is P positions: H W pixels or D H W voxels alike.  Only integer arithmetic: the same bits on every
+ * run.  Neither call reads anything back, waits on a flag or lets one block wait on another: both can be captured in a
+ * graph, and whatever is cleared is cleared by a kernel of the call's own chain.
+ *
+ * sq_label_overlap.  a, b (N, P) int32; values outside 1 .. max_label count as 0.
+ *   pairs (max_pairs, 4) int32 [n, la, lb, overlap], in no particular order: one row per distinct (n, la, lb) with la > 0
+ *       and lb > 0 that occurs, overlap = the number of positions p with a[n,p] == la && b[n,p] == lb.
+ *   area_a, area_b (N, max_label + 1) int64, each may be NULL: the number of positions per label in a / in b.  Row 0
+ *       stays 0.
+ *   count (device int32): the number of rows written, at most max_pairs.
+ *   dropped (device int32): 0 iff the rows are complete, as in sq_zone_graph: it counts the runs that found no free slot
+ *       in the table plus the distinct triples that found no row; when it is not 0 the caller comes back with a larger
+ *       max_pairs.  The areas are complete either way.
+ * labels[:-1] and labels[1:] of one contiguous (F, ...) stack are valid a and b: nothing is assumed about the alignment
+ * of b beyond 4 bytes, nor about P.
+ * Two forms, which give the same table:
+ *   one-lane  : a wave takes 4 groups of 64 consecutive positions of a frame at a time, one lane per position, all 8 loads
+ *               issued before the first is used; a group without a label in either stack (most of a frame is background)
+ *               is left after one ballot.  Runs of equal (la, lb) along memory are found with a shuffle and a ballot; the
+ *               run's leader lane makes one insert-and-add of the run's
+ *               length into an open-addressing table in the workspace (a 64-bit key n << 42 | la << 21 | lb claimed with a
+ *               compare-and-swap, a 32-bit integer add for the count; the smallest power of two >= 2 max_pairs slots).  The
+ *               areas likewise: one 64-bit add per run of equal label, never one per position.
+ *   four-lane : 16-byte loads, four positions per lane, 2 groups of 256 positions at a time; taken only when a and b are
+ *               16-byte aligned and P % 4 == 0 (every frame then starts on 16 bytes and no quad straddles two frames).  Runs are
+ *               merged inside the lane first: a lane whose four keys are equal enters the wave's run search with a weight
+ *               of 4, a lane that sees a change adds its at most four runs itself.
+ *   The environment variable SQ_LINK_VEC=0|1, read per call, selects the one-lane / four-lane form; without it
+ *   SQ_LINK_VEC_DEFAULT holds: the one-lane form, which is the faster one with the areas, as the linker calls it (DESIGN.md
+ *   has the figures; without the areas the four-lane form is).  A second kernel writes the rows.
+ * Sums of integers: the set of rows and every count are independent of the order in which the atomics arrive.
+ * workspace: sq_label_overlap_workspace(max_pairs) bytes = 12 per slot rounded up to 16 (-1: max_pairs outside 1 .. 2^28).
+ * SQ_EINVAL with a message, before any launch: null a, b, pairs, count, dropped or workspace; N < 1, N >= 2^21, P < 1,
+ * P >= 2^31 (N P >= 2^63 cannot then occur); max_label outside 1 .. 2^21 - 1; max_pairs outside 1 .. 2^28; a workspace
+ * that is not 16-B aligned or overlaps an input or an output; area arrays that are not 8-B aligned.
+ *
+ * sq_relabel_lut_i32.  labels, out (N, P) int32; offsets (N + 1) device int64, non-decreasing within 0 .. lut_len; lut
+ * (lut_len) device int32.  With L = labels[n,p]:
+ *   out[n,p] = lut[offsets[n] + L - 1]   if 1 <= L <= offsets[n+1] - offsets[n],   0 otherwise.
+ * The call cannot validate device data: an entry that would be read outside 0 .. lut_len - 1 reads as 0.
+ * out == labels (in place) is allowed; any other overlap of out with labels, offsets or lut is refused.  A streaming
+ * kernel: 16-byte loads and stores when labels and out are 16-byte aligned and P % 4 == 0, a scalar path otherwise.
+ * It turns each object's per-frame rank into its track ID, so that a cell keeps one value through the movie.
+ * SQ_EINVAL with a message, before any launch: null labels, out or offsets; null lut with lut_len > 0; lut_len < 0;
+ * N < 1, N >= 2^21, P < 1, P >= 2^31; offsets not 8-B aligned; a refused overlap.
+ * ---------------------------------------------------------------------------------------- */
+#define SQ_LINK_VEC_DEFAULT 0
+int64_t sq_label_overlap_workspace(int max_pairs);
+int sq_label_overlap(const int32_t *a, const int32_t *b, int N, int64_t P, int max_label, int64_t *area_a, int64_t *area_b,
+                     int32_t *pairs, int max_pairs, int32_t *count, int32_t *dropped, void *workspace, void *stream);
+int sq_relabel_lut_i32(const int32_t *labels, int32_t *out, int N, int64_t P, const int64_t *offsets, const int32_t *lut,
+                       int64_t lut_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,9 @@ SIGNATURES = {
     "sq_label_zones3d_i32": (c_int, [c_void_p] * 3 + [c_int] * 6 + [ctypes.c_double, c_void_p, c_void_p]),
     "sq_zone_graph3d_workspace": (c_int64, [c_int]),
     "sq_zone_graph3d": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int] + [c_void_p] * 4),
+    "sq_label_overlap_workspace": (c_int64, [c_int]),
+    "sq_label_overlap": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 4),
+    "sq_relabel_lut_i32": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "sq_dense_workspace_f32":(c_int64, [c_int, c_int, c_int]),
     "sq_dense_fwd_f32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "sq_convT_conv3x3_fwd_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

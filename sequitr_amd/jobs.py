@@ -598,10 +598,24 @@ def SERVER_segment_frames(params, options):
     options['save_zones'] adds ``zones.npy`` (F,H,W) int32.  params['d_thresh'] (default 100.0), params['zone_reach'] (the
     zones' max_distance, default none) and params['neighbor_seeds'] ('objects' or 'centroids'); a bad value raises before a
     frame is opened.  The table describes the mask after `postprocess` and the size filter: dropped objects are no seeds.
-    Without the option every file is what it was."""
+    Without the option every file is what it was.
+
+    options['link'] (implies measure) links every object to its successor in the next frame while the batch's labels are
+    in HBM (sequitr_amd/analysis/linking.py: overlap tracks and divisions; its module text is the rule): ``lineage.npz``
+    holds TrackTable.columns() of the whole stack -- ``track`` has one entry per row of ``objects.npz`` -- and segment.json a
+    ``link`` record (objects, tracks, links, divisions, roots and the parameters with their defaults filled in);
+    options['save_track_labels'] adds ``track_labels.npy`` (F,H,W) int32, every object's pixels holding its track ID, so
+    that a cell keeps one value through the movie.  params['link_reach'] (0), params['link_min_iou'] (0.0),
+    params['link_min_overlap'] (1), params['link_divisions'] (true), params['link_min_child_fraction'] (0.5) and
+    params['link_same_class'] (true); a bad value raises before a frame is opened.  The result does not depend on
+    frames_per_batch.  Without the option every file is what it was."""
     _refuse_volume_postprocess(params, 'SERVER_segment_frames')
     postprocess = _parse_postprocess(params)                    # before anything is opened
     want_neighbors = bool(options.get('neighbors'))
+    want_link = bool(options.get('link'))
+    if want_link:                                               # a bad value raises here, before a frame is opened
+        from .analysis.linking import DEFAULTS as link_defaults, FrameLinker
+        linker = FrameLinker(**{k: params.get('link_' + k, v) for k, v in link_defaults.items()})
     if want_neighbors:                                          # a bad value raises here, before a frame is opened
         from .analysis.neighbors import check_params
         d_thresh, zone_reach, neighbor_seeds = check_params(params.get('d_thresh', 100.0), params.get('zone_reach'),
@@ -626,7 +640,7 @@ def SERVER_segment_frames(params, options):
     net = UNet2D(net_p, 'infer')
     _load_net_weights(net, params)
     per_frame = {}
-    want_measure = bool(options.get('measure')) or want_neighbors
+    want_measure = bool(options.get('measure')) or want_neighbors or want_link
     want_centroids = bool(options.get('centroids')) or want_measure
     masks = np.empty((F, H, W), np.uint8) if want_centroids else None
     min_area, max_area = int(params.get('min_area') or 1), params.get('max_area')
@@ -638,6 +652,8 @@ def SERVER_segment_frames(params, options):
     neighbor_tables = []
     zone_stack = np.empty((F, H, W), np.int32) if want_neighbors and options.get('save_zones') else None
     num_classes = int(net_p.get('num_outputs', 2))
+    track_stack = np.empty((F, H, W), np.int32) if want_link and options.get('save_track_labels') else None
+    kept_labels = []                                            # with save_track_labels: the batches' label frames, in HBM
 
     def sink(first, m):                                       # centroids need the masks while they are in HBM
         from .centroids import mask_centroids
@@ -650,7 +666,7 @@ def SERVER_segment_frames(params, options):
         from .objects import measure_objects
         image = raw if raw.dim() == 3 else raw[measure_channel]   # (C, n, H, W) planes: the channel's slice as it lies
         t = measure_objects(m, image=image, min_area=min_area, max_area=max_area,
-                            labels=label_stack is not None or want_neighbors, filtered_mask=bounded)
+                            labels=label_stack is not None or want_neighbors or want_link, filtered_mask=bounded)
         masks[first:first + m.shape[0]] = (t.mask if bounded else m).cpu().numpy()
         if label_stack is not None:
             label_stack[first:first + m.shape[0]] = t.labels.cpu().numpy()
@@ -662,6 +678,10 @@ def SERVER_segment_frames(params, options):
                 zone_stack[first:first + m.shape[0]] = nt.zones.cpu().numpy()
                 nt.zones = None
             neighbor_tables.append(nt)
+        if want_link:                                           # batches arrive in the stack's order
+            linker.push(first, t.labels, t)
+            if track_stack is not None:
+                kept_labels.append((first, t.labels))
         tables.append(t)
         firsts.append(first)
 
@@ -711,6 +731,20 @@ def SERVER_segment_frames(params, options):
             info['neighbors'] = {'objects': len(ntable), 'pairs': int(ntable.n_pairs),
                                  'pairs_removed': int(ntable.n_pairs_removed), 'num_classes': num_classes,
                                  'd_thresh': d_thresh, 'zone_reach': zone_reach, 'neighbor_seeds': neighbor_seeds}
+        if want_link:
+            from .analysis.linking import relabel
+            tracks = linker.finish()
+            np.savez(os.path.join(out_dir, 'lineage.npz'), **tracks.columns())
+            if track_stack is not None:                         # ranks -> track IDs on the device, batch by batch
+                offsets, lut = tracks.lut()
+                lut_d = torch.from_numpy(lut).to(device)
+                for first, lab in kept_labels:
+                    n = int(lab.shape[0])
+                    track_stack[first:first + n] = relabel(lab, offsets[first:first + n + 1], lut_d, out=lab).cpu().numpy()
+                np.save(os.path.join(out_dir, 'track_labels.npy'), track_stack)
+            info['link'] = dict(tracks.options, objects=len(tracks.track), tracks=len(tracks), links=len(tracks.links),
+                                divisions=int((tracks.children[:, 0] > 0).sum()),
+                                roots=int((tracks.parent == tracks.ID).sum()))
     elif want_centroids:
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
