@@ -626,6 +626,38 @@ int sq_objects_relabel(const uint8_t *mask, int N, int planes, int H, int W, con
                        const int32_t *rank, int n_slots, int32_t *labels, uint8_t *mask_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Shape of the measured objects: second-order coordinate sums, exposed faces, boundary voxels and the counts of the
+ * 4-neighbourhood perimeter estimator (regionprops' `perimeter`), all integers defined on the mask.
+ * sq_objects_shape reads the workspace the measure call on the same mask left behind, as sq_objects_relabel does:
+ *   workspace, n_slots: that call's workspace and max_out;  slots, n: that call's `slots` and its count.
+ *   shape_workspace: sq_objects_shape_workspace(n_slots) bytes (-1: n_slots < 1) = 104 per slot rounded up to 16, 16-B
+ *     aligned; the call clears it.
+ *   shape_i (n,16) int64: row i describes the object of row i of the measure call's rows_i / rows_f, in the same
+ *     unsorted order, so the host applies one permutation to all three.
+ * Coordinates are (p, r, c) = plane, row, column within the frame.  "Same object" = same root of the labelling.  A
+ * neighbour outside the frame is not in the object; nothing connects across frames.  The columns:
+ *    0- 2  s_p, s_r, s_c                       sum of p, r, c over the object's voxels (s_p = 0 when planes == 1)
+ *    3- 8  s_pp, s_rr, s_cc, s_pr, s_pc, s_rc  sums of the products over the object's voxels
+ *    9-11  faces_p, faces_r, faces_c           the (voxel, +/- direction along the axis) pairs whose neighbour is outside
+ *                                              the frame or carries another byte; faces_p = 0 when planes == 1
+ *   12     boundary                            voxels with at least one such exposed face (4 neighbours when planes == 1,
+ *                                              6 otherwise)
+ *   13-15  per_straight, per_diag, per_mixed   planar masks only (0 when planes > 1): with B = the object's boundary
+ *          pixels, every pixel of B gets code = 1 + 2 n4 + 10 n8, n4 = its 4 edge neighbours that are in B OF THE SAME
+ *          OBJECT, n8 the same for its 4 diagonal neighbours; codes 5, 7, 15, 17, 25, 27 count in per_straight, 21, 33 in
+ *          per_diag, 13, 23 in per_mixed, every other code nowhere.  This is the 3 x 3 kernel [[10,2,10],[2,1,2],[10,2,10]]
+ *          over the border image of one object's crop; perimeter = per_straight + per_diag sqrt(2) + per_mixed (1 + sqrt(2)) / 2.
+ * planes, H and W may not exceed 65536: with fewer than 2^31 voxels per call that keeps every sum below 2^63
+ * (a product of two coordinates is below 2^32), so the sums are exact and independent of the order of the atomics.
+ * SQ_EINVAL with a message, before any launch and leaving shape_i untouched, for null pointers, n < 0 or n > n_slots,
+ * a workspace / shape / n_slots that does not match the measure call that filled the workspace, workspaces that are
+ * not 16-B aligned, planes, H or W above 65536.  n == 0 succeeds and writes nothing.
+ * ---------------------------------------------------------------------------------------- */
+int64_t sq_objects_shape_workspace(int max_out);
+int sq_objects_shape(const uint8_t *mask, int N, int planes, int H, int W, const void *workspace, int n_slots,
+                     const int32_t *slots, int n, void *shape_workspace, int64_t *shape_i, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * EDT weight maps (the step in front of the training hot path).
  * ImageWeightMap.pipe, sequitr/pipeline.py:475-479:
  *   d = distance_transform_edt(1 - image);  out = w0*(1-image)*exp(-(d*d)/(2 sigma^2 + 1e-99)) + image + 1

@@ -58,6 +58,8 @@ SIGNATURES = {
     "sq_objects_measure": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int, c_int64, c_int64] + [c_void_p] * 6
                            + [c_int, c_void_p]),
     "sq_objects_relabel": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "sq_objects_shape_workspace": (c_int64, [c_int]),
+    "sq_objects_shape": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 3),
     "sq_weightmap_workspace": (c_int64, [c_int, c_int, c_int]),
     "sq_edt_sq_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "sq_weightmap_edt_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -16,21 +16,11 @@
 // the last bits of sum and sumsq may differ from run to run.  Minimum and maximum of float32 images go through an
 // order-preserving unsigned encoding and integer atomicMin / atomicMax: exact, and NaN pixels are left out of them (a NaN
 // pixel makes sum and sumsq NaN).
-#include "sq_ccl.h"
+#include "sq_objects.h"
 
 #include <mutex>
 
 namespace {
-
-// one object's accumulators, 88 bytes; rows of the table at the start of the workspace
-struct ObjAcc {
-    u64 area, srow, scol, splane;                              // pixel count and the three coordinate sums
-    u64 isum, isumsq;                                          // integer images: u64; float32 images: the bits of a double
-    int lo[3], hi[3];                                          // box along (plane, row, column), hi exclusive
-    unsigned imin, imax;                                       // integer images: the value; float32: ord_f32 of it
-    int root, pad;
-};
-static_assert(sizeof(ObjAcc) == 88, "ObjAcc layout");
 
 __device__ __forceinline__ unsigned ord_f32(float x) {          // a < b  <=>  ord(a) < ord(b), for all non-NaN a, b
     const unsigned u = __float_as_uint(x);
@@ -227,19 +217,15 @@ __global__ __launch_bounds__(256) void obj_relabel_kernel(const uint8_t *__restr
     }
 }
 
-inline int64_t obj_table_bytes(int max_out) { return ((int64_t)max_out * (int64_t)sizeof(ObjAcc) + 15) / 16 * 16; }
-
-// what the last sq_objects_measure calls left in which workspace (host side): sq_objects_relabel reads a workspace only
-// under the geometry it was filled with
-struct ObjFilled {
-    const void *workspace;
-    int N, planes, H, W, max_out;
-};
+// sq_objects.h: sq_objects_relabel and sq_objects_shape read a workspace only under the geometry it was filled with
+typedef SqObjFilled ObjFilled;
 std::mutex obj_filled_lock;
 ObjFilled obj_filled[16];
 unsigned obj_filled_next = 0;
 
-void obj_remember(const void *workspace, int N, int planes, int H, int W, int max_out) {
+}  // namespace
+
+void sq_obj_remember(const void *workspace, int N, int planes, int H, int W, int max_out) {
     std::lock_guard<std::mutex> hold(obj_filled_lock);
     ObjFilled *e = nullptr;
     for (ObjFilled &f : obj_filled)
@@ -248,7 +234,7 @@ void obj_remember(const void *workspace, int N, int planes, int H, int W, int ma
     *e = ObjFilled{workspace, N, planes, H, W, max_out};
 }
 
-bool obj_recall(const void *workspace, ObjFilled *out) {
+bool sq_obj_recall(const void *workspace, SqObjFilled *out) {
     std::lock_guard<std::mutex> hold(obj_filled_lock);
     for (const ObjFilled &f : obj_filled)
         if (f.workspace == workspace) {
@@ -257,8 +243,6 @@ bool obj_recall(const void *workspace, ObjFilled *out) {
         }
     return false;
 }
-
-}  // namespace
 
 extern "C" int64_t sq_objects_workspace(int N, int planes, int H, int W, int max_out) {
     if (N <= 0 || planes <= 0 || H <= 0 || W <= 0 || max_out <= 0) return -1;
@@ -286,7 +270,7 @@ extern "C" int sq_objects_measure(const uint8_t *mask, int N, int planes, int H,
     int *slot = parent + total;
     const int rows = N * planes * H;
     const int pix = image ? dtype : -1;
-    obj_remember(workspace, N, planes, H, W, max_out);
+    sq_obj_remember(workspace, N, planes, H, W, max_out);
     if (hipMemsetAsync(count, 0, sizeof(int32_t), st) != hipSuccess || hipMemsetAsync(found, 0, sizeof(int32_t), st) != hipSuccess) {
         sq_set_error("%s: cannot clear the counters", who);
         return SQ_ELAUNCH;
@@ -319,7 +303,7 @@ extern "C" int sq_objects_relabel(const uint8_t *mask, int N, int planes, int H,
                "%s: the mask must have fewer than 2^31 elements", who);
     SQ_REQUIRE((((uintptr_t)workspace) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
     ObjFilled f;
-    SQ_REQUIRE(obj_recall(workspace, &f), "%s: n_slots %d matches nothing: sq_objects_measure has not filled this workspace",
+    SQ_REQUIRE(sq_obj_recall(workspace, &f),"%s: n_slots %d matches nothing: sq_objects_measure has not filled this workspace",
                who, n_slots);
     SQ_REQUIRE(f.N == N && f.planes == planes && f.H == H && f.W == W && f.max_out == n_slots,
                "%s: n_slots %d and mask (%d,%d,%d,%d) do not match the sq_objects_measure call that filled this workspace "

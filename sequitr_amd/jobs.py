@@ -210,11 +210,11 @@ def _brick_volumes(params, options):
     return device, x, (bz, bx, by), margin, geometry
 
 
-VOLUME_ANALYSIS_OPTIONS = ('measure', 'save_labels', 'neighbors', 'save_zones')
+VOLUME_ANALYSIS_OPTIONS = ('measure', 'save_labels', 'neighbors', 'save_zones', 'shape')
 
 
 def _parse_volume_analysis(params, options):
-    """options['measure'] / ['save_labels'] / ['neighbors'] / ['save_zones'] of SERVER_segment_volume, before any input is
+    """options['measure'] / ['save_labels'] / ['neighbors'] / ['save_zones'] / ['shape'] of SERVER_segment_volume, before any input is
     opened: None without them, else a dict of what they ask for with the neighbour parameters checked and their defaults
     filled in.  They need params['brick']; a bad value raises here."""
     asked = [k for k in VOLUME_ANALYSIS_OPTIONS if options.get(k)]
@@ -234,6 +234,10 @@ def _parse_volume_analysis(params, options):
         from .analysis.neighbors import check_params, check_spacing
         a['d_thresh'], a['zone_reach'], a['neighbor_seeds'] = check_params(
             params.get('d_thresh', 100.0), params.get('zone_reach'), params.get('neighbor_seeds', 'objects'))
+        a['spacing'] = check_spacing(params.get('spacing', 1.0))
+    a['shape'] = bool(options.get('shape'))
+    if a['shape']:                                              # the metric shape columns read the same depth spacing
+        from .analysis.neighbors import check_spacing
         a['spacing'] = check_spacing(params.get('spacing', 1.0))
     return a
 
@@ -279,7 +283,7 @@ def _segment_volume_bricks(params, options, cleanup=None, analysis=None):
     def measure_sink(i, raw, m):                               # objects against the raw volume, both in HBM as they lie
         from .objects import measure_objects
         t = measure_objects(m, image=raw, min_area=analysis['min_area'], max_area=analysis['max_area'],
-                            labels=label_stack is not None or analysis['neighbors'], filtered_mask=bounded)
+                            labels=label_stack is not None or analysis['neighbors'], filtered_mask=bounded, shape=analysis['shape'])
         if label_stack is not None:
             label_stack[i] = t.labels[0].cpu().numpy()
         if analysis['neighbors']:                               # on the kept objects' labels, while the volume is in HBM
@@ -327,12 +331,15 @@ def _segment_volume_bricks(params, options, cleanup=None, analysis=None):
     if analysis:
         from .objects import ObjectTable
         table = ObjectTable.concatenate([tables[i] for i in range(N)], list(range(N)), N)
-        np.savez(os.path.join(out_dir, 'objects.npz'), **table.columns())
+        np.savez(os.path.join(out_dir, 'objects.npz'), **table.columns(spacing=analysis.get('spacing', 1.0)))
         if label_stack is not None:
             np.save(os.path.join(out_dir, 'labels.npy'), label_stack)
         info['objects'] = {'count': len(table), 'found': int(table.found), 'min_area': analysis['min_area'],
                            'max_area': None if analysis['max_area'] is None else int(analysis['max_area']),
                            'with_intensity': True}
+        if analysis['shape']:                                   # the record's own 'shape' key is the volumes' shape
+            info['objects']['shape'] = True
+            info['objects']['spacing'] = analysis['spacing']
         if analysis['neighbors']:
             from .analysis.neighbors import NeighborTable
             ntable = NeighborTable.concatenate([neighbor_tables[i] for i in range(N)], list(range(N)), N)
@@ -381,7 +388,10 @@ def SERVER_segment_volume(params, options):
     in, options['save_zones'] adds ``zones.npy`` (N,Z,X,Y) int32.  params['d_thresh'] (100.0, in in-plane pixels),
     params['zone_reach'] (none), params['neighbor_seeds'] ('objects') and params['spacing'] (1.0: the slice spacing in
     in-plane pixels, SERVER_train_volume's key); a bad value raises before any input is opened, and so do these four options
-    without ``brick``.  Without them every file is what it was.
+    without ``brick``.  Without them every file is what it was.  options['shape'] (implies measure, refused without
+    ``brick`` like its siblings) adds the shape columns and the columns derived from them under params['spacing']
+    (covariance, axis_lengths, equivalent_diameter, extent, surface_area, sphericity; ObjectTable's docstrings are the
+    formulas) to ``objects.npz``, and the json's ``objects`` record gains ``shape: true`` and ``spacing``.
 
     ``segment_volume.json``: ``seconds`` / ``mvoxels_per_s`` cover the volumes (upload, network, download);
     ``setup_seconds`` is weights plus one warm-up volume."""
@@ -608,7 +618,13 @@ def SERVER_segment_frames(params, options):
     that a cell keeps one value through the movie.  params['link_reach'] (0), params['link_min_iou'] (0.0),
     params['link_min_overlap'] (1), params['link_divisions'] (true), params['link_min_child_fraction'] (0.5) and
     params['link_same_class'] (true); a bad value raises before a frame is opened.  The result does not depend on
-    frames_per_batch.  Without the option every file is what it was."""
+    frames_per_batch.  Without the option every file is what it was.
+
+    options['shape'] (implies measure) adds the shape columns (objects.measure_objects(shape=True): second-order moments,
+    exposed faces, boundary pixels, perimeter counts) and the columns derived from them (covariance, axis_lengths,
+    eccentricity, orientation, equivalent_diameter, extent, perimeter, crack_perimeter, circularity; ObjectTable's
+    docstrings are the formulas) to ``objects.npz``, for the cleaned mask behind `postprocess` and the size filter, as
+    `measure` does; segment.json's ``objects`` record gains ``shape: true``.  Without the option every file is what it was."""
     _refuse_volume_postprocess(params, 'SERVER_segment_frames')
     postprocess = _parse_postprocess(params)                    # before anything is opened
     want_neighbors = bool(options.get('neighbors'))
@@ -640,7 +656,8 @@ def SERVER_segment_frames(params, options):
     net = UNet2D(net_p, 'infer')
     _load_net_weights(net, params)
     per_frame = {}
-    want_measure = bool(options.get('measure')) or want_neighbors or want_link
+    want_shape = bool(options.get('shape'))
+    want_measure = bool(options.get('measure')) or want_neighbors or want_link or want_shape
     want_centroids = bool(options.get('centroids')) or want_measure
     masks = np.empty((F, H, W), np.uint8) if want_centroids else None
     min_area, max_area = int(params.get('min_area') or 1), params.get('max_area')
@@ -666,7 +683,7 @@ def SERVER_segment_frames(params, options):
         from .objects import measure_objects
         image = raw if raw.dim() == 3 else raw[measure_channel]   # (C, n, H, W) planes: the channel's slice as it lies
         t = measure_objects(m, image=image, min_area=min_area, max_area=max_area,
-                            labels=label_stack is not None or want_neighbors or want_link, filtered_mask=bounded)
+                            labels=label_stack is not None or want_neighbors or want_link, filtered_mask=bounded, shape=want_shape)
         masks[first:first + m.shape[0]] = (t.mask if bounded else m).cpu().numpy()
         if label_stack is not None:
             label_stack[first:first + m.shape[0]] = t.labels.cpu().numpy()
@@ -721,6 +738,8 @@ def SERVER_segment_frames(params, options):
         info['centroids'] = {'file': os.path.basename(cw.filename), 'objects': len(table)}
         info['objects'] = {'count': len(table), 'found': int(table.found), 'min_area': min_area,
                            'max_area': None if max_area is None else int(max_area), 'with_intensity': True}
+        if want_shape:                                          # the record's own 'shape' key is the frames' shape
+            info['objects']['shape'] = True
         if want_neighbors:
             from .analysis.neighbors import NeighborTable
             order = np.argsort(firsts, kind='stable')           # batches in the stack's order: indices become global rows
