@@ -1030,6 +1030,73 @@ int sq_frames_to_tiles_mc(const void *frames, int dtype, int64_t chan_stride, co
                           int TS, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tile views and probability stitch: test-time augmentation over the symmetries of the square, and per-pixel class
+ * probabilities stitched to whole frames (sequitr_amd/frontend.py: FrameTiler.view, FrameTiler.stitch_probs,
+ * segment_frames(tta=, probabilities=)).  The reference samples the same symmetries on the training side (ImageFlip's four
+ * flip states, the quarter turns of ImageRotate; sequitr/pipeline.py); here a trained net is evaluated under them and its
+ * logits averaged, all in HBM.
+ *
+ * VIEWS.  A tile batch is (N, T, T, E) float32: square tiles, E interleaved elements per pixel (C input channels or K
+ * class logits), 1 <= E <= 16.  op is 0 .. 7: bit 0 mirrors axis 1, bit 1 mirrors axis 2, bit 2 transposes the two axes
+ * (the role of the volume sampler's transpose bit):
+ *
+ *     view_op(x)[n, i, j, e] = x[n, a, b, e]
+ *     (p, q) = (j, i) if op & 4 else (i, j)
+ *     a = T-1-p if op & 1 else p
+ *     b = T-1-q if op & 2 else q
+ *
+ * unview_op is the inverse, unview_op(view_op(x)) == x.  The eight ops are the dihedral group of the square, so the inverse
+ * of an op is an op:  unview_op == view_op'  with  op' = op  for op in {0, 1, 2, 3, 4, 7}  (the mirrors, the half turn and
+ * the two diagonal reflections are involutions),  5' = 6  and  6' = 5  (the two quarter turns).  As numpy says it, on one
+ * (T, T, E) tile: op 3 is np.rot90(x, 2), op 5 is np.rot90(x, -1) (clockwise), op 6 is np.rot90(x, 1) (counter-clockwise), op 4 is
+ * x.transpose(1, 0, 2), op 7 the transpose about the other diagonal.
+ *
+ * SETS.  tta = None: ops (0);  'flips': ops (0, 1, 2, 3), ImageFlip's four states;  'dihedral': ops (0 .. 7).  Only these,
+ * so n is 1, 4 or 8: the mean is an exact scaling and the argmax of the sum is the argmax of the mean.
+ *
+ * MERGE.  With L_op = net.build(view_op(tiles)):
+ *     acc = unview_0(L_0)
+ *     acc = acc + unview_op(L_op)        for op ascending, one float32 add per element per op
+ * in that order: deterministic, run-to-run identical.  mean = acc * (1/n) is exact.
+ *
+ * MASK.  Frame pixel (y, x) takes its owner tile and local coordinate from ymap / xmap (sq_stitch_masks_u8's maps,
+ * unchanged: one owner per pixel, no seam blending).  Its class pc is the one sq_argmax_u8's loop writes for the K values
+ * of acc:  best = 0;  for c = 1 .. K-1: if (acc[c] > acc[best]) best = c  -- ties go to the lowest class, NaN never wins,
+ * a row that starts with NaN gives class 0.  With n = 1 the mask is sq_stitch_masks_u8 of sq_argmax_u8, byte for byte.
+ *
+ * PROBABILITIES.  From the same K values, in float32, contraction off:
+ *     l_k = acc_k * inv_n                 inv_n = 1/n
+ *     m   = l_pc
+ *     e_k = expf(l_k - m)                 full-precision expf
+ *     s   = e_0 + ... + e_{K-1}           in index order, starting from 0
+ *     p_k = e_k / s
+ * A row whose m is not finite, or that holds a NaN, gives NaN in every class.  Output is planar (F, K, H, W): SQ_PIX_F32
+ * writes p_k, SQ_PIX_U8 writes (uint8) floorf(p_k * 255 + 0.5f) and 0 for NaN.  With K == 1, p = 1 where the logit is
+ * finite.  Against the float64 softmax every finite p_k is within (K + 4) * 2^-23: one rounding in l - m costs at most
+ * 2^-24 d e^-d <= 2^-24 / e in e_k, expf, the K - 1 adds and the divide about an ulp each on values <= 1, doubled.
+ *
+ *   sq_tiles_view_f32 : dst = view_op(src), or unview_op(src) when inverse != 0; dst += ... when accumulate != 0 (every
+ *                       element read, changed and written by exactly one thread).  Refused before any launch, dst
+ *                       untouched: a null pointer, src and dst the same or overlapping, op outside 0 .. 7, E outside
+ *                       1 .. 16, T outside 1 .. 65535, N < 1 or N * T > 2^31 - 1, pointers not 16-byte aligned
+ *                       (SQ_EALIGN).  Ops 0 .. 3 are row streams (16-byte accesses where E and T allow: E % 4 == 0, or
+ *                       T * E % 4 == 0 with no mirror of axis 2 or E <= 2).  Ops 4 .. 7 go through a padded LDS block of
+ *                       sq_tiles_view_block(E) pixels a side (32 for E <= 4, 16 above), so that loads and stores both run
+ *                       along rows; SQ_TTA_LDS=0 (read per call) gathers them directly instead, with the same bits.  The
+ *                       LDS form was made the default by design and has kept it by measurement: on an MI355X it is
+ *                       2.1 - 2.6 x the direct gather (tools/tta_bench.py, profiles/tta_bench.json; DESIGN.md "Test-time
+ *                       augmentation").  No allocation, no synchronisation: the same under graph capture.
+ *   sq_stitch_probs   : mask_out (F, H, W) uint8 and / or prob_out (F, K, H, W) of prob_dtype SQ_PIX_U8 or SQ_PIX_F32
+ *                       from tile_logits (F*TR*TC, TS, TS, K) = acc, as defined above.  Either output may be NULL, not
+ *                       both.  K is 1 .. 16, inv_n in (0, 1]; F * H <= 2^31 - 1; tile_logits 16-byte aligned.  The maps
+ *                       are trusted as sq_stitch_masks_u8 trusts them.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int sq_tiles_view_block(int E);
+int sq_tiles_view_f32(const float *src, float *dst, int N, int T, int E, int op, int inverse, int accumulate, void *stream);
+int sq_stitch_probs(const float *tile_logits, const int32_t *ymap, const int32_t *xmap, uint8_t *mask_out, void *prob_out,
+                    int prob_dtype, float inv_n, int F, int H, int W, int TR, int TC, int TS, int K, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame cleaning: the pipes the reference applies to raw microscope frames in front of ImageNorm, per whole frame,
  * in the order ImageOutliers -> ImageBlur -> ImageBGSubtract -> ImageNorm (sequitr_amd/frontend.py: FrameClean,
  * FrameTiler).

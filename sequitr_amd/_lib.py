@@ -78,6 +78,9 @@ SIGNATURES = {
     "sq_frames_to_tiles": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
     "sq_stitch_masks_u8": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "sq_frames_to_tiles_mc": (c_int, [c_void_p, c_int, c_int64] + [c_void_p] * 9 + [c_int] * 7 + [c_void_p]),
+    "sq_tiles_view_block": (c_int, [c_int]),
+    "sq_tiles_view_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "sq_stitch_probs": (c_int, [c_void_p] * 5 + [c_int, c_float] + [c_int] * 7 + [c_void_p]),
     "sq_frame_outliers_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "sq_frame_blur_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sq_frame_bgfit_workspace": (c_int64, [c_int, c_int, c_int]),

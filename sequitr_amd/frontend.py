@@ -14,6 +14,12 @@ pipeline.py:244-263) and ImageBGSubtract (uneven illumination, pipeline.py:360-4
 before tiling (FrameClean, FrameTiler.outliers / blur / background / tiles(clean=), segment_frames(clean=);
 include/sequitr_hip.h "Frame cleaning").
 
+Behind the network the frame path can keep the float32 logits: FrameTiler.view applies the eight symmetries of the square
+to a tile batch (and undoes them, accumulating), so that segment_frames(tta='flips' | 'dihedral') averages the network's
+logits over the flip states of the reference's ImageFlip or over all eight, and FrameTiler.stitch_probs writes the mask of
+the merged logits and their softmax as whole frames in one launch (segment_frames(probabilities=); include/sequitr_hip.h
+"Tile views and probability stitch").
+
 Volumes take the same path in three dimensions (VolumeTiler, segment_volumes): a brick is a box of the network's
 input shape, the rule above holds along each axis, and an axis shorter than the brick is padded with the
 normalised mean, 0.
@@ -564,6 +570,80 @@ class FrameTiler(object):
                                           torch.cuda.current_stream().cuda_stream), 'sq_stitch_masks_u8')
         return out
 
+    def view(self, tiles, op, inverse=False, out=None, accumulate=False):
+        """view_op (or, with `inverse`, unview_op) of every tile of a contiguous (N, T, T, E) float32 batch in GPU memory,
+        E = 1 .. 16 input channels or class logits: op bit 0 mirrors axis 1, bit 1 mirrors axis 2, bit 2 transposes the
+        two (include/sequitr_hip.h "Tile views and probability stitch").  The result goes to `out` (a new tensor when
+        None; never `tiles` itself); with `accumulate` it is added to `out` instead, one float32 add per element."""
+        if not isinstance(tiles, torch.Tensor) or not tiles.is_cuda:
+            raise _lib.SequitrHipError('tiles must be a tensor in GPU memory (no CPU fallback exists)')
+        if tiles.dtype != torch.float32 or tiles.dim() != 4 or not tiles.is_contiguous() or tiles.shape[0] < 1:
+            raise ValueError('tiles must be a contiguous (N,T,T,E) float32 tensor, got %s %s' % (tiles.dtype, tuple(tiles.shape)))
+        N, T, T2, E = (int(s) for s in tiles.shape)
+        if T != T2:                                             # any square size: the geometry of the frames plays no part
+            raise ValueError('tiles %s are not square' % (tuple(tiles.shape),))
+        if isinstance(op, bool) or int(op) != op or not 0 <= int(op) <= 7:
+            raise ValueError('op must be 0 .. 7, got %r' % (op,))
+        if out is None:
+            if accumulate:
+                raise ValueError('accumulate adds to `out`: give it')
+            out = torch.empty_like(tiles)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.shape == tiles.shape):
+            raise ValueError('out must be a contiguous float32 tensor of shape %s in GPU memory' % (tuple(tiles.shape),))
+        _lib.check(_lib.load().sq_tiles_view_f32(tiles.data_ptr(), out.data_ptr(), N, T, E, int(op), int(bool(inverse)),
+                                                 int(bool(accumulate)), torch.cuda.current_stream().cuda_stream),
+                   'sq_tiles_view_f32')
+        return out
+
+    def stitch_probs(self, tile_logits, n=1, mask=True, probabilities=None):
+        """(F*TR*TC, T, T, K) float32 tile logits -- one pass, or the merged sum of n = 4 or 8 views -- to whole frames in
+        one launch: returns (mask or None, probs or None), the (F, H, W) uint8 class mask (sq_argmax_u8's rule on the
+        owner tile's logits) and the (F, K, H, W) softmax of logits / n as `probabilities` = 'uint8' (rounded p * 255) or
+        'float32' (include/sequitr_hip.h "Tile views and probability stitch")."""
+        if not isinstance(tile_logits, torch.Tensor) or not tile_logits.is_cuda:
+            raise _lib.SequitrHipError('tile_logits must be a tensor in GPU memory (no CPU fallback exists)')
+        if tile_logits.dtype != torch.float32 or tile_logits.dim() != 4 or not tile_logits.is_contiguous():
+            raise ValueError('tile_logits must be a contiguous (N,T,T,K) float32 tensor')
+        nt, K = int(tile_logits.shape[0]), int(tile_logits.shape[3])
+        if nt < 1 or nt % self.tiles_per_frame or tuple(tile_logits.shape[1:3]) != (self.T, self.T):
+            raise ValueError('tile_logits %s do not match %d tiles of %d per frame' % (tuple(tile_logits.shape), nt, self.T))
+        if not 1 <= K <= 16:
+            raise ValueError('%d classes are not 1 .. 16' % K)
+        if n not in (1, 4, 8):
+            raise ValueError('n must be 1, 4 or 8 (the sizes of the view sets), got %r' % (n,))
+        dtype = check_probabilities(probabilities)
+        if not mask and dtype is None:
+            raise ValueError('nothing to compute: mask is off and probabilities is None')
+        F = nt // self.tiles_per_frame
+        m = torch.empty((F, self.H, self.W), dtype=torch.uint8, device=self.device) if mask else None
+        p = torch.empty((F, K, self.H, self.W), dtype=dtype, device=self.device) if dtype is not None else None
+        _lib.check(_lib.load().sq_stitch_probs(tile_logits.data_ptr(), self._ymap.data_ptr(), self._xmap.data_ptr(),
+                                               m.data_ptr() if mask else None, p.data_ptr() if p is not None else None,
+                                               PIX[dtype] if p is not None else 0, 1.0 / n, F, self.H, self.W, self.TR,
+                                               self.TC, self.T, K, torch.cuda.current_stream().cuda_stream), 'sq_stitch_probs')
+        return m, p
+
+
+TTA_OPS = {None: (0,), 'flips': (0, 1, 2, 3), 'dihedral': (0, 1, 2, 3, 4, 5, 6, 7)}
+PROBABILITIES = {'uint8': torch.uint8, 'float32': torch.float32}
+
+
+def check_tta(tta):
+    """the ops of a view set: None (one plain pass), 'flips' (ImageFlip's four states) or 'dihedral' (all eight)"""
+    if tta is not None and not isinstance(tta, str) or tta not in TTA_OPS:
+        raise ValueError("tta must be None, 'flips' or 'dihedral', got %r" % (tta,))
+    return TTA_OPS[tta]
+
+
+def check_probabilities(probabilities):
+    """the torch dtype of a probability map: None for None, else 'uint8' or 'float32'"""
+    if probabilities is None:
+        return None
+    if not isinstance(probabilities, str) or probabilities not in PROBABILITIES:
+        raise ValueError("probabilities must be None, 'uint8' or 'float32', got %r" % (probabilities,))
+    return PROBABILITIES[probabilities]
+
 
 _PINNED = {}
 
@@ -615,7 +695,7 @@ def open_channels(frames):
 
 
 def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None,
-                   on_batch=None, postprocess=None):
+                   on_batch=None, postprocess=None, tta=None, probabilities=None, on_probs=None):
     """Segment a stack of raw frames (numpy array / memmap / OctopusData, (F,H,W) uint8|uint16|float32).
     Raw frames are staged through two pinned buffers and uploaded on a side stream while the previous batch is
     normalised, tiled, segmented (net.predict) and stitched; returns the (F,H,W) uint8 masks (host), or
@@ -635,9 +715,30 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     `postprocess` (a maskops.MaskCleanup, or the step list one is made of) cleans every batch's stitched masks in HBM with
     net.n_outputs classes; its result takes the stitched batch's place before on_masks / on_batch and before the
     double-buffered download.  A bad step list raises before a frame is read.  The steps are maskops.MaskCleanup's:
-    morphology, fill_holes, split (touching objects cut apart), clear_border."""
+    morphology, fill_holes, split (touching objects cut apart), clear_border.
+
+    `tta` ('flips' or 'dihedral') is test-time augmentation: every batch of tiles goes through the network once per
+    symmetry of the set -- the four flip states of the reference's ImageFlip, or all eight symmetries of the square --
+    and the float32 logits are brought back (FrameTiler.view) and summed in op order in one buffer allocated once per
+    call; the mask is the argmax of the sum (include/sequitr_hip.h "Tile views and probability stitch").  It costs 4 or
+    8 network passes and changes nothing downstream: `postprocess` and every sink see the merged mask.
+    `probabilities` ('uint8' or 'float32') also returns the softmax of the (mean) logits stitched to whole frames, planar
+    (F,K,H,W), 'uint8' as rounded p * 255: the function then returns (masks, probs), both host arrays.  With a sink
+    (on_masks / on_batch), on_probs(first_frame, probs) is called with the batch's device tensor just before it (valid
+    until the callback returns) and is required; on_probs without `probabilities`, or without a mask sink, raises.
+    `postprocess` changes the masks only: the probabilities are the network's own.  With both keys None the function
+    runs what it always ran (net.predict, then stitch).  A bad value raises before a frame is read."""
     if on_masks is not None and on_batch is not None:
         raise ValueError('on_masks and on_batch are two forms of the same sink: pass one of them')
+    view_ops, prob_dtype = check_tta(tta), check_probabilities(probabilities)
+    if on_probs is not None and prob_dtype is None:
+        raise ValueError("on_probs receives the probabilities: it needs probabilities='uint8' or 'float32'")
+    if (on_probs is not None) != (prob_dtype is not None and (on_masks is not None or on_batch is not None)):
+        raise ValueError('on_probs goes with on_masks / on_batch: with a mask sink the probabilities need on_probs, '
+                         'without one both come back as host arrays')
+    merged = len(view_ops) > 1 or prob_dtype is not None       # else: exactly the code of before, predict + stitch
+    if merged and not 1 <= int(net.n_outputs) <= 16:
+        raise ValueError('tta / probabilities take 1 .. 16 classes, the network has %d' % int(net.n_outputs))
     if postprocess is not None:
         from .maskops import MaskCleanup
         if not isinstance(postprocess, MaskCleanup):
@@ -663,6 +764,22 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     ready = [torch.cuda.Event(), torch.cuda.Event()]            # upload of buffer i finished
     freed = [torch.cuda.Event(), torch.cuda.Event()]            # compute no longer reads staged[i]
     out = None if on_masks is not None or on_batch is not None else np.empty((F, H, W), np.uint8)
+    K = int(net.n_outputs)
+    out_probs = np.empty((F, K, H, W), probabilities) if out is not None and prob_dtype is not None else None
+    acc = views = None                                          # the merge buffer and the viewed tiles: once per call
+    if len(view_ops) > 1:
+        acc = torch.empty((B * tiler.tiles_per_frame, tiler.T, tiler.T, K), dtype=torch.float32, device=dev)
+        views = torch.empty((B * tiler.tiles_per_frame, tiler.T, tiler.T, C), dtype=torch.float32, device=dev)
+
+    def merged_logits(tiles):
+        """the batch's logits where the network left them (one pass), or the op-ordered sum over the view set in acc"""
+        if acc is None:
+            return net.build(tiles)
+        nt = tiles.shape[0]
+        for op in view_ops:
+            logits = net.build(tiles if op == 0 else tiler.view(tiles, op, out=views[:nt]))
+            tiler.view(logits, op, inverse=True, out=acc[:nt], accumulate=op != 0)
+        return acc[:nt]
 
     def upload(k, first):
         n = min(B, F - first)
@@ -686,11 +803,14 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     host_masks = [_pinned('out%d' % i, (B, H, W), torch.uint8) for i in range(2)] if out is not None else None
     done = [torch.cuda.Event(), torch.cuda.Event()]             # masks of batch parity k are in host_masks[k]
     pending = None                                              # (batch index, n) whose masks are still in flight
+    host_probs = ([_pinned('probs%d' % i, (B, K, H, W), prob_dtype) for i in range(2)] if out_probs is not None else None)
 
     def drain(p):
         pb, pn = p
         done[pb & 1].synchronize()
         out[pb * B:pb * B + pn] = host_masks[pb & 1][:pn].numpy()
+        if out_probs is not None:
+            out_probs[pb * B:pb * B + pn] = host_probs[pb & 1][:pn].numpy()
 
     for b in range(nb):
         k = b & 1
@@ -703,9 +823,14 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         tiles = tiler.tiles(raw, normalise=normalise, clean=clean, scratch=scratch)
         if on_batch is None:
             freed[k].record(cur)                               # after the last kernel that reads staged[k]
-        masks = tiler.stitch(net.predict(tiles))
+        if merged:
+            masks, probs = tiler.stitch_probs(merged_logits(tiles), n=len(view_ops), probabilities=probabilities)
+        else:
+            masks, probs = tiler.stitch(net.predict(tiles)), None
         if postprocess is not None:
             masks = postprocess.apply(masks, int(net.n_outputs))
+        if on_probs is not None:
+            on_probs(b * B, probs)
         if on_batch is not None:
             on_batch(b * B, raw, masks)
             freed[k].record(cur)                               # the callback's kernels read staged[k] too
@@ -714,6 +839,8 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
             on_masks(b * B, masks)
             continue
         host_masks[k][:n].copy_(masks, non_blocking=True)      # D2H queued behind this batch's kernels
+        if out_probs is not None:
+            host_probs[k][:n].copy_(probs, non_blocking=True)
         done[k].record(cur)
         if pending is not None:
             drain(pending)                                      # the previous batch's masks, while this one runs
@@ -721,7 +848,7 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     if pending is not None:
         drain(pending)
     torch.cuda.synchronize(dev)
-    return out
+    return out if out_probs is None else (out, out_probs)
 
 
 def volume_stats(vols):

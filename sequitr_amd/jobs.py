@@ -81,6 +81,7 @@ def SERVER_segment(params, options):
     staging buffers, one warm-up batch) and ``mpixels_per_s_with_setup`` the rate with it counted.
     """
     _refuse_volume_postprocess(params, 'SERVER_segment')
+    _refuse_tta(params, options, 'SERVER_segment (the tile job)')
     import torch
     from .networks.unet import UNet2D
     from .pipeline import ImagePipeline
@@ -398,6 +399,7 @@ def SERVER_segment_volume(params, options):
     if params.get('postprocess') is not None:
         raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope "
                          "(params['volume_postprocess'] cleans them)")
+    _refuse_tta(params, options, 'SERVER_segment_volume')
     cleanup = _parse_volume_postprocess(params)                 # before anything is opened
     analysis = _parse_volume_analysis(params, options)          # likewise
     import torch
@@ -534,6 +536,38 @@ def _refuse_volume_postprocess(params, job):
                          "params['brick']: %s does not take it" % job)
 
 
+TTA_SETS = (None, 'flips', 'dihedral')
+
+
+def _parse_tta(params, options, job):
+    """(tta, probabilities) of a whole-frame job: params['tta'] -- null, "flips" or "dihedral" (frontend.segment_frames'
+    view sets) -- and options['save_probabilities'] -- true ('uint8'), 'uint8' or 'float32'; false / null: none.  Volumes
+    (params['brick']) take neither; a bad value raises here, before anything is opened."""
+    tta = params.get('tta')
+    if tta is not None and not (isinstance(tta, str) and tta in TTA_SETS):
+        raise ValueError("params['tta'] must be null, \"flips\" or \"dihedral\", got %r" % (tta,))
+    save = options.get('save_probabilities')
+    if save is None or save is False:
+        probabilities = None
+    elif save is True:
+        probabilities = 'uint8'
+    elif isinstance(save, str) and save in ('uint8', 'float32'):
+        probabilities = save
+    else:
+        raise ValueError("options['save_probabilities'] must be true, false, 'uint8' or 'float32', got %r" % (save,))
+    if (tta is not None or probabilities is not None) and params.get('brick') is not None:
+        raise ValueError("params['tta'] / options['save_probabilities'] cover whole frames only: %s with params['brick'] "
+                         "segments volumes, and test-time augmentation for UNet3D is not built" % job)
+    return tta, probabilities
+
+
+def _refuse_tta(params, options, job):
+    """jobs that do not segment whole frames take neither params['tta'] nor options['save_probabilities']"""
+    if params.get('tta') is not None or options.get('save_probabilities'):
+        raise ValueError("params['tta'] / options['save_probabilities'] belong to the whole-frame jobs (SERVER_segment_frames, "
+                         "SERVER_evaluate on frames): %s does not take them" % job)
+
+
 def _channel_setup(params, C, parsed=None):
     """What the frame jobs derive from params once the number of channels is known, before a pixel is read:
     (clean, normalise, pipeline record or None, num_inputs or None).  params['pipeline'] (`parsed`: what _parse_pipelines
@@ -624,8 +658,20 @@ def SERVER_segment_frames(params, options):
     exposed faces, boundary pixels, perimeter counts) and the columns derived from them (covariance, axis_lengths,
     eccentricity, orientation, equivalent_diameter, extent, perimeter, crack_perimeter, circularity; ObjectTable's
     docstrings are the formulas) to ``objects.npz``, for the cleaned mask behind `postprocess` and the size filter, as
-    `measure` does; segment.json's ``objects`` record gains ``shape: true``.  Without the option every file is what it was."""
+    `measure` does; segment.json's ``objects`` record gains ``shape: true``.  Without the option every file is what it was.
+
+    params['tta'] (null, "flips" or "dihedral") is test-time augmentation (frontend.segment_frames: the network sees every
+    tile under the four flip states or all eight symmetries of the square and the logits are averaged in HBM; 4 or 8 network
+    passes).  Every sink sees the merged mask -- ``mask.npy``, the centroid file, `measure`, `shape`, `neighbors`, `link`,
+    the size filter and `postprocess`.  options['save_probabilities'] (true = 'uint8', or 'uint8' / 'float32') writes
+    ``probability.npy`` (F,K,H,W) next to ``mask.npy``: the softmax of the (mean) logits stitched to whole frames, uint8 as
+    rounded p * 255; `postprocess` and the size filter do not touch it.  segment.json records ``tta`` and ``probabilities``
+    with the defaults filled in, but only when the keys are present.  A bad value, or either key together with
+    params['brick'], raises before anything is opened; SERVER_segment (the tile job) and SERVER_segment_volume refuse both.
+    WORLD_SIZE plays no part in this job (every process segments the stack it was given), so the keys add nothing to refuse
+    there.  Without them every file is what it was."""
     _refuse_volume_postprocess(params, 'SERVER_segment_frames')
+    tta, probabilities = _parse_tta(params, options, 'SERVER_segment_frames')
     postprocess = _parse_postprocess(params)                    # before anything is opened
     want_neighbors = bool(options.get('neighbors'))
     want_link = bool(options.get('link'))
@@ -670,6 +716,7 @@ def SERVER_segment_frames(params, options):
     zone_stack = np.empty((F, H, W), np.int32) if want_neighbors and options.get('save_zones') else None
     num_classes = int(net_p.get('num_outputs', 2))
     track_stack = np.empty((F, H, W), np.int32) if want_link and options.get('save_track_labels') else None
+    prob_stack = np.empty((F, num_classes, H, W), probabilities) if probabilities and want_centroids else None
     kept_labels = []                                            # with save_track_labels: the batches' label frames, in HBM
 
     def sink(first, m):                                       # centroids need the masks while they are in HBM
@@ -678,6 +725,9 @@ def SERVER_segment_frames(params, options):
         for k, coords in enumerate(mask_centroids(m)):
             coords[:, 0] = first + k
             per_frame[first + k] = coords
+
+    def prob_sink(first, p):                                   # with a mask sink the probabilities are visited too
+        prob_stack[first:first + p.shape[0]] = p.cpu().numpy()
 
     def measure_sink(first, raw, m):                           # objects against the raw frames, both still in HBM
         from .objects import measure_objects
@@ -709,14 +759,23 @@ def SERVER_segment_frames(params, options):
                          frames_per_batch=int(params.get('frames_per_batch', 4)),
                          on_masks=sink if want_centroids and not want_measure else None,
                          on_batch=measure_sink if want_measure else None, normalise=normalise, clean=clean,
-                         postprocess=postprocess)
+                         postprocess=postprocess, tta=tta, probabilities=probabilities,
+                         on_probs=prob_sink if prob_stack is not None else None)
+    if probabilities is not None and not want_centroids:
+        out, prob_stack = out
     if not want_centroids:
         masks = out
     torch.cuda.synchronize()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'mask.npy'), masks)
+    if probabilities is not None:
+        np.save(os.path.join(out_dir, 'probability.npy'), prob_stack)
     info = {'frames': int(F), 'shape': [int(H), int(W)], 'tile': tile, 'seconds': dt,
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
+    if 'tta' in params:
+        info['tta'] = tta
+    if 'save_probabilities' in options:
+        info['probabilities'] = probabilities
     if C_in is not None:
         info['channels'] = C_in
         if want_measure:
@@ -913,8 +972,16 @@ def SERVER_evaluate(params, options):
     scores and ``mask.npy`` describe the cleaned masks and evaluate.json records the steps under 'postprocess'.  It covers
     frames only: together with params['brick'] it is refused.  params['volume_postprocess'] (as SERVER_segment_volume takes
     it) does the same for volumes: it needs params['brick'] and is refused without it; evaluate.json records the steps
-    under 'volume_postprocess'."""
-    postprocess = _parse_postprocess(params)                    # before anything is opened
+    under 'volume_postprocess'.
+
+    params['tta'] (null, "flips" or "dihedral", as SERVER_segment_frames takes it) scores the test-time-augmented masks --
+    the way to see whether the 4 or 8 network passes pay on a data set; evaluate.json records ``tta`` when the key is
+    present.  Frames only: with params['brick'] it is refused, and so is options['save_probabilities'], before anything is
+    opened."""
+    if options.get('save_probabilities'):
+        raise ValueError("options['save_probabilities'] belongs to SERVER_segment_frames: SERVER_evaluate writes scores")
+    tta, _ = _parse_tta(params, {}, 'SERVER_evaluate')          # before anything is opened
+    postprocess = _parse_postprocess(params)
     cleanup = _parse_volume_postprocess(params)
     if params.get('brick') is not None:
         return _evaluate_volume_bricks(params, options, cleanup)
@@ -954,7 +1021,7 @@ def SERVER_evaluate(params, options):
 
     t0 = time.time()
     segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)), frames_per_batch=B, on_masks=sink,
-                   normalise=normalise, clean=clean, postprocess=postprocess)
+                   normalise=normalise, clean=clean, postprocess=postprocess, tta=tta)
     counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
@@ -962,6 +1029,8 @@ def SERVER_evaluate(params, options):
         np.save(os.path.join(out_dir, 'mask.npy'), masks)
     info = {'frames': F, 'shape': [H, W], 'tile': tile, 'num_classes': C, 'seconds': dt,
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
+    if 'tta' in params:
+        info['tta'] = tta
     if C_in is not None:
         info['channels'] = C_in
     if pipe_record is not None:
