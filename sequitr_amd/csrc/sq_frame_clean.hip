@@ -222,8 +222,13 @@ __global__ __launch_bounds__(256) void bg_resid_sums_kernel(const float *__restr
 }
 
 // mean = sum r / n;  std = sqrt(sum r^2 / n - mean^2), np.std's population definition.  The residual of a fit that
-// holds the constant has mean 0 up to rounding, and in fp64 the one-pass form loses nothing that float32 tiles can show
-// even for coefficients that fit nothing.
+// holds the constant has mean 0 up to rounding, so nothing cancels and the one-pass form is exact to fp64 rounding
+// (errors of 1e-13 on the tall frames of tests/frame_side_cases.py).  With coefficients that fit nothing the two terms
+// cancel: the variance is off by about 2^-53 mean^2 times the growth of the sums, the std by about 2^-54 (mean / std)^2
+// of itself.  Measured on a 96 x 80 frame at level 60000 with noise 1 under zero coefficients: 2.0e-7 relative, seven
+// float32 half-ulps; an fp64 emulation with pairwise sums gives 8e-7 at 2048 x 2048.  That is inside the surface's own
+// bound of 2^-32 max|x| (1.4e-5 there), which tests/test_gpu_frame_side_sweep.py holds, but it is not below what float32
+// tiles can show.
 __global__ void bg_stats_finish_kernel(const double *__restrict__ ws, double *__restrict__ mean, double *__restrict__ stdv,
                                        int F, double n, int nstrips) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;

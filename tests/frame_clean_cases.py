@@ -26,7 +26,7 @@ SIZES = (2, 3, 4, 5)
 def _hot_positions(H, W, rng):
     """corners, the middle of each edge, a horizontal and a vertical pair, and about 1 % of the pixels at random"""
     pos = {(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (0, W // 2), (H - 1, W // 2), (H // 2, 0), (H // 2, W - 1),
-           (H // 3, W // 3), (H // 3, W // 3 + 1), (2 * H // 3, W // 2), (2 * H // 3 + 1, W // 2)}
+           (H // 3, W // 3), (H // 3, W // 3 + 1), (2 * H // 3, W // 2), (min(2 * H // 3 + 1, H - 1), W // 2)}    # min: frames of 2 or 3 rows
     n = (H * W) // 100
     pos |= set(zip(rng.integers(0, H, n).tolist(), rng.integers(0, W, n).tolist()))
     ys, xs = zip(*sorted(pos))
@@ -37,8 +37,13 @@ def _hot_positions(H, W, rng):
 def frames(case):
     """the frames of CASES[case]: a smooth quadratic ramp plus noise, hot pixels far above any threshold used; no NaN,
     no negative zero.  Frame 0 of the (2, 48, 40) float32 case is the golden file's img_in.  Read only."""
-    (F, H, W), dtype = CASES[case]
-    rng = np.random.default_rng(100 + case)
+    return make_frames(CASES[case][0], CASES[case][1], 100 + case)
+
+
+def make_frames(shape, dtype, seed):
+    """frames() for any (F, H, W), pixel type and seed (tests/frame_side_cases.py makes its own shapes with it)"""
+    F, H, W = shape
+    rng = np.random.default_rng(seed)
     v, u = np.mgrid[0:H, 0:W].astype(np.float64)
     s, t = u / max(W - 1, 1) - 0.5, v / max(H - 1, 1) - 0.5
     level, noise, hot = (60., 3., 150.) if dtype == np.uint8 else (1500., 12., 4000.)
