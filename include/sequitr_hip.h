@@ -1227,6 +1227,73 @@ int sq_volume_sample_onehot_u8(const uint8_t *labels, int C, const int32_t *plan
                                int BZ, int BX, int BY, int count, int allow_transpose, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Brick views and probability scatter: "Tile views and probability stitch" for volumes -- test-time augmentation and class
+ * probability maps for UNet3D on whole volumes (sequitr_amd/frontend.py: VolumeTiler.view, VolumeTiler.scatter_probs,
+ * segment_volumes(tta=, probabilities=)).  The volume sampler trains on exactly these symmetries; here a trained net is
+ * evaluated under them and its logits averaged, all in HBM.
+ *
+ * VIEWS.  A brick batch is (N, BZ, BX, BY, E) float32, contiguous, E interleaved elements per voxel, 1 <= E <= 16.  op is
+ * the sample plan's 4-bit symmetry, the bits and the meaning of "Volume sampler": bit 0 flips z, bit 1 flips x, bit 2
+ * flips y, bit 3 transposes x and y and needs BX == BY.  In numpy, per brick b of shape (BZ, BX, BY, E):
+ *
+ *     if op & 8: b = b.transpose(0, 2, 1, 3)
+ *     if op & 1: b = b[::-1];  if op & 2: b = b[:, ::-1];  if op & 4: b = b[:, :, ::-1]
+ *
+ * that is view_op(b)[z, x, y, e] = b[fz(z), a, b, e] with (a, b) = (fx(x), fy(y)), or (fy(y), fx(x)) under bit 3.
+ * unview_op is the inverse, and the inverse of an op is an op:  unview_op == view_op'  with
+ *
+ *     op   0  1  2  3  4  5  6  7  8  9 10 11 12 13 14 15
+ *     op'  0  1  2  3  4  5  6  7  8  9 12 13 10 11 14 15
+ *
+ * (the mirrors commute and are involutions; carried through the transpose the x and y mirrors change places, so bits 1
+ * and 2 swap under bit 3: 8, 9, 14, 15 are reflections about a diagonal or half turns with it, 10 <-> 12 and 11 <-> 13
+ * the quarter turns).  In a slice, op >> 1 names the element of the square's group that the planar section's op names,
+ * except that the planar op mirrors before it transposes: planar (bit 0, bit 1) are this section's (bit 2, bit 1) under
+ * the transpose and (bit 1, bit 2) without it.
+ *
+ * SETS.  tta = None: ops (0);  'flips': ops (0 .. 7), the three mirrors, any brick;  'dihedral': ops (0 .. 15), requires
+ * BX == BY.  So n is 1, 8 or 16, 1/n a power of two, the mean an exact scaling.
+ *
+ * MERGE.  With L_op = net.build(view_op(bricks)):
+ *     acc = unview_0(L_0)
+ *     acc = acc + unview_op(L_op)        for op ascending, one float32 add per element per op
+ * in that order: deterministic, run-to-run identical.  mean = acc * (1/n) is exact.
+ *
+ * MASK and PROBABILITIES.  The planar section's rules, word for word, on the K values acc holds for a voxel in its owner
+ * brick: the class is sq_argmax_u8's loop (ties to the lowest class, NaN never wins, a row that starts with NaN gives
+ * class 0); l_k = acc_k * inv_n, m = l_pc, e_k = expf(l_k - m), s = e_0 + ... + e_{K-1} in index order, p_k = e_k / s, in
+ * float32 with contraction off; a row whose m is not finite, or that holds a NaN, gives NaN in every class; SQ_PIX_U8
+ * writes (uint8) floorf(p_k * 255 + 0.5f) and 0 for NaN; every finite p_k is within (K + 4) * 2^-23 of the float64
+ * softmax.  The owner of a voxel comes from `geom` exactly as sq_bricks_scatter_* reads it ("Volume front end": the owned
+ * boxes of a volume partition it; no seam blending).  With n = 1 the mask is sq_bricks_scatter_u8 of sq_argmax_u8, byte
+ * for byte.  Probability output is planar per volume: (V, K, Z, X, Y).
+ *
+ *   sq_bricks_view_f32      : dst = view_op(src), or unview_op(src) when inverse != 0; dst += ... when accumulate != 0
+ *                             (every element read, changed and written by exactly one thread, once).  Refused before any
+ *                             launch, dst untouched: a null pointer, src and dst the same or overlapping, op outside
+ *                             0 .. 15, bit 3 with BX != BY, E outside 1 .. 16, a dimension < 1, BX or BY > 65535,
+ *                             N * BZ * BX > 2^31 - 1, pointers not 16-byte aligned (SQ_EALIGN).  It is sq_tiles_view_f32's
+ *                             kernel family on N * BZ slices with the slice remapped under bit 0 (sq_tiles_view_f32 is its
+ *                             BZ = 1, BX = BY case, instantiated with those fixed at compile time): ops 0 .. 7 are row streams, any BX, BY, with 16-byte accesses where E
+ *                             and BY allow (E % 4 == 0, or BY * E % 4 == 0 with no mirror of y or E <= 2), one float
+ *                             otherwise; ops 8 .. 15 go per slice through the padded LDS block of sq_tiles_view_block(E)
+ *                             pixels a side, and SQ_TTA_LDS=0 (read per call) gathers them directly instead, with the same
+ *                             bits.  No allocation, no synchronisation: the same under graph capture.
+ *   sq_bricks_scatter_probs : for bricks first .. first+count-1 with brick_logits (count, BZ, BX, BY, K) = acc, every voxel
+ *                             of each brick's owned box -- clamped into brick and volume, whatever the table says -- gets
+ *                             its class in mask_out (V, Z, X, Y) uint8 and / or its K probabilities in prob_out
+ *                             (V, K, Z, X, Y) of prob_dtype SQ_PIX_U8 or SQ_PIX_F32; nothing else is written, so batches
+ *                             may be scattered in any order.  Either output may be NULL, not both.  K is 1 .. 16, inv_n in
+ *                             (0, 1]; count <= 65535 and BZ <= 65535 (grid dimensions); brick_logits 16-byte aligned.
+ *                             Refused before any launch, outputs untouched.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+int sq_bricks_view_f32(const float *src, float *dst, int N, int BZ, int BX, int BY, int E, int op, int inverse,
+                       int accumulate, void *stream);
+int sq_bricks_scatter_probs(const float *brick_logits, const int32_t *geom, uint8_t *mask_out, void *prob_out,
+                            int prob_dtype, float inv_n, int V, int Z, int X, int Y, int KZ, int KX, int KY, int BZ, int BX,
+                            int BY, int K, int64_t first, int count, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tile sampler: the planar twin of the volume sampler, and the one interpolating op of the pipeline -- the reference's
  * tr_augment (sequitr/networks/unet.py:348-401: per element one random angle, image and weight map rotated bilinearly,
  * labels by nearest neighbour, 1 - rotate(ones, NEAREST) added to the weights, a random crop of the network's shape,

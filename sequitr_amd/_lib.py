@@ -92,6 +92,8 @@ SIGNATURES = {
     "sq_volume_to_bricks": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 10 + [c_int64, c_int, c_void_p]),
     "sq_bricks_scatter_u8": (c_int, [c_void_p] * 3 + [c_int] * 10 + [c_int64, c_int, c_void_p]),
     "sq_bricks_scatter_f32": (c_int, [c_void_p] * 3 + [c_int] * 11 + [c_int64, c_int, c_void_p]),
+    "sq_bricks_view_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
+    "sq_bricks_scatter_probs": (c_int, [c_void_p] * 4 + [c_int, c_float] + [c_int] * 11 + [c_int64, c_int, c_void_p]),
     "sq_volume_sample_f32": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "sq_volume_sample_copy": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "sq_volume_sample_onehot_u8": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),

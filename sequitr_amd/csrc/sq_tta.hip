@@ -19,8 +19,13 @@
 // sq_stitch_probs: one frame pixel per lane; its K logits are one contiguous run in the owner tile, read as vectors; the
 // argmax is sq_argmax_u8's loop, the softmax the header's expression with contraction off, and every class plane gets one
 // coalesced store per wave.
-#include "sq_common.h"
-#include <math.h>
+//
+// sq_bricks_view_f32 (include/sequitr_hip.h "Brick views and probability scatter") is the same kernel family: a brick
+// batch (N, BZ, BX, BY, E) is N * BZ slices of BX rows of BY pixels; bit 0 of its op remaps the slice (z mirrored inside
+// its brick), the other three bits are the in-plane op.  The row kernels take rectangular slices (BX != BY) for the
+// un-transposed ops.  sq_tiles_view_f32 is the BZ = 1, BX = BY = T call of the same templates with VOL off: one slice size and
+// no remap at compile time, because the run-time general form cost the planar merge 4 - 8 % (profiles/volume_tta_bench.json).
+#include "sq_probs.h"
 #include <stdlib.h>
 
 #pragma clang fp contract(off)
@@ -35,34 +40,43 @@ inline int view_pitch(int B, int E) { return B * E + (((E - B * E) % 32) + 32) %
 
 enum { ROWS_SCALAR = 0, ROWS_VEC_PIXEL = 1, ROWS_VEC_RUN = 2 };
 
-// source pixel (a, b) of destination pixel (i, j) under op
-__device__ __forceinline__ void view_source(int op, unsigned T, unsigned i, unsigned j, unsigned &a, unsigned &b) {
+// source pixel (a, b) of destination pixel (i, j) under the in-plane op; slices of TX rows of TY pixels, TX == TY under bit 2
+__device__ __forceinline__ void view_source(int op, unsigned TX, unsigned TY, unsigned i, unsigned j, unsigned &a, unsigned &b) {
     const unsigned p = (op & 4) ? j : i, q = (op & 4) ? i : j;
-    a = (op & 1) ? T - 1 - p : p;
-    b = (op & 2) ? T - 1 - q : q;
+    a = (op & 1) ? TX - 1 - p : p;
+    b = (op & 2) ? TY - 1 - q : q;
+}
+
+// source slice of destination slice n: z mirrored inside its brick of BZ slices when fz (wave-uniform branch)
+__device__ __forceinline__ unsigned view_slice(unsigned n, unsigned BZ, int fz) {
+    return fz ? n + BZ - 1 - 2 * (n % BZ) : n;
 }
 
 // A block takes chunks of 256 consecutive units of the flat destination; UR units make a destination row.
 //   ROWS_SCALAR    : a unit is one float, any op
 //   ROWS_VEC_PIXEL : a unit is 4 floats inside one pixel (E % 4 == 0), any op
-//   ROWS_VEC_RUN   : a unit is 4 floats of a row (T * E % 4 == 0), ops 0 .. 3 with E = 1 or 2 when bit 1 mirrors
-template <int MODE, bool ACC>
+//   ROWS_VEC_RUN   : a unit is 4 floats of a row (TY * E % 4 == 0), ops 0 .. 3 with E = 1 or 2 when bit 1 mirrors
+// VOL: brick slices -- TX x TY pixels, the source slice remapped under fz; without it the planar tile of the parent form,
+// TY == TX and no remap, so that sq_tiles_view_f32 keeps the instruction stream it was measured with.
+template <int MODE, bool ACC, bool VOL>
 __global__ __launch_bounds__(TTA_THREADS) void view_rows_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                                unsigned T, unsigned E, int op, unsigned UR, int64_t total) {
+                                                                unsigned TX, unsigned TYv, unsigned E, int op, unsigned BZ,
+                                                                int fz, unsigned UR, int64_t total) {
+    const unsigned TY = VOL ? TYv : TX;
     const int64_t nchunks = (total + TTA_THREADS - 1) / TTA_THREADS;
-    const size_t R = (size_t)T * E;
+    const size_t R = (size_t)TY * E;
     for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         const int64_t base = chunk * TTA_THREADS;
         if (base + threadIdx.x >= total) continue;
         const int64_t base_row = base / UR;                     // the one 64-bit division is the block's
         const unsigned l = (unsigned)(base - base_row * UR) + threadIdx.x;
-        const unsigned row = (unsigned)base_row + l / UR, u = l % UR;   // row < N * T < 2^31 (checked on the host)
-        const unsigned i = row % T, n = row / T;
+        const unsigned row = (unsigned)base_row + l / UR, u = l % UR;   // row < slices * TX < 2^31 (checked on the host)
+        const unsigned i = row % TX, n = VOL ? view_slice(row / TX, BZ, fz) : row / TX;
         if (MODE == ROWS_SCALAR) {
             const unsigned j = u / E, e = u % E;
             unsigned a, b;
-            view_source(op, T, i, j, a, b);
-            const float s = src[(((size_t)n * T + a) * T + b) * E + e];
+            view_source(op, TX, TY, i, j, a, b);
+            const float s = src[(((size_t)n * TX + a) * TY + b) * E + e];
             float *d = dst + (size_t)row * R + u;
             *d = ACC ? *d + s : s;
         } else {
@@ -71,12 +85,12 @@ __global__ __launch_bounds__(TTA_THREADS) void view_rows_kernel(const float *__r
             if (MODE == ROWS_VEC_PIXEL) {
                 const unsigned f = 4 * u, j = f / E, e = f % E;
                 unsigned a, b;
-                view_source(op, T, i, j, a, b);
-                from = (((size_t)n * T + a) * T + b) * E + e;
+                view_source(op, TX, TY, i, j, a, b);
+                from = (((size_t)n * TX + a) * TY + b) * E + e;
             } else {
-                const unsigned a = (op & 1) ? T - 1 - i : i;
+                const unsigned a = (op & 1) ? TX - 1 - i : i;
                 mirrored = (op & 2) != 0;
-                from = ((size_t)n * T + a) * R + (mirrored ? R - 4 - 4 * (size_t)u : 4 * (size_t)u);
+                from = ((size_t)n * TX + a) * R + (mirrored ? R - 4 - 4 * (size_t)u : 4 * (size_t)u);
             }
             f32x4 v = *reinterpret_cast<const f32x4 *>(src + from);
             if (MODE == ROWS_VEC_RUN && mirrored) {
@@ -93,12 +107,12 @@ __global__ __launch_bounds__(TTA_THREADS) void view_rows_kernel(const float *__r
     }
 }
 
-// Transposed ops: an item is the B x B pixel block (I0, J0) of destination tile n.  Eight half-waves: half-wave g takes
+// Transposed ops: an item is the B x B pixel block (I0, J0) of destination slice n (square slices of T x T pixels).  Eight half-waves: half-wave g takes
 // rows g, g + 8, ... of the block, its 32 lanes a run of floats.  ET: E at compile time, 0 = read E at run time.
-template <int ET, bool ACC>
+template <int ET, bool ACC, bool VOL>
 __global__ __launch_bounds__(TTA_THREADS) void view_tiles_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                                 unsigned T, unsigned Ert, int op, unsigned B, unsigned pitch,
-                                                                 unsigned nb, int64_t items) {
+                                                                 unsigned T, unsigned Ert, int op, unsigned BZ, int fz,
+                                                                 unsigned B, unsigned pitch, unsigned nb, int64_t items) {
     __shared__ float lds[VIEW_LDS_FLOATS];
     const unsigned E = ET ? (unsigned)ET : Ert;
     const unsigned g = threadIdx.x >> 5, lane = threadIdx.x & 31;
@@ -109,7 +123,7 @@ __global__ __launch_bounds__(TTA_THREADS) void view_tiles_kernel(const float *__
         // lds[jl][il][e] = src[n, a(J0 + jl), b(I0 + il), e]: lanes along il, e -- the source row
         for (unsigned jl = g; jl < nj; jl += 8) {
             const unsigned a = (op & 1) ? T - 1 - (J0 + jl) : J0 + jl;
-            const float *s = src + ((size_t)n * T + a) * T * E;
+            const float *s = src + ((size_t)(VOL ? view_slice(n, BZ, fz) : n) * T + a) * T * E;
             for (unsigned w = lane; w < ni * E; w += 32) {
                 const unsigned il = w / E, e = w - il * E;
                 const unsigned b = (op & 2) ? T - 1 - (I0 + il) : I0 + il;
@@ -137,45 +151,26 @@ inline bool tta_lds() {
     return !(e && e[0] == '0');
 }
 
-template <int MODE>
-void rows_launch(const float *src, float *dst, int T, int E, int op, unsigned UR, int64_t total, bool acc, hipStream_t st) {
+template <int MODE, bool VOL>
+void rows_launch(const float *src, float *dst, int TX, int TY, int E, int op, int BZ, int fz, unsigned UR, int64_t total, bool acc,
+                 hipStream_t st) {
     const dim3 grid(tta_grid((total + TTA_THREADS - 1) / TTA_THREADS)), block(TTA_THREADS);
-    if (acc) hipLaunchKernelGGL((view_rows_kernel<MODE, true>), grid, block, 0, st, src, dst, (unsigned)T, (unsigned)E, op, UR, total);
-    else hipLaunchKernelGGL((view_rows_kernel<MODE, false>), grid, block, 0, st, src, dst, (unsigned)T, (unsigned)E, op, UR, total);
+    if (acc)
+        hipLaunchKernelGGL((view_rows_kernel<MODE, true, VOL>), grid, block, 0, st, src, dst, (unsigned)TX, (unsigned)TY, (unsigned)E, op,
+                           (unsigned)BZ, fz, UR, total);
+    else
+        hipLaunchKernelGGL((view_rows_kernel<MODE, false, VOL>), grid, block, 0, st, src, dst, (unsigned)TX, (unsigned)TY, (unsigned)E, op,
+                           (unsigned)BZ, fz, UR, total);
 }
 
-template <int ET>
-void tiles_launch(const float *src, float *dst, int N, int T, int E, int op, bool acc, hipStream_t st) {
+template <int ET, bool VOL>
+void tiles_launch(const float *src, float *dst, int64_t N, int T, int E, int op, int BZ, int fz, bool acc, hipStream_t st) {
     const unsigned B = (unsigned)view_block(E), pitch = (unsigned)view_pitch((int)B, E), nb = ((unsigned)T + B - 1) / B;
-    const int64_t items = (int64_t)N * nb * nb;
+    const int64_t items = N * nb * nb;
     const dim3 grid(tta_grid(items)), block(TTA_THREADS);
-    if (acc) hipLaunchKernelGGL((view_tiles_kernel<ET, true>), grid, block, 0, st, src, dst, (unsigned)T, (unsigned)E, op, B, pitch, nb, items);
-    else hipLaunchKernelGGL((view_tiles_kernel<ET, false>), grid, block, 0, st, src, dst, (unsigned)T, (unsigned)E, op, B, pitch, nb, items);
+    if (acc) hipLaunchKernelGGL((view_tiles_kernel<ET, true, VOL>), grid, block, 0, st, src, dst, (unsigned)T, (unsigned)E, op, (unsigned)BZ, fz, B, pitch, nb, items);
+    else hipLaunchKernelGGL((view_tiles_kernel<ET, false, VOL>), grid, block, 0, st, src, dst, (unsigned)T, (unsigned)E, op, (unsigned)BZ, fz, B, pitch, nb, items);
 }
-
-// the K floats of one interleaved pixel at p, in the widest pieces K allows (sq_store_pixel's rule)
-template <int K>
-__device__ __forceinline__ void load_pixel(const float *__restrict__ p, float (&z)[K]) {
-    if constexpr (K % 4 == 0) {
-#pragma unroll
-        for (int q = 0; q < K; q += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(p + q);
-            z[q] = v.x; z[q + 1] = v.y; z[q + 2] = v.z; z[q + 3] = v.w;
-        }
-    } else if constexpr (K % 2 == 0) {
-#pragma unroll
-        for (int q = 0; q < K; q += 2) {
-            const float2 v = *reinterpret_cast<const float2 *>(p + q);
-            z[q] = v.x; z[q + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < K; ++q) z[q] = p[q];
-    }
-}
-
-__device__ __forceinline__ void store_prob(float *p, float v) { *p = v; }
-__device__ __forceinline__ void store_prob(uint8_t *p, float v) { *p = v != v ? (uint8_t)0 : (uint8_t)floorf(v * 255.0f + 0.5f); }
 
 // frame pixel (f, y, x) of the flat order, 256 consecutive pixels a chunk; P: float or uint8_t planes
 template <int K, typename P>
@@ -195,24 +190,11 @@ __global__ __launch_bounds__(TTA_THREADS) void stitch_probs_kernel(const float *
         const size_t t = ((size_t)f * TR + (unsigned)(ym >> 16)) * TC + (unsigned)(xm >> 16);
         float z[K];
         load_pixel<K>(logits + ((t * TS + (unsigned)(ym & 0xffff)) * TS + (unsigned)(xm & 0xffff)) * K, z);
-        float bv = z[0];
-        int best = 0;
-#pragma unroll
-        for (int c = 1; c < K; ++c)
-            if (z[c] > bv) { bv = z[c]; best = c; }
+        float bv;
+        const int best = pixel_class<K>(z, bv);
         if (mask) mask[base + threadIdx.x] = (uint8_t)best;
         if (prob) {
-            const float m = bv * inv_n;
-            bool bad = !(fabsf(m) < INFINITY);                  // NaN or +-inf
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < K; ++c) {
-                const float lc = z[c] * inv_n;
-                bad = bad || lc != lc;
-                z[c] = expf(lc - m);
-                s = s + z[c];
-            }
-            if (bad) s = NAN;                                   // e / NaN: NaN in every class
+            const float s = pixel_exps<K>(z, bv, inv_n);
             P *o = prob + ((size_t)f * K * H + y) * W + x;
             const size_t plane = (size_t)H * W;
 #pragma unroll
@@ -240,6 +222,33 @@ void stitch_launch(const float *logits, const int *ymap, const int *xmap, uint8_
 
 extern "C" int sq_tiles_view_block(int E) { return (E >= 1 && E <= 16) ? view_block(E) : -1; }
 
+// dst (+)= the in-plane op (bit 0 mirrors the rows, bit 1 the pixels of a row, bit 2 transposes) of every slice, the source
+// slice z-mirrored inside its brick of BZ when fz: what both entry points launch
+template <bool VOL>
+static int view_launch(const char *what, const float *src, float *dst, int64_t slices, int BZ, int TX, int TY, int E, int op, int fz,
+                       bool acc, hipStream_t st) {
+    if ((op & 4) && tta_lds()) {
+        switch (E) {
+        case 1: tiles_launch<1, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        case 2: tiles_launch<2, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        case 3: tiles_launch<3, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        case 4: tiles_launch<4, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        case 8: tiles_launch<8, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        case 16: tiles_launch<16, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        default: tiles_launch<0, VOL>(src, dst, slices, TX, E, op, BZ, fz, acc, st); break;
+        }
+        return sq_check_launch(what);
+    }
+    const int64_t R = (int64_t)TY * E, rows = slices * TX;
+    if (E % 4 == 0 && ((op & 4) || (op & 2)))
+        rows_launch<ROWS_VEC_PIXEL, VOL>(src, dst, TX, TY, E, op, BZ, fz, (unsigned)(R / 4), rows * (R / 4), acc, st);
+    else if (!(op & 4) && R % 4 == 0 && (!(op & 2) || E <= 2))
+        rows_launch<ROWS_VEC_RUN, VOL>(src, dst, TX, TY, E, op, BZ, fz, (unsigned)(R / 4), rows * (R / 4), acc, st);
+    else
+        rows_launch<ROWS_SCALAR, VOL>(src, dst, TX, TY, E, op, BZ, fz, (unsigned)R, rows * R, acc, st);
+    return sq_check_launch(what);
+}
+
 extern "C" int sq_tiles_view_f32(const float *src, float *dst, int N, int T, int E, int op, int inverse, int accumulate,
                                  void *stream) {
     const char *what = "sq_tiles_view_f32";
@@ -255,28 +264,33 @@ extern "C" int sq_tiles_view_f32(const float *src, float *dst, int N, int T, int
     SQ_REQUIRE_ALIGNED(dst);
     static const int inverse_op[8] = {0, 1, 2, 3, 4, 6, 5, 7};   // unview_op == view_op'
     if (inverse) op = inverse_op[op];
-    hipStream_t st = (hipStream_t)stream;
-    const bool acc = accumulate != 0;
-    if ((op & 4) && tta_lds()) {
-        switch (E) {
-        case 1: tiles_launch<1>(src, dst, N, T, E, op, acc, st); break;
-        case 2: tiles_launch<2>(src, dst, N, T, E, op, acc, st); break;
-        case 3: tiles_launch<3>(src, dst, N, T, E, op, acc, st); break;
-        case 4: tiles_launch<4>(src, dst, N, T, E, op, acc, st); break;
-        case 8: tiles_launch<8>(src, dst, N, T, E, op, acc, st); break;
-        case 16: tiles_launch<16>(src, dst, N, T, E, op, acc, st); break;
-        default: tiles_launch<0>(src, dst, N, T, E, op, acc, st); break;
-        }
-        return sq_check_launch(what);
-    }
-    const int64_t R = (int64_t)T * E, rows = (int64_t)N * T;
-    if (E % 4 == 0 && ((op & 4) || (op & 2)))
-        rows_launch<ROWS_VEC_PIXEL>(src, dst, T, E, op, (unsigned)(R / 4), rows * (R / 4), acc, st);
-    else if (!(op & 4) && R % 4 == 0 && (!(op & 2) || E <= 2))
-        rows_launch<ROWS_VEC_RUN>(src, dst, T, E, op, (unsigned)(R / 4), rows * (R / 4), acc, st);
-    else
-        rows_launch<ROWS_SCALAR>(src, dst, T, E, op, (unsigned)R, rows * R, acc, st);
-    return sq_check_launch(what);
+    return view_launch<false>(what, src, dst, N, 1, T, T, E, op, 0, accumulate != 0, (hipStream_t)stream);
+}
+
+extern "C" int sq_bricks_view_f32(const float *src, float *dst, int N, int BZ, int BX, int BY, int E, int op, int inverse,
+                                  int accumulate, void *stream) {
+    const char *what = "sq_bricks_view_f32";
+    SQ_REQUIRE(src && dst, "%s: null pointer", what);
+    SQ_REQUIRE(op >= 0 && op <= 15, "%s: op %d is not one of 0 .. 15", what, op);
+    SQ_REQUIRE(E >= 1 && E <= 16, "%s: %d elements per voxel are not 1 .. 16", what, E);
+    SQ_REQUIRE(N >= 1 && BZ >= 1 && BX >= 1 && BY >= 1, "%s: sizes must be positive", what);
+    SQ_REQUIRE(BX <= 65535 && BY <= 65535, "%s: brick rows %d x %d are not 1 .. 65535", what, BX, BY);
+    SQ_REQUIRE(!(op & 8) || BX == BY, "%s: op %d transposes x and y, the brick is %d x %d", what, op, BX, BY);
+    SQ_REQUIRE((int64_t)N * BZ * BX <= 0x7fffffff, "%s: %d bricks of %d x %d rows are out of range", what, N, BZ, BX);
+    const size_t bytes = (size_t)N * BZ * BX * BY * E * sizeof(float);
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    SQ_REQUIRE(s0 + bytes <= d0 || d0 + bytes <= s0, "%s: src and dst overlap (a view is not made in place)", what);
+    SQ_REQUIRE_ALIGNED(src);
+    SQ_REQUIRE_ALIGNED(dst);
+    // unview_op == view_op': under the transpose the x and y mirrors change places
+    static const int inverse_op[16] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 10, 11, 14, 15};
+    if (inverse) op = inverse_op[op];
+    // The brick op transposes first and mirrors the result (the volume sampler's order): dst[x, y] = src[fy(y), fx(x)].
+    // The in-plane op of the kernels mirrors first: dst[i, j] = src[f0(j), f1(i)].  So under the transpose f0 is the y
+    // mirror and f1 the x mirror; without it f0 mirrors x and f1 mirrors y.
+    const int fx = (op >> 1) & 1, fy = (op >> 2) & 1, t = (op >> 3) & 1;
+    const int plane_op = t ? (fy | fx << 1 | 4) : (fx | fy << 1);
+    return view_launch<true>(what, src, dst, (int64_t)N * BZ, BZ, BX, BY, E, plane_op, op & 1, accumulate != 0, (hipStream_t)stream);
 }
 
 extern "C" int sq_stitch_probs(const float *tile_logits, const int32_t *ymap, const int32_t *xmap, uint8_t *mask_out,

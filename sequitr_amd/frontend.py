@@ -872,6 +872,9 @@ def volume_stats(vols):
     return mean, std
 
 
+BRICKS_PER_LAUNCH = 65535                                       # a grid dimension of the brick kernels
+
+
 class VolumeTiler(object):
     """Geometry + device kernels for single-channel volumes of one (Z, X, Y) shape cut into network bricks
     (include/sequitr_hip.h "Volume front end").  brick / margin are in the array's (Z, X, Y) order."""
@@ -962,9 +965,92 @@ class VolumeTiler(object):
                                                     *(self._dims(V) + (first + lo, n, st))), 'sq_bricks_scatter_u8')
         return out
 
+    def view(self, bricks, op, inverse=False, out=None, accumulate=False):
+        """view_op (or, with `inverse`, unview_op) of every brick of a contiguous (N, BZ, BX, BY, E) float32 batch in GPU
+        memory, E = 1 .. 16 input channels or class logits: op is the sample plan's symmetry -- bit 0 flips z, bit 1 flips
+        x, bit 2 flips y, bit 3 transposes x and y and needs BX == BY (include/sequitr_hip.h "Brick views and probability
+        scatter").  Any brick shape: the tiler's geometry plays no part.  The result goes to `out` (a new tensor when None;
+        never `bricks` itself); with `accumulate` it is added to `out` instead, one float32 add per element."""
+        if not isinstance(bricks, torch.Tensor) or not bricks.is_cuda:
+            raise _lib.SequitrHipError('bricks must be a tensor in GPU memory (no CPU fallback exists)')
+        if bricks.dtype != torch.float32 or bricks.dim() != 5 or not bricks.is_contiguous() or bricks.shape[0] < 1:
+            raise ValueError('bricks must be a contiguous (N,BZ,BX,BY,E) float32 tensor, got %s %s'
+                             % (bricks.dtype, tuple(bricks.shape)))
+        N, BZ, BX, BY, E = (int(s) for s in bricks.shape)
+        if isinstance(op, bool) or int(op) != op or not 0 <= int(op) <= 15:
+            raise ValueError('op must be 0 .. 15, got %r' % (op,))
+        if int(op) & OP_TRANSPOSE and BX != BY:
+            raise ValueError('op %d transposes x and y: bricks %s are not square in (BX, BY)' % (op, tuple(bricks.shape)))
+        if out is None:
+            if accumulate:
+                raise ValueError('accumulate adds to `out`: give it')
+            out = torch.empty_like(bricks)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.shape == bricks.shape):
+            raise ValueError('out must be a contiguous float32 tensor of shape %s in GPU memory' % (tuple(bricks.shape),))
+        _lib.check(_lib.load().sq_bricks_view_f32(bricks.data_ptr(), out.data_ptr(), N, BZ, BX, BY, E, int(op),
+                                                  int(bool(inverse)), int(bool(accumulate)),
+                                                  torch.cuda.current_stream().cuda_stream), 'sq_bricks_view_f32')
+        return out
+
+    def scatter_probs(self, brick_logits, mask_out, prob_out, first=0, n=1):
+        """Bricks first .. first+len(brick_logits)-1 of (count, BZ, BX, BY, K) float32 logits -- one pass, or the merged sum
+        of n = 8 or 16 views -- into caller-owned full-volume tensors, in place: every owned voxel's class (sq_argmax_u8's
+        rule) into mask_out (V, Z, X, Y) uint8 and / or the softmax of logits / n into prob_out (V, K, Z, X, Y), uint8
+        (rounded p * 255) or float32 (include/sequitr_hip.h "Brick views and probability scatter").  Either output may
+        be None, not both.  Returns (mask_out, prob_out)."""
+        if not isinstance(brick_logits, torch.Tensor) or not brick_logits.is_cuda:
+            raise _lib.SequitrHipError('brick_logits must be a tensor in GPU memory (no CPU fallback exists)')
+        if brick_logits.dtype != torch.float32 or brick_logits.dim() != 5 or not brick_logits.is_contiguous():
+            raise ValueError('brick_logits must be a contiguous (N,BZ,BX,BY,K) float32 tensor')
+        count, K = int(brick_logits.shape[0]), int(brick_logits.shape[4])
+        if count < 1 or tuple(brick_logits.shape[1:4]) != self.brick:
+            raise ValueError('brick_logits %s are not bricks of %s' % (tuple(brick_logits.shape), self.brick))
+        if not 1 <= K <= 16:
+            raise ValueError('%d classes are not 1 .. 16' % K)
+        if n not in (1, 8, 16):
+            raise ValueError('n must be 1, 8 or 16 (the sizes of the view sets), got %r' % (n,))
+        if mask_out is None and prob_out is None:
+            raise ValueError('nothing to compute: mask_out and prob_out are both None')
+        for t, what in ((mask_out, 'mask_out'), (prob_out, 'prob_out')):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
+                raise ValueError('%s must be a contiguous tensor in GPU memory' % what)
+        V = int((mask_out if mask_out is not None else prob_out).shape[0])
+        if mask_out is not None and (mask_out.dtype != torch.uint8 or tuple(mask_out.shape) != (V,) + self.shape):
+            raise ValueError('mask_out must be uint8 %s, got %s %s' % ((V,) + self.shape, mask_out.dtype, tuple(mask_out.shape)))
+        if prob_out is not None and (prob_out.dtype not in PROBABILITIES.values()
+                                     or tuple(prob_out.shape) != (V, K) + self.shape):
+            raise ValueError('prob_out must be uint8 or float32 %s, got %s %s'
+                             % ((V, K) + self.shape, prob_out.dtype, tuple(prob_out.shape)))
+        first, count = self._range(V, first, count)
+        lib = _lib.load()
+        st = torch.cuda.current_stream().cuda_stream
+        for lo in range(0, count, BRICKS_PER_LAUNCH):
+            _lib.check(lib.sq_bricks_scatter_probs(brick_logits[lo:].data_ptr(), self._geom.data_ptr(),
+                                                   mask_out.data_ptr() if mask_out is not None else None,
+                                                   prob_out.data_ptr() if prob_out is not None else None,
+                                                   PIX[prob_out.dtype] if prob_out is not None else 0, 1.0 / n,
+                                                   *(self._dims(V) + (K, first + lo, min(BRICKS_PER_LAUNCH, count - lo), st))),
+                       'sq_bricks_scatter_probs')
+        return mask_out, prob_out
+
+
+OP_FLIP_Z, OP_FLIP_X, OP_FLIP_Y, OP_TRANSPOSE = 1, 2, 4, 8     # the symmetry bits of a sample plan's `op`
+VOLUME_TTA_OPS = {None: (0,), 'flips': tuple(range(8)), 'dihedral': tuple(range(16))}
+
+
+def check_volume_tta(tta, brick=None):
+    """the ops of a volume view set: None (one plain pass), 'flips' (the three mirrors: ops 0 .. 7) or 'dihedral' (with the
+    in-plane transpose: ops 0 .. 15), which a `brick` (BZ, BX, BY) that is given must allow (BX == BY)"""
+    if tta is not None and not isinstance(tta, str) or tta not in VOLUME_TTA_OPS:
+        raise ValueError("volume tta must be None, 'flips' or 'dihedral', got %r" % (tta,))
+    if tta == 'dihedral' and brick is not None and int(brick[1]) != int(brick[2]):
+        raise ValueError("volume tta 'dihedral' transposes x and y: brick %r is not square in (BX, BY)" % (tuple(brick),))
+    return VOLUME_TTA_OPS[tta]
+
 
 def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise=True, want_logits=False, on_masks=None,
-                    postprocess=None, on_volume=None):
+                    postprocess=None, on_volume=None, tta=None, probabilities=None, on_probs=None):
     """Segment whole volumes brick by brick: `volumes` is an (N, Z, X, Y) uint8 | uint16 | float32 numpy array or memmap,
     `net` a UNet3D built at the brick shape (brick and margin in the array's (Z, X, Y) order).  Raw volume i+1 goes
     through two pinned Z-slab buffers of bounded size and is uploaded on a side stream while volume i runs: statistics,
@@ -977,9 +1063,32 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     stitched mask on the compute stream with net.n_outputs classes before anything else sees it: the cleaned mask is
     what on_masks receives and what drains to the host.  Logits are not touched.  on_volume(i, raw, mask) is on_masks with
     the raw volume (1, Z, X, Y) as it was uploaded, still in HBM, next to the mask -- segment_frames' on_batch for volumes;
-    the upload of volume i+2 waits for what the sink has queued on the current stream.  Pass one of the two sinks."""
+    the upload of volume i+2 waits for what the sink has queued on the current stream.  Pass one of the two sinks.
+
+    `tta` ('flips' or 'dihedral') is test-time augmentation: every batch of bricks goes through the network once per
+    symmetry of the set -- the eight mirror states, or all 16 symmetries the volume sampler trains with, which need
+    BX == BY -- and the float32 logits are brought back (VolumeTiler.view) and summed in op order in one buffer allocated
+    once per call; the mask is the argmax of the sum (include/sequitr_hip.h "Brick views and probability scatter").  It
+    costs 8 or 16 network passes and changes nothing downstream: `postprocess` and every sink see the merged mask, and
+    the logits returned with want_logits are the mean over the views (the sum times 1/n, exact).
+    `probabilities` ('uint8' or 'float32') also scatters the softmax of the (mean) logits into whole volumes, planar
+    (N, K, Z, X, Y), 'uint8' as rounded p * 255: the function then returns (masks, logits, probs), probs a host array.
+    With a sink (on_masks / on_volume), on_probs(i, probs (1, K, Z, X, Y)) is called with the volume's device tensor just
+    before it (valid until volume i+2 is started) and is required; on_probs without `probabilities`, or without a mask
+    sink, raises.  `postprocess` changes the masks only: the probabilities are the network's own.  With both keys None the
+    function runs what it always ran (net.predict, then scatter).  A bad value raises before a voxel is read."""
     if on_masks is not None and on_volume is not None:
         raise ValueError('on_masks and on_volume are two forms of the same sink: pass one of them')
+    view_ops, prob_dtype = check_volume_tta(tta, brick), check_probabilities(probabilities)
+    sink = on_masks is not None or on_volume is not None
+    if on_probs is not None and prob_dtype is None:
+        raise ValueError("on_probs receives the probabilities: it needs probabilities='uint8' or 'float32'")
+    if (on_probs is not None) != (prob_dtype is not None and sink):
+        raise ValueError('on_probs goes with on_masks / on_volume: with a mask sink the probabilities need on_probs, '
+                         'without one they come back as a host array')
+    merged = len(view_ops) > 1 or prob_dtype is not None       # else: exactly the code of before, predict + scatter
+    if merged and not 1 <= int(net.n_outputs) <= 16:
+        raise ValueError('tta / probabilities take 1 .. 16 classes, the network has %d' % int(net.n_outputs))
     arr = volumes
     if postprocess is not None:
         from .volumeops import VolumeCleanup
@@ -1006,6 +1115,24 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     done = [torch.cuda.Event(), torch.cuda.Event()]             # mask_dev[k] / logits_dev[k] are complete
     out_masks = None if on_masks is not None or on_volume is not None else np.empty((N, Z, X, Y), np.uint8)
     out_logits = np.empty((N, Z, X, Y, n_out), np.float32) if want_logits else None
+    prob_dev = [torch.empty((1, n_out, Z, X, Y), dtype=prob_dtype, device=dev) for _ in range(2)] if prob_dtype is not None else None
+    out_probs = np.empty((N, n_out, Z, X, Y), probabilities) if prob_dtype is not None and not sink else None
+    acc = views = mean = None                                   # the merge buffers: once per call
+    if merged:
+        acc = torch.empty((B,) + tiler.brick + (n_out,), dtype=torch.float32, device=dev)
+        views = torch.empty((B,) + tiler.brick + (1,), dtype=torch.float32, device=dev)
+        if want_logits and len(view_ops) > 1:
+            mean = torch.empty_like(acc)
+    inv_n = 1.0 / len(view_ops)
+
+    def merged_logits(bricks):
+        """the op-ordered sum of the batch's logits over the view set, in acc"""
+        nt = bricks.shape[0]
+        for op in view_ops:
+            logits = net.build(bricks if op == 0 else tiler.view(bricks, op, out=views[:nt]))
+            tiler.view(logits, op, inverse=True, out=acc[:nt], accumulate=op != 0)
+        return acc[:nt]
+
     cur = torch.cuda.current_stream(dev)
     for e in slab_sent + freed:
         e.record(cur)
@@ -1032,6 +1159,8 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
                 torch.from_numpy(out_masks[i]).copy_(mask_dev[k][0])
             if out_logits is not None:
                 torch.from_numpy(out_logits[i]).copy_(logits_dev[k][0])
+            if out_probs is not None:
+                torch.from_numpy(out_probs[i]).copy_(prob_dev[k][0])
         out_stream.synchronize()
 
     if N:
@@ -1042,12 +1171,23 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
         stats = tiler.stats(staged[k]) if normalise else None
         for first in range(0, nb, B):
             bricks = tiler.bricks(staged[k], first, min(B, nb - first), normalise=normalise, stats=stats)
+            if merged:
+                logits = merged_logits(bricks)
+                tiler.scatter_probs(logits, mask_dev[k], prob_dev[k] if prob_dev is not None else None, first,
+                                    n=len(view_ops))
+                if want_logits:
+                    if mean is not None:
+                        logits = torch.mul(logits, inv_n, out=mean[:logits.shape[0]])
+                    tiler.scatter(logits, logits_dev[k], first)
+                continue
             masks = net.predict(bricks)
             tiler.scatter(masks, mask_dev[k], first)
             if want_logits:
                 tiler.scatter(net.logits(), logits_dev[k], first)
         if postprocess is not None:                             # the result lives in the cleaner's buffers: back into
             mask_dev[k].copy_(postprocess.apply(mask_dev[k], n_out))    # mask_dev[k], which stays valid until volume i+2
+        if on_probs is not None:
+            on_probs(i, prob_dev[k])
         if on_volume is not None:                               # the sink reads staged[k]: it is free once its work is queued
             on_volume(i, staged[k], mask_dev[k])
         freed[k].record(cur)
@@ -1061,10 +1201,7 @@ def segment_volumes(net, volumes, brick, margin=0, bricks_per_batch=8, normalise
     if N:
         drain(N - 1)
     torch.cuda.synchronize(dev)
-    return out_masks, out_logits
-
-
-OP_FLIP_Z, OP_FLIP_X, OP_FLIP_Y, OP_TRANSPOSE = 1, 2, 4, 8     # the symmetry bits of a sample plan's `op`
+    return (out_masks, out_logits) if prob_dtype is None else (out_masks, out_logits, out_probs)
 
 
 def sample_plan(vol_shape, brick, volumes, count, rng, augment=('flip', 'rot90')):

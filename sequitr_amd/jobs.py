@@ -81,6 +81,7 @@ def SERVER_segment(params, options):
     staging buffers, one warm-up batch) and ``mpixels_per_s_with_setup`` the rate with it counted.
     """
     _refuse_volume_postprocess(params, 'SERVER_segment')
+    _refuse_volume_tta(params, options, 'SERVER_segment')
     _refuse_tta(params, options, 'SERVER_segment (the tile job)')
     import torch
     from .networks.unet import UNet2D
@@ -243,11 +244,12 @@ def _parse_volume_analysis(params, options):
     return a
 
 
-def _segment_volume_bricks(params, options, cleanup=None, analysis=None):
+def _segment_volume_bricks(params, options, cleanup=None, analysis=None, volume_tta=(None, None)):
     """SERVER_segment_volume with params['brick']: volumes of any size, raw, brick by brick (frontend.segment_volumes)."""
     device, x, (bz, bx, by), margin, geometry = _brick_volumes(params, options)
     out_dir = params['output']
     N, Z, X, Y = (int(s) for s in x.shape)
+    tta, probabilities = volume_tta
 
     import torch
     from .networks.unet import UNet3D
@@ -304,18 +306,32 @@ def _segment_volume_bricks(params, options, cleanup=None, analysis=None):
         else:
             masks[i] = kept[0].cpu().numpy()
 
+    with_sink = bool(want_centroids or analysis)
+    prob_stack = np.empty((N, num_classes, Z, X, Y), probabilities) if probabilities and with_sink else None
+
+    def prob_sink(i, p):                                       # with a mask sink the probabilities are visited too
+        prob_stack[i] = p[0].cpu().numpy()
+
     t0 = time.time()
-    out, logits = segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch,
-                                  normalise=bool(params.get('normalise', True)), want_logits=want_logits,
-                                  on_masks=sink if want_centroids and not analysis else None,
-                                  **({'postprocess': cleanup} if cleanup else {}),
-                                  **({'on_volume': measure_sink} if analysis else {}))
-    if not (want_centroids or analysis):
+    res = segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch,
+                          normalise=bool(params.get('normalise', True)), want_logits=want_logits,
+                          on_masks=sink if want_centroids and not analysis else None,
+                          **({'postprocess': cleanup} if cleanup else {}),
+                          **({'on_volume': measure_sink} if analysis else {}),
+                          **({'tta': tta} if tta is not None else {}),
+                          **({'probabilities': probabilities,
+                              'on_probs': prob_sink if with_sink else None} if probabilities is not None else {}))
+    out, logits = res[0], res[1]
+    if probabilities is not None and not with_sink:
+        prob_stack = res[2]
+    if not with_sink:
         masks = out
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'mask.npy'), masks)
     if logits is not None:
         np.save(os.path.join(out_dir, 'logits.npy'), logits)
+    if probabilities is not None:
+        np.save(os.path.join(out_dir, 'probability.npy'), prob_stack)
     voxels = N * Z * X * Y
     info = {'volumes': int(N), 'shape': [Z, X, Y], 'seconds': dt, 'setup_seconds': t0 - t_setup,
             'mvoxels_per_s': float(voxels / max(dt, 1e-9) / 1e6), 'device': device,
@@ -323,6 +339,10 @@ def _segment_volume_bricks(params, options, cleanup=None, analysis=None):
             'bricks_per_volume': int(geometry.per_volume)}
     if cleanup is not None:
         info['volume_postprocess'] = cleanup.record()
+    if 'volume_tta' in params:
+        info['volume_tta'] = tta
+    if 'save_volume_probabilities' in options:
+        info['probabilities'] = probabilities
     if want_centroids:
         from .centroids import CentroidWriter
         with CentroidWriter(os.path.join(out_dir, 'tracks.hdf5')) as cw:
@@ -379,6 +399,16 @@ def SERVER_segment_volume(params, options):
     nothing changes.  The steps: 3-D morphology, fill_holes, split3d (touching cells cut apart; ``split`` is the planar
     step's name and is refused here), clear_border.  params['postprocess'], the planar list, stays refused.
 
+    With ``brick``, params['volume_tta'] (null, "flips" or "dihedral") is test-time augmentation (frontend.segment_volumes:
+    the network sees every batch of bricks under the 8 mirror states, or under all 16 symmetries the volume sampler trains
+    with -- "dihedral" needs a brick with X == Y -- and the float32 logits are merged in HBM); ``mask.npy`` is the argmax of
+    the merged logits, ``logits.npy`` (options['save_logits']) their mean, and the clean-up and the analysis see the merged
+    mask.  options['save_volume_probabilities'] (true = 'uint8', or 'uint8' / 'float32') writes ``probability.npy``
+    (N,K,Z,X,Y) next to ``mask.npy``: the softmax of the (mean) logits per voxel, uint8 as rounded p * 255; the clean-up
+    does not touch it.  ``segment_volume.json`` records ``volume_tta`` and ``probabilities`` when the keys are present.
+    Both keys are refused before anything is opened without ``brick``, on "dihedral" with a non-square brick and on bad
+    values; the planar params['tta'] / options['save_probabilities'] stay refused here.
+
     With ``brick``, options['measure'] measures every volume's objects in HBM (objects.measure_objects on the cleaned mask as
     it lies, D0, D1, D2 = Z, X, Y, 6-connected, against the RAW volume): ``objects.npz`` holds ObjectTable.columns() with
     ``frame`` the volume index, ``segment_volume.json`` an ``objects`` record, options['save_labels'] adds ``labels.npy``
@@ -400,13 +430,14 @@ def SERVER_segment_volume(params, options):
         raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope "
                          "(params['volume_postprocess'] cleans them)")
     _refuse_tta(params, options, 'SERVER_segment_volume')
-    cleanup = _parse_volume_postprocess(params)                 # before anything is opened
+    volume_tta = _parse_volume_tta(params, options, 'SERVER_segment_volume')    # before anything is opened
+    cleanup = _parse_volume_postprocess(params)                 # likewise
     analysis = _parse_volume_analysis(params, options)          # likewise
     import torch
     from .networks.unet import UNet3D
 
     if params.get('brick') is not None:
-        return _segment_volume_bricks(params, options, cleanup, analysis)
+        return _segment_volume_bricks(params, options, cleanup, analysis, volume_tta)
     device = _resolve_device(params, options)
     torch.cuda.set_device(torch.device(device))
     out_dir = params['output']
@@ -568,6 +599,46 @@ def _refuse_tta(params, options, job):
                          "SERVER_evaluate on frames): %s does not take them" % job)
 
 
+def _parse_volume_tta(params, options, job):
+    """(volume_tta, probabilities) of a brick job: params['volume_tta'] -- null, "flips" or "dihedral"
+    (frontend.segment_volumes' view sets: the 8 mirror states, or the 16 symmetries the volume sampler trains with, which
+    need a brick with X == Y) -- and options['save_volume_probabilities'] -- true ('uint8'), 'uint8' or 'float32'; false /
+    null: none.  Both need params['brick']; a bad value raises here, before anything is opened."""
+    tta = params.get('volume_tta')
+    if tta is not None and not (isinstance(tta, str) and tta in TTA_SETS):
+        raise ValueError("params['volume_tta'] must be null, \"flips\" or \"dihedral\", got %r" % (tta,))
+    save = options.get('save_volume_probabilities')
+    if save is None or save is False:
+        probabilities = None
+    elif save is True:
+        probabilities = 'uint8'
+    elif isinstance(save, str) and save in ('uint8', 'float32'):
+        probabilities = save
+    else:
+        raise ValueError("options['save_volume_probabilities'] must be true, false, 'uint8' or 'float32', got %r" % (save,))
+    if tta is None and probabilities is None:
+        return None, None
+    brick = params.get('brick')
+    if brick is None:
+        raise ValueError("params['volume_tta'] / options['save_volume_probabilities'] merge and scatter brick logits: %s "
+                         "takes them with params['brick'] only" % job)
+    if tta == 'dihedral':
+        if len(tuple(brick)) != 3:
+            raise ValueError("params['brick'] must be (X, Y, Z), got %r" % (brick,))
+        if int(brick[0]) != int(brick[1]):
+            raise ValueError("params['volume_tta'] \"dihedral\" transposes x and y: params['brick'] %r is not square in "
+                             "(X, Y)" % (tuple(brick),))
+    return tta, probabilities
+
+
+def _refuse_volume_tta(params, options, job):
+    """jobs that do not segment volumes brick by brick take neither params['volume_tta'] nor
+    options['save_volume_probabilities']"""
+    if params.get('volume_tta') is not None or options.get('save_volume_probabilities'):
+        raise ValueError("params['volume_tta'] / options['save_volume_probabilities'] belong to the brick jobs "
+                         "(SERVER_segment_volume and SERVER_evaluate with params['brick']): %s does not take them" % job)
+
+
 def _channel_setup(params, C, parsed=None):
     """What the frame jobs derive from params once the number of channels is known, before a pixel is read:
     (clean, normalise, pipeline record or None, num_inputs or None).  params['pipeline'] (`parsed`: what _parse_pipelines
@@ -671,6 +742,7 @@ def SERVER_segment_frames(params, options):
     WORLD_SIZE plays no part in this job (every process segments the stack it was given), so the keys add nothing to refuse
     there.  Without them every file is what it was."""
     _refuse_volume_postprocess(params, 'SERVER_segment_frames')
+    _refuse_volume_tta(params, options, 'SERVER_segment_frames')
     tta, probabilities = _parse_tta(params, options, 'SERVER_segment_frames')
     postprocess = _parse_postprocess(params)                    # before anything is opened
     want_neighbors = bool(options.get('neighbors'))
@@ -897,7 +969,7 @@ def _evaluation_record(counts, ignored):
             'per_frame': [dict(json_ready(scores(c)), ignored=int(g)) for c, g in zip(counts, ignored)]}
 
 
-def _evaluate_volume_bricks(params, options, cleanup=None):
+def _evaluate_volume_bricks(params, options, cleanup=None, tta=None):
     """SERVER_evaluate with params['brick']: volumes brick by brick, each stitched mask scored where segment_volumes
     leaves it (after params['volume_postprocess'], when given)"""
     labels = _load_labels(params.get('labels'))
@@ -933,7 +1005,7 @@ def _evaluate_volume_bricks(params, options, cleanup=None):
 
     t0 = time.time()
     segment_volumes(net, x, (bz, bx, by), margin, bricks_per_batch=batch, normalise=bool(params.get('normalise', True)),
-                    on_masks=sink, **({'postprocess': cleanup} if cleanup else {}))
+                    on_masks=sink, **({'postprocess': cleanup} if cleanup else {}), **({'tta': tta} if tta is not None else {}))
     counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
@@ -945,6 +1017,8 @@ def _evaluate_volume_bricks(params, options, cleanup=None):
             'bricks_per_volume': int(geometry.per_volume)}
     if cleanup is not None:
         info['volume_postprocess'] = cleanup.record()
+    if 'volume_tta' in params:
+        info['volume_tta'] = tta
     info.update(_evaluation_record(counts_h, ignored_h))
     with open(os.path.join(out_dir, 'evaluate.json'), 'w') as f:
         json.dump(info, f, indent=2)
@@ -977,15 +1051,20 @@ def SERVER_evaluate(params, options):
     params['tta'] (null, "flips" or "dihedral", as SERVER_segment_frames takes it) scores the test-time-augmented masks --
     the way to see whether the 4 or 8 network passes pay on a data set; evaluate.json records ``tta`` when the key is
     present.  Frames only: with params['brick'] it is refused, and so is options['save_probabilities'], before anything is
-    opened."""
+    opened.  With params['brick'], params['volume_tta'] (as SERVER_segment_volume takes it) scores the merged masks of the
+    8 or 16 views and evaluate.json records ``volume_tta``; options['save_volume_probabilities'] is refused."""
     if options.get('save_probabilities'):
         raise ValueError("options['save_probabilities'] belongs to SERVER_segment_frames: SERVER_evaluate writes scores")
     tta, _ = _parse_tta(params, {}, 'SERVER_evaluate')          # before anything is opened
     postprocess = _parse_postprocess(params)
     cleanup = _parse_volume_postprocess(params)
+    if options.get('save_volume_probabilities'):
+        raise ValueError("options['save_volume_probabilities'] belongs to SERVER_segment_volume: SERVER_evaluate writes scores")
     if params.get('brick') is not None:
-        return _evaluate_volume_bricks(params, options, cleanup)
+        volume_tta, _ = _parse_volume_tta(params, {}, 'SERVER_evaluate')
+        return _evaluate_volume_bricks(params, options, cleanup, volume_tta)
     _refuse_volume_postprocess(params, 'SERVER_evaluate without it')
+    _refuse_volume_tta(params, options, 'SERVER_evaluate without it')
     labels = _load_labels(params.get('labels'))
     frames, F, H, W, C_in = _open_channels(params)
     if tuple(labels.shape) != (F, H, W):
@@ -1411,6 +1490,7 @@ def SERVER_train(params, options):
     validation time out.  Single process only: with WORLD_SIZE > 1 the keys raise.
     """
     _refuse_volume_postprocess(params, 'SERVER_train')
+    _refuse_volume_tta(params, options, 'SERVER_train')
     if params.get('tile') is not None:
         return _train_frame_tiles(params, options)
     import torch
@@ -1672,6 +1752,7 @@ def SERVER_train_volume(params, options):
     with the same ``brick``.
     """
     _refuse_volume_postprocess(params, 'SERVER_train_volume')
+    _refuse_volume_tta(params, options, 'SERVER_train_volume')
     import torch
     from . import utils
     from .networks.unet import UNet3DTrain
@@ -1760,6 +1841,7 @@ def SERVER_train_gan(params, options):
     (and writes to ``train.json``) levels, sizes, steps, d_loss and g_loss of the last discriminator step, graph, dtype,
     crop, images, seconds, export_dir."""
     _refuse_volume_postprocess(params, 'SERVER_train_gan')
+    _refuse_volume_tta(params, options, 'SERVER_train_gan')
     import torch
     from .networks import gan
 
