@@ -348,6 +348,27 @@ int sq_conv2d_concat_nhwc_fwd_f32(const float *xa, const float *xb, const float 
 int sq_conv3x3_pool_fwd_f32(const float *x, const float *w, const float *bias, float *y, float *pooled,
                             int N, int H, int W, int Cin, int Cout, int act, void *stream);
 
+/* Fragment-order filter pack of an inference model's 3x3 layers on 64-channel blocks, made ONCE per model: a pure permutation
+ * of the stored (3,3,Cin,Cout) weights (bits in, bits out; no scaling, no rounding).  For each (64-channel output block cb,
+ * 16-channel chunk c, tap, 4-channel k-step s) it holds the 64 lanes' four A operands of one v_mfma_f32_16x16x4_f32 step as one
+ * float4 per lane:  wp[((((cb * Cin/16 + c) * 9 + tap) * 4 + s) * 64 + 16 kk + li) * 4 + nb]
+ *                   = w[tap][16 c + 4 s + kk][64 cb + 16 nb + li]        (li 0..15, kk 0..3, nb 0..3)
+ * -- value for value what the unpacked kernel re-stages through LDS for every (tile, chunk).  Eligible: K == 3, Cin % 16 == 0,
+ * Cout % 64 == 0; sq_conv_packed_filter_elems_f32 gives the element count 9 Cin Cout (-1: not eligible).
+ * sq_conv2d_packed_nhwc_fwd_f32 / sq_conv3x3_pool_packed_fwd_f32 are sq_conv2d_nhwc_fwd_f32 / sq_conv3x3_pool_fwd_f32 with the
+ * pack of `w` beside it (wp, or NULL): same bits.  The packed kernel (one barrier per item, halo double-buffered, A operands
+ * from the pack through a register ring) runs where sq_conv_packed_takes_f32 says 1: wp given, wscale == 1, the pack eligible
+ * the plan on 64-channel blocks (sq_conv_plan) and every tensor below 2 GiB, switch SQ_CONV_PACKED (0: never; read per call).  It walks the grid of the
+ * unpacked 64-channel form, so sq_conv_walk_plan describes it too.  Everything else runs the unpacked entry point on w.
+ * The caller keeps wp current: it is a function of w's contents at pack time. */
+int64_t sq_conv_packed_filter_elems_f32(int K, int Cin, int Cout);
+int sq_conv_pack_filter_f32(const float *w, float *wp, int K, int Cin, int Cout, void *stream);
+int sq_conv_packed_takes_f32(int N, int H, int W, int Cin, int Cout, int K);
+int sq_conv2d_packed_nhwc_fwd_f32(const float *x, const float *w, const float *wp, const float *bias, float *y, int N, int H,
+                                  int W, int Cin, int Cout, int K, float wscale, int act, void *stream);
+int sq_conv3x3_pool_packed_fwd_f32(const float *x, const float *w, const float *wp, const float *bias, float *y, float *pooled,
+                                   int N, int H, int W, int Cin, int Cout, int act, void *stream);
+
 /* last conv_layer of up0 + conv_layer_1x1 + prediction (unet.py:252-253,321): 3x3 conv Cin -> 16
  * + bias + act, then the 1x1 head (16 -> head_c <= 4, HWIO head_w (1,1,16,head_c)) and the argmax
  * mask in the epilogue; the 16-channel activation never reaches HBM.  mask may be NULL. */

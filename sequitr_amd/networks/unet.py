@@ -280,6 +280,7 @@ class UNet2D(UNet):
         self.bn_eps = float(params.get('bn_epsilon', ops.BN_EPS))
         self.bn_momentum = float(params.get('bn_momentum', ops.BN_MOMENTUM))
         self._mask = None
+        self._packs = {}                                      # inference: variable key -> ops.FilterPackF32 of that kernel, or None
 
     # -- variables ---------------------------------------------------------------------
     @classmethod
@@ -342,6 +343,29 @@ class UNet2D(UNet):
             self._loaded, self._creatable = True, set(opt)
         for k, v in weights.items():
             self._vars[k] = torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32)).to(self.device)
+        self._packs = {}                                      # new weights: every pack is rebuilt, whatever the epoch says
+        if not self.training and not self.batch_norm and type(self).conv_layer is UNet2D.conv_layer:   # the paths that pass pack=
+            for k in weights:
+                if k.endswith('/kernel'):
+                    self._wpack(k, self._vars[k])
+
+    def _wpack(self, key, w):
+        """The fragment-order pack (ops.FilterPackF32) of the 3x3 kernel variable `key`, or None where the filter has none
+        (ops.pack_filter).  An inference net owns the packs of its layers: made here when the weights are loaded (or, in a
+        net that was never loaded, when build() creates the variable), never per predict(); the pack itself repacks when
+        ops.invalidation_epoch() has moved -- every in-place parameter write of this code base bumps it."""
+        e = self._packs.get(key, False)
+        if e is False or (e is not None and e.w is not w):
+            e = self._packs[key] = ops.pack_filter(w)
+        return e
+
+    def refresh_packs(self):
+        """Repack every pack made before the last in-place parameter write (ops.invalidation_epoch() moved).  The eager
+        path does this per call inside ops; a replayed hipGraph runs no Python, so GraphedPredict calls it before a replay:
+        the packs are rewritten in place, at the addresses the captured kernels read."""
+        for e in self._packs.values():
+            if e is not None:
+                e.current(e.w)
 
     def initialize(self):
         """Create every variable without running a tile (same draws as a first build)."""
@@ -371,7 +395,7 @@ class UNet2D(UNet):
             return self.batch_norm_layer(z, act='relu')
         if self.training:
             return F.conv2d(x, w, b, act='relu')
-        return ops.conv2d(x, w, b, act='relu')
+        return ops.conv2d(x, w, b, act='relu', pack=self._wpack(self.scope + '/kernel', w))
 
     def batch_norm_layer(self, z, act=None):
         """tf.layers.batch_normalization(training=self.training) + activation: batch statistics (and a
@@ -517,11 +541,12 @@ class UNet2D(UNet):
             if i == 0 and cin == 1 and f[0] == 16:
                 y, pooled = ops.conv3x3_first_block(src, w1, b1, w2, b2, want_pool=not last)
             else:
-                c1 = ops.conv2d(src, w1, b1, act='relu')
+                p1, p2 = self._wpack(s + '/conv1/kernel', w1), self._wpack(s + '/conv2/kernel', w2)
+                c1 = ops.conv2d(src, w1, b1, act='relu', pack=p1)
                 if last:
-                    y, pooled = ops.conv2d(c1, w2, b2, act='relu'), None
+                    y, pooled = ops.conv2d(c1, w2, b2, act='relu', pack=p2), None
                 else:
-                    y, pooled = ops.conv3x3_pool(c1, w2, b2, act='relu')
+                    y, pooled = ops.conv3x3_pool(c1, w2, b2, act='relu', pack=p2)
             net.append(y)
         head_fused = f[0] == 16 and self.n_outputs <= 4
         logits = None
@@ -535,14 +560,14 @@ class UNet2D(UNet):
                 c1 = ops.convT_conv3x3(net[-1], wt, bt, net[i], self.bridge_type, w1, b1, act='relu')
             else:
                 merged = ops.convT2x2s2(net[-1], wt, bt, skip=net[i], bridge=self.bridge_type)
-                c1 = ops.conv2d(merged, w1, b1, act='relu')
+                c1 = ops.conv2d(merged, w1, b1, act='relu', pack=self._wpack(s + '/conv1/kernel', w1))
             if i == 0 and head_fused:
                 wh = self._v('UNet/to_image', 'kernel', (1, 1, f[0], self.n_outputs))
                 bh = self._v('UNet/to_image', 'bias', (self.n_outputs,))
                 logits, self._mask = ops.conv3x3_head(c1, w2, b2, wh, bh, act='relu')
                 net.append(None)                                   # up0's activation is never materialised
             else:
-                net.append(ops.conv2d(c1, w2, b2, act='relu'))
+                net.append(ops.conv2d(c1, w2, b2, act='relu', pack=self._wpack(s + '/conv2/kernel', w2)))
         if logits is None:
             wh = self._v('UNet/to_image', 'kernel', (1, 1, f[0], self.n_outputs))
             bh = self._v('UNet/to_image', 'bias', (self.n_outputs,))
@@ -681,6 +706,7 @@ class GraphedPredict(object):
         if tuple(features.shape) != tuple(self.x.shape):
             raise ValueError('captured for %s, got %s' % (tuple(self.x.shape), tuple(features.shape)))
         self.x.copy_(features, non_blocking=True)
+        self.net.refresh_packs()                             # a replay reads the filter packs as captured: keep them current
         self.graph.replay()
         return self.mask, self.logits
 

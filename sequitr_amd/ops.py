@@ -217,6 +217,52 @@ class FilterPackPlan(object):
         return self.out[d0:d0 + n]
 
 
+class FilterPackF32(object):
+    """The f32 fragment-order pack of ONE 3x3 inference filter (sq_conv_pack_filter_f32: a permutation of w's values for the
+    64-channel-block MFMA kernel), made once per model by its owner and handed to conv2d / conv3x3_pool as `pack=`.  It holds
+    the filter tensor itself (ops never guesses a pack from a data pointer: the call's `w` must BE that tensor) and the
+    invalidation epoch it was made at; current() repacks when any in-place parameter write (invalidate_packs) came since."""
+
+    def __init__(self, w):
+        _chk(w, "w", ndim=4)
+        K, K2, Cin, Cout = w.shape
+        n = _lib.load().sq_conv_packed_filter_elems_f32(K, Cin, Cout) if K == K2 else -1
+        if n <= 0:
+            raise ValueError("no f32 filter pack for a %s filter (3x3, Cin %% 16 == 0, Cout %% 64 == 0)" % (tuple(w.shape),))
+        self.w = w
+        self.wp = torch.empty((n,), dtype=torch.float32, device=w.device)
+        self.epoch = None
+        self.repack()
+
+    def repack(self):
+        K, _, Cin, Cout = self.w.shape
+        self.epoch = invalidation_epoch()
+        _lib.check(_lib.load().sq_conv_pack_filter_f32(_ptr(self.w), _ptr(self.wp), K, Cin, Cout, _stream()),
+                   "sq_conv_pack_filter_f32")
+
+    def current(self, w):
+        if w is not self.w:
+            raise ValueError("pack= belongs to another filter tensor than the call's w")
+        if self.epoch != invalidation_epoch():
+            self.repack()
+        return self.wp
+
+
+def pack_filter(w):
+    """FilterPackF32 of `w`, or None where the filter has no pack (not 3x3, Cin % 16, Cout % 64)"""
+    if w.dim() != 4 or w.shape[0] != w.shape[1] or w.dtype != torch.float32:
+        return None
+    if _lib.load().sq_conv_packed_filter_elems_f32(w.shape[0], w.shape[2], w.shape[3]) <= 0:
+        return None
+    return FilterPackF32(w)
+
+
+def conv_packed_takes(x_shape, w_shape):
+    """does conv2d / conv3x3_pool with a pack run the packed kernel at this shape?  (sq_conv_packed_takes_f32, host only)"""
+    N, H, W, Cin = x_shape
+    return bool(_lib.load().sq_conv_packed_takes_f32(N, H, W, Cin, w_shape[3], w_shape[0])) and w_shape[2] == Cin
+
+
 def _packed_filter(w, K, Cin, Cout, wscale, transform):
     """bf16 pack of the conv Cin -> Cout; transform: `w` is the FORWARD filter (K,K,Cout,Cin) of which this conv
     is the dgrad (taps rotated, channel roles swapped inside the pack kernel -- no separate transform pass)."""
@@ -283,8 +329,10 @@ def dense_wgrad(x, dy, want_bias=True, dw_scale=1.0, shape4=False, dw_out=None, 
     return dw, db
 
 
-def conv2d(x, w, bias=None, act=None, wscale=1.0, out=None, _dgrad=False):
+def conv2d(x, w, bias=None, act=None, wscale=1.0, out=None, _dgrad=False, pack=None):
     """KxK SAME conv + bias + activation.  x (N,H,W,Cin), w (K,K,Cin,Cout) HWIO.
+    pack: the FilterPackF32 of `w` (inference models): the plain f32 call then reads the filter from it where the packed
+    kernel takes the shape -- same bits; every other route of this function ignores it.
     Batches of small images (H, W <= 8) run as one mosaic image (3x3) or as a flat pixel strip (1x1):
     same fmaf chain per output, far fewer and fuller 16x16 tiles.
     _dgrad (internal): `w` is the filter (K,K,Cout,Cin) of the forward conv whose input gradient this is."""
@@ -327,6 +375,11 @@ def conv2d(x, w, bias=None, act=None, wscale=1.0, out=None, _dgrad=False):
     if MIXED and Cin % 8 == 0 and Cout % 4 == 0:
         return _conv2d_mixed(x, w, bias, act, wscale, y, _dgrad)
     lib = _lib.load()
+    if pack is not None and not _dgrad:
+        _lib.check(lib.sq_conv2d_packed_nhwc_fwd_f32(_ptr(x), _ptr(w), _ptr(pack.current(w)), _ptr(bias), _ptr(y), N, H, W, Cin,
+                                                    Cout, K, float(wscale), ACT[act], _stream()),
+                   "sq_conv2d_packed_nhwc_fwd_f32")
+        return y
     _lib.check(lib.sq_conv2d_nhwc_fwd_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), N, H, W, Cin, Cout, K,
                                          float(wscale), ACT[act], _stream()), "sq_conv2d_nhwc_fwd_f32")
     return y
@@ -1315,8 +1368,8 @@ def conv_wgrad_raw(x, dy, K, want_bias=False, dw_out=None, db_out=None, dw_scale
 # ----------------------------------------------------------------------------------------------
 # fused inference variants (include/sequitr_hip.h "Fused inference variants")
 # ----------------------------------------------------------------------------------------------
-def conv3x3_pool(x, w, bias, act="relu"):
-    """conv + bias + act -> (y, maxpool2x2(y)) from one kernel."""
+def conv3x3_pool(x, w, bias, act="relu", pack=None):
+    """conv + bias + act -> (y, maxpool2x2(y)) from one kernel.  pack: the FilterPackF32 of `w` (see conv2d)."""
     _chk(x, "x", ndim=4), _chk(w, "w", ndim=4)
     N, H, W, Cin = x.shape
     Cout = w.shape[3]
@@ -1327,6 +1380,10 @@ def conv3x3_pool(x, w, bias, act="relu"):
     y = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x.device)
     p = torch.empty((N, H // 2, W // 2, Cout), dtype=torch.float32, device=x.device)
     lib = _lib.load()
+    if pack is not None:
+        _lib.check(lib.sq_conv3x3_pool_packed_fwd_f32(_ptr(x), _ptr(w), _ptr(pack.current(w)), _ptr(bias), _ptr(y), _ptr(p), N, H,
+                                                     W, Cin, Cout, ACT[act], _stream()), "sq_conv3x3_pool_packed_fwd_f32")
+        return y, p
     _lib.check(lib.sq_conv3x3_pool_fwd_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), _ptr(p), N, H, W, Cin, Cout,
                                           ACT[act], _stream()), "sq_conv3x3_pool_fwd_f32")
     return y, p

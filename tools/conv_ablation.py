@@ -73,23 +73,23 @@ def _build(src_file, obj_name, variants):
 _STAMP = ("if (dbg_ && vb < 32 && lane == 0 && it < 64) dbg_[(((size_t)vb * 4 + wv) * 64 + it) * 6 + %d] = "
           "(long long)__builtin_readcyclecounter();\n")
 VARIANTS["timeline"] = [
-    ("    SqConvEpi epi = {};\n    epi.store_y = 1;\n    if (Cin % 16 == 0)\n        return K == 3 ? dispatch_bn<3, 16>(x, w, bias, y, N, H, W, Cin, Cout, wscale, act, epi, st)",
-     "    SqConvEpi epi = {};\n    epi.store_y = 1;\n    if (const char *e_ = getenv(\"SQ_DBG_PTR\")) epi.first_b = (const float *)strtoull(e_, 0, 16);\n"
-     "    if (Cin % 16 == 0)\n        return K == 3 ? dispatch_bn<3, 16>(x, w, bias, y, N, H, W, Cin, Cout, wscale, act, epi, st)"),
+    ("    epi.store_y = 1;\n    if (Cin == 16 && (Cout == 16 || Cout == 32) && K == 3 && wscale == 1.0f) {\n",
+     "    epi.store_y = 1;\n    if (const char *e_ = getenv(\"SQ_DBG_PTR\")) epi.first_b = (const float *)strtoull(e_, 0, 16);\n"
+     "    if (Cin == 16 && (Cout == 16 || Cout == 32) && K == 3 && wscale == 1.0f) {\n"),
     ('#include "sq_common.h"\n', '#include "sq_common.h"\n#include <stdlib.h>\n'),
     ("    int tile = t_begin, chunk = 0;\n    for (int it = 0; it < nitems; ++it) {\n",
      "    long long *dbg_ = MODE == 0 ? (long long *)epi.first_b : nullptr;\n"
      "    int tile = t_begin, chunk = 0;\n    for (int it = 0; it < nitems; ++it) {\n"),
-    ("        if (has_next) issue(ntile, nchk * KC, restage_w, true);\n",
-     "        if (has_next) issue(ntile, nchk * KC, restage_w, true);\n        " + _STAMP % 0),
+    ("        if (has_next) issue(itx, ity, itn, nchk * KC, restage_w, true);\n",
+     "        if (has_next) issue(itx, ity, itn, nchk * KC, restage_w, true);\n        " + _STAMP % 0),
     ("            __builtin_amdgcn_s_setprio(3);\n        }\n",
      "            __builtin_amdgcn_s_setprio(3);\n        }\n        " + _STAMP % 1),
     ("        __builtin_amdgcn_s_waitcnt(0x0F70);                     // vmcnt(0); expcnt / lgkmcnt untouched\n        if (has_next) {\n"
      "            __syncthreads();            // every wave is done reading this item's LDS image\n            commit(restage_w);\n",
      "        __builtin_amdgcn_s_waitcnt(0x0F70);\n        " + _STAMP % 2 +
      "        if (has_next) {\n            __syncthreads();\n            commit(restage_w);\n            __builtin_amdgcn_s_waitcnt(0);\n            " + _STAMP % 3),
-    ("        if (chunk == nchunk - 1) epilogue(tile);\n        if (has_next) __syncthreads();\n",
-     "        if (chunk == nchunk - 1) epilogue(tile);\n        " + _STAMP % 4 + "        if (has_next) __syncthreads();\n        " + _STAMP % 5),
+    ("        if (has_next) __syncthreads();\n        if (ntile != tile) {",
+     "        " + _STAMP % 4 + "        if (has_next) __syncthreads();\n        " + _STAMP % 5 + "        if (ntile != tile) {"),
 ]
 
 
@@ -102,7 +102,7 @@ def timeline():
     dbg = torch.zeros((32 * 4 * 64 * 6,), dtype=torch.int64, device="cuda:0")
     os.environ["SQ_DBG_PTR"] = "%x" % dbg.data_ptr()
     from sequitr_amd import ops
-    for (n, h, ci, co) in [(32, 512, 16, 16), (32, 256, 32, 32), (32, 128, 64, 64)]:
+    for (n, h, ci, co) in [(32, 128, 64, 64), (32, 64, 128, 128), (32, 32, 256, 256)]:       # the <64,3,16> layers
         x = torch.randn(n, h, h, ci, device="cuda:0")
         w = torch.randn(3, 3, ci, co, device="cuda:0") * 0.05
         b = torch.zeros(co, device="cuda:0")
