@@ -1118,6 +1118,62 @@ int sq_stitch_probs(const float *tile_logits, const int32_t *ymap, const int32_t
                     int prob_dtype, float inv_n, int F, int H, int W, int TR, int TC, int TS, int K, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Seam blending: sq_stitch_probs with more than one tile per frame pixel (sequitr_amd/frontend.py: axis_blend,
+ * FrameTiler.stitch_blend, segment_frames(blend=)).  Neighbouring tiles overlap by 2 * margin and see different context, so
+ * their logits disagree a little and an owner-map stitch carries a step along every seam line; here the merged logits of
+ * the overlapping tiles are mixed with integer tent weights before the argmax and the softmax.  Planar frames only: bricks
+ * keep one owner per voxel.
+ *
+ * PER AXIS.  An axis of length L, tile T, margin m, the origins o[0 .. n-1] of the tile front end.  Tile k owns
+ * [s[k], s[k+1]) with s[0] = 0, s[k] = o[k] + m for k >= 1 and s[n] = L: the runs the owner map encodes.  With a blend
+ * width B the integer weight of tile k at frame coordinate p is
+ *
+ *     dl = p - s[k]            if k > 0      else +infinity
+ *     dr = s[k+1] - 1 - p      if k < n - 1  else +infinity
+ *     w_k(p) = clamp(min(dl, dr) + B + 1, 0, 2B + 1)
+ *
+ * B must satisfy 0 <= B <= m, 2B <= T - 2m and B <= 255.  Then: w_k(p) > 0 only inside tile k, and for k > 0 only at local
+ * coordinates >= m - B (the outer m - B pixels of a tile are never used); the owner's weight is >= B + 1; the tiles with a
+ * positive weight at p are consecutive and at most 3 (three where the last tile is clamped to L - T and its neighbour's run
+ * is shorter than 2B: L = 53, T = 16, m = 4, B = 4 has origins 0, 8, 16, 24, 32, 37 and weight sums 10, 11, 10 at
+ * p = 37, 38, 39); at a regular seam s, pixel s + j with -B <= j < B gets the weights B - j and B + j + 1, sum 2B + 1;
+ * with B = 0 every pixel has its owner with weight 1 and nothing else.
+ *
+ * PER PIXEL.  KY and KX are the contributing tiles (positive weight) along y and x, each ascending; acc is the MERGE of
+ * "Tile views and probability stitch".  In float32, contraction off:
+ *
+ *     S_c = +0.0f
+ *     for ky in KY ascending: for kx in KX ascending:
+ *         S_c = S_c + (float)(wy * wx) * acc[tile(f, ky, kx), y - oy[ky], x - ox[kx], c]
+ *     Wt  = (float)(sum(wy over KY) * sum(wx over KX))        exact: < 2^24
+ *     b_c = S_c / Wt
+ *
+ * Terms with zero weight are not read and not added: a NaN in a tile that does not contribute does not show.  A pixel
+ * with one contributor goes through the same expression, b_c = (w * acc_c) / w.
+ *
+ * MASK is sq_argmax_u8's loop on b_0 .. b_{K-1}; PROBABILITIES the text of "Tile views and probability stitch" with
+ * l_k = b_k * inv_n, its bound against the float64 softmax of those l_k unchanged.  At B = 0 both outputs are
+ * sq_stitch_probs' bit for bit (w = Wt = 1; +0 + (-0) = +0 changes no comparison and no expf).
+ *
+ * SLOTS.  yslots / xslots are (L, 3, 2) int32 tables built on the host: per coordinate three slots of
+ * (tile << 16 | local coordinate, weight), the contributors first in ascending tile order, unused slots (0, 0).
+ *
+ *   sq_blend_axis_slots : host only, no HIP call: fills slots (L, 3, 2) in host memory for one axis and returns the number
+ *                         of tiles n, or SQ_EINVAL (slots untouched) for a null pointer, T outside 1 .. 65535, T > L,
+ *                         margin outside 0 <= 2 margin < T, blend outside the range above, or more than 65535 tiles.
+ *   sq_stitch_blend     : mask_out (F, H, W) uint8 and / or prob_out (F, K, H, W) of prob_dtype SQ_PIX_U8 or SQ_PIX_F32
+ *                         from tile_logits (F*TR*TC, TS, TS, K) = acc, as defined above.  Either output may be NULL, not
+ *                         both.  K is 1 .. 16, inv_n in (0, 1]; F * H <= 2^31 - 1; tile_logits 16-byte aligned, the slot
+ *                         tables 8-byte aligned (a slot is read as one pair of words; else SQ_EINVAL).  The tables are
+ *                         trusted as sq_stitch_masks_u8 trusts its maps.  One frame pixel per lane; a wave none of whose
+ *                         pixels lies in a blend band reads one tile per pixel, as sq_stitch_probs does.  No allocation,
+ *                         no synchronisation: the same under graph capture.
+ * ---------------------------------------------------------------------------------------- */
+int sq_blend_axis_slots(int L, int T, int margin, int blend, int32_t *slots);
+int sq_stitch_blend(const float *tile_logits, const int32_t *yslots, const int32_t *xslots, uint8_t *mask_out, void *prob_out,
+                    int prob_dtype, float inv_n, int F, int H, int W, int TR, int TC, int TS, int K, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame cleaning: the pipes the reference applies to raw microscope frames in front of ImageNorm, per whole frame,
  * in the order ImageOutliers -> ImageBlur -> ImageBGSubtract -> ImageNorm (sequitr_amd/frontend.py: FrameClean,
  * FrameTiler).

@@ -81,6 +81,8 @@ SIGNATURES = {
     "sq_tiles_view_block": (c_int, [c_int]),
     "sq_tiles_view_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "sq_stitch_probs": (c_int, [c_void_p] * 5 + [c_int, c_float] + [c_int] * 7 + [c_void_p]),
+    "sq_blend_axis_slots": (c_int, [c_int] * 4 + [c_void_p]),
+    "sq_stitch_blend": (c_int, [c_void_p] * 5 + [c_int, c_float] + [c_int] * 7 + [c_void_p]),
     "sq_frame_outliers_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "sq_frame_blur_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "sq_frame_bgfit_workspace": (c_int64, [c_int, c_int, c_int]),

@@ -18,7 +18,9 @@ Behind the network the frame path can keep the float32 logits: FrameTiler.view a
 to a tile batch (and undoes them, accumulating), so that segment_frames(tta='flips' | 'dihedral') averages the network's
 logits over the flip states of the reference's ImageFlip or over all eight, and FrameTiler.stitch_probs writes the mask of
 the merged logits and their softmax as whole frames in one launch (segment_frames(probabilities=); include/sequitr_hip.h
-"Tile views and probability stitch").
+"Tile views and probability stitch").  Neighbouring tiles overlap by 2 * margin; segment_frames(blend=) mixes their
+logits across every seam with integer tent weights in the same launch (axis_blend, FrameTiler.stitch_blend;
+include/sequitr_hip.h "Seam blending") instead of giving every pixel one owner tile.
 
 Volumes take the same path in three dimensions (VolumeTiler, segment_volumes): a brick is a box of the network's
 input shape, the rule above holds along each axis, and an axis shorter than the brick is padded with the
@@ -68,6 +70,49 @@ def axis_tiles(L, T, margin):
     owner = np.searchsorted(starts, np.arange(L), side='right') - 1
     local = np.arange(L) - origins[owner]
     return origins, ((owner.astype(np.int64) << 16) | local).astype(np.int32)
+
+
+def check_blend(blend, T, margin):
+    """the blend width B of seam blending as an int: None is 0; 0 <= B <= margin, 2B <= T - 2 margin and B <= 255"""
+    if blend is None:
+        return 0
+    if isinstance(blend, bool) or not isinstance(blend, (int, np.integer)):
+        raise ValueError('blend must be None or an integer number of pixels, got %r' % (blend,))
+    B = int(blend)
+    if not (0 <= B <= margin and 2 * B <= T - 2 * margin and B <= 255):
+        raise ValueError('blend %d is not in 0 .. %d: a seam is blended over at most the margin (%d), half of what a tile '
+                         'of %d owns, and 255 pixels' % (B, max(0, min(margin, (T - 2 * margin) // 2, 255)), margin, T))
+    return B
+
+
+def axis_blend(L, T, margin, blend):
+    """(origins, slots) along one axis for seam blending (include/sequitr_hip.h "Seam blending"): axis_tiles' origins and
+    an (L, 3, 2) int32 table, per coordinate three slots of (tile index << 16 | local coordinate, weight) -- the tiles
+    whose tent weight clamp(min(p - s[k], s[k+1] - 1 - p) + blend + 1, 0, 2 blend + 1) is positive, in ascending order
+    (at most three, the owner among them), then (0, 0).  Tile k owns [s[k], s[k+1]); the frame border cuts no weight."""
+    origins, _ = axis_tiles(L, T, margin)
+    B = check_blend(blend, T, margin)
+    n = len(origins)
+    s = np.concatenate([origins.astype(np.int64) + margin, [L]])
+    s[0] = 0
+    slots = np.zeros((L, 3, 2), np.int32)
+    used = np.zeros(L, np.int64)
+    for k in range(n):                                          # ascending: a coordinate's slots fill in tile order
+        lo, hi = (max(0, s[k] - B) if k else 0), (min(L, s[k + 1] + B) if k < n - 1 else L)
+        p = np.arange(lo, hi)
+        d = np.full(len(p), 2 * B, np.int64)                    # at least B: the clamp's upper end
+        if k:
+            d = np.minimum(d, p - s[k])
+        if k < n - 1:
+            d = np.minimum(d, s[k + 1] - 1 - p)
+        w = np.clip(d + B + 1, 0, 2 * B + 1)
+        p, w = p[w > 0], w[w > 0]
+        if len(p) and used[p].max() >= 3:
+            raise AssertionError('more than three tiles at one coordinate')
+        slots[p, used[p], 0] = (k << 16) | (p - int(origins[k]))
+        slots[p, used[p], 1] = w
+        used[p] += 1
+    return origins, slots
 
 
 def axis_bricks(L, T, margin):
@@ -275,6 +320,7 @@ class FrameTiler(object):
         d = self.device
         self._oy, self._ox = torch.from_numpy(self.oy).to(d), torch.from_numpy(self.ox).to(d)
         self._ymap, self._xmap = torch.from_numpy(self.ymap).to(d), torch.from_numpy(self.xmap).to(d)
+        self._blend_slots = {}                                  # blend -> (yslots, xslots) in HBM, made on first use
 
     @property
     def tiles_per_frame(self):
@@ -596,11 +642,8 @@ class FrameTiler(object):
                    'sq_tiles_view_f32')
         return out
 
-    def stitch_probs(self, tile_logits, n=1, mask=True, probabilities=None):
-        """(F*TR*TC, T, T, K) float32 tile logits -- one pass, or the merged sum of n = 4 or 8 views -- to whole frames in
-        one launch: returns (mask or None, probs or None), the (F, H, W) uint8 class mask (sq_argmax_u8's rule on the
-        owner tile's logits) and the (F, K, H, W) softmax of logits / n as `probabilities` = 'uint8' (rounded p * 255) or
-        'float32' (include/sequitr_hip.h "Tile views and probability stitch")."""
+    def _check_logits(self, tile_logits, n, mask, probabilities):
+        """what stitch_probs and stitch_blend take: (F, K, torch dtype of the probabilities or None)"""
         if not isinstance(tile_logits, torch.Tensor) or not tile_logits.is_cuda:
             raise _lib.SequitrHipError('tile_logits must be a tensor in GPU memory (no CPU fallback exists)')
         if tile_logits.dtype != torch.float32 or tile_logits.dim() != 4 or not tile_logits.is_contiguous():
@@ -615,13 +658,39 @@ class FrameTiler(object):
         dtype = check_probabilities(probabilities)
         if not mask and dtype is None:
             raise ValueError('nothing to compute: mask is off and probabilities is None')
-        F = nt // self.tiles_per_frame
+        return nt // self.tiles_per_frame, K, dtype
+
+    def stitch_probs(self, tile_logits, n=1, mask=True, probabilities=None):
+        """(F*TR*TC, T, T, K) float32 tile logits -- one pass, or the merged sum of n = 4 or 8 views -- to whole frames in
+        one launch: returns (mask or None, probs or None), the (F, H, W) uint8 class mask (sq_argmax_u8's rule on the
+        owner tile's logits) and the (F, K, H, W) softmax of logits / n as `probabilities` = 'uint8' (rounded p * 255) or
+        'float32' (include/sequitr_hip.h "Tile views and probability stitch")."""
+        F, K, dtype = self._check_logits(tile_logits, n, mask, probabilities)
         m = torch.empty((F, self.H, self.W), dtype=torch.uint8, device=self.device) if mask else None
         p = torch.empty((F, K, self.H, self.W), dtype=dtype, device=self.device) if dtype is not None else None
         _lib.check(_lib.load().sq_stitch_probs(tile_logits.data_ptr(), self._ymap.data_ptr(), self._xmap.data_ptr(),
                                                m.data_ptr() if mask else None, p.data_ptr() if p is not None else None,
                                                PIX[dtype] if p is not None else 0, 1.0 / n, F, self.H, self.W, self.TR,
                                                self.TC, self.T, K, torch.cuda.current_stream().cuda_stream), 'sq_stitch_probs')
+        return m, p
+
+    def stitch_blend(self, tile_logits, blend, n=1, mask=True, probabilities=None):
+        """stitch_probs with the seams blended over `blend` pixels to either side: where tiles overlap, the logits of up
+        to 3 x 3 of them are mixed with axis_blend's integer tent weights before the argmax and the softmax, in one launch
+        (include/sequitr_hip.h "Seam blending").  Arguments and results are stitch_probs'; blend is 0 .. min(margin,
+        (tile - 2 margin) // 2, 255), and blend = 0 gives stitch_probs' bits.  The device tables are made once per blend."""
+        F, K, dtype = self._check_logits(tile_logits, n, mask, probabilities)
+        B = check_blend(blend, self.T, self.margin)
+        if B not in self._blend_slots:
+            self._blend_slots[B] = tuple(torch.from_numpy(axis_blend(L, self.T, self.margin, B)[1]).to(self.device)
+                                         for L in (self.H, self.W))
+        yslots, xslots = self._blend_slots[B]
+        m = torch.empty((F, self.H, self.W), dtype=torch.uint8, device=self.device) if mask else None
+        p = torch.empty((F, K, self.H, self.W), dtype=dtype, device=self.device) if dtype is not None else None
+        _lib.check(_lib.load().sq_stitch_blend(tile_logits.data_ptr(), yslots.data_ptr(), xslots.data_ptr(),
+                                               m.data_ptr() if mask else None, p.data_ptr() if p is not None else None,
+                                               PIX[dtype] if p is not None else 0, 1.0 / n, F, self.H, self.W, self.TR,
+                                               self.TC, self.T, K, torch.cuda.current_stream().cuda_stream), 'sq_stitch_blend')
         return m, p
 
 
@@ -695,7 +764,7 @@ def open_channels(frames):
 
 
 def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normalise=True, on_masks=None, clean=None,
-                   on_batch=None, postprocess=None, tta=None, probabilities=None, on_probs=None):
+                   on_batch=None, postprocess=None, tta=None, probabilities=None, on_probs=None, blend=None):
     """Segment a stack of raw frames (numpy array / memmap / OctopusData, (F,H,W) uint8|uint16|float32).
     Raw frames are staged through two pinned buffers and uploaded on a side stream while the previous batch is
     normalised, tiled, segmented (net.predict) and stitched; returns the (F,H,W) uint8 masks (host), or
@@ -727,18 +796,26 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
     (on_masks / on_batch), on_probs(first_frame, probs) is called with the batch's device tensor just before it (valid
     until the callback returns) and is required; on_probs without `probabilities`, or without a mask sink, raises.
     `postprocess` changes the masks only: the probabilities are the network's own.  With both keys None the function
-    runs what it always ran (net.predict, then stitch).  A bad value raises before a frame is read."""
+    runs what it always ran (net.predict, then stitch).  A bad value raises before a frame is read.
+
+    `blend` (pixels, 1 .. min(margin, (tile - 2 margin) // 2, 255)) blends the seams: neighbouring tiles overlap by
+    2 * margin, and within `blend` pixels to either side of every seam line the (summed) logits of the overlapping tiles
+    are mixed with integer tent weights before the argmax and the softmax (FrameTiler.stitch_blend; include/sequitr_hip.h
+    "Seam blending"), so that mask and probabilities carry no step there.  It costs no network pass and goes with `tta`,
+    `probabilities`, `postprocess` and every sink.  None or 0: one owner tile per pixel, the code of before; a value out
+    of range (any blend >= 1 with margin 0) raises before a frame is read."""
     if on_masks is not None and on_batch is not None:
         raise ValueError('on_masks and on_batch are two forms of the same sink: pass one of them')
     view_ops, prob_dtype = check_tta(tta), check_probabilities(probabilities)
+    blend = check_blend(blend, int(tile), int(margin))
     if on_probs is not None and prob_dtype is None:
         raise ValueError("on_probs receives the probabilities: it needs probabilities='uint8' or 'float32'")
     if (on_probs is not None) != (prob_dtype is not None and (on_masks is not None or on_batch is not None)):
         raise ValueError('on_probs goes with on_masks / on_batch: with a mask sink the probabilities need on_probs, '
                          'without one both come back as host arrays')
-    merged = len(view_ops) > 1 or prob_dtype is not None       # else: exactly the code of before, predict + stitch
+    merged = len(view_ops) > 1 or prob_dtype is not None or blend > 0   # else: exactly the code of before, predict + stitch
     if merged and not 1 <= int(net.n_outputs) <= 16:
-        raise ValueError('tta / probabilities take 1 .. 16 classes, the network has %d' % int(net.n_outputs))
+        raise ValueError('tta / probabilities / blend take 1 .. 16 classes, the network has %d' % int(net.n_outputs))
     if postprocess is not None:
         from .maskops import MaskCleanup
         if not isinstance(postprocess, MaskCleanup):
@@ -823,7 +900,9 @@ def segment_frames(net, frames, tile=512, margin=32, frames_per_batch=4, normali
         tiles = tiler.tiles(raw, normalise=normalise, clean=clean, scratch=scratch)
         if on_batch is None:
             freed[k].record(cur)                               # after the last kernel that reads staged[k]
-        if merged:
+        if blend:
+            masks, probs = tiler.stitch_blend(merged_logits(tiles), blend, n=len(view_ops), probabilities=probabilities)
+        elif merged:
             masks, probs = tiler.stitch_probs(merged_logits(tiles), n=len(view_ops), probabilities=probabilities)
         else:
             masks, probs = tiler.stitch(net.predict(tiles)), None

@@ -83,6 +83,7 @@ def SERVER_segment(params, options):
     _refuse_volume_postprocess(params, 'SERVER_segment')
     _refuse_volume_tta(params, options, 'SERVER_segment')
     _refuse_tta(params, options, 'SERVER_segment (the tile job)')
+    _refuse_blend(params, 'SERVER_segment (the tile job)')
     import torch
     from .networks.unet import UNet2D
     from .pipeline import ImagePipeline
@@ -430,6 +431,7 @@ def SERVER_segment_volume(params, options):
         raise ValueError("params['postprocess'] cleans planar (N,H,W) masks only: volumes are out of scope "
                          "(params['volume_postprocess'] cleans them)")
     _refuse_tta(params, options, 'SERVER_segment_volume')
+    _refuse_blend(params, 'SERVER_segment_volume')
     volume_tta = _parse_volume_tta(params, options, 'SERVER_segment_volume')    # before anything is opened
     cleanup = _parse_volume_postprocess(params)                 # likewise
     analysis = _parse_volume_analysis(params, options)          # likewise
@@ -599,6 +601,31 @@ def _refuse_tta(params, options, job):
                          "SERVER_evaluate on frames): %s does not take them" % job)
 
 
+def _parse_blend(params, job):
+    """params['blend'] of a whole-frame job: null, or the number of pixels to either side of a seam over which
+    frontend.segment_frames blends the overlapping tiles (0: none), checked against the job's tile and margin as
+    segment_frames checks it.  Volumes (params['brick']) do not take it; a bad value raises here, before anything is
+    opened."""
+    blend = params.get('blend')
+    if blend is None:
+        return None
+    if params.get('brick') is not None:
+        raise ValueError("params['blend'] covers whole frames only: %s with params['brick'] segments volumes, and seam "
+                         "blending between bricks is not built" % job)
+    from .frontend import check_blend
+    try:
+        return check_blend(blend, int(params.get('shape', (512, 512))[0]), int(params.get('margin', 32)))
+    except ValueError as e:
+        raise ValueError("params['blend']: %s" % e)
+
+
+def _refuse_blend(params, job):
+    """jobs that do not segment whole frames do not take params['blend']"""
+    if params.get('blend') is not None:
+        raise ValueError("params['blend'] belongs to the whole-frame jobs (SERVER_segment_frames, SERVER_evaluate on "
+                         "frames): %s does not take it" % job)
+
+
 def _parse_volume_tta(params, options, job):
     """(volume_tta, probabilities) of a brick job: params['volume_tta'] -- null, "flips" or "dihedral"
     (frontend.segment_volumes' view sets: the 8 mirror states, or the 16 symmetries the volume sampler trains with, which
@@ -740,10 +767,18 @@ def SERVER_segment_frames(params, options):
     with the defaults filled in, but only when the keys are present.  A bad value, or either key together with
     params['brick'], raises before anything is opened; SERVER_segment (the tile job) and SERVER_segment_volume refuse both.
     WORLD_SIZE plays no part in this job (every process segments the stack it was given), so the keys add nothing to refuse
-    there.  Without them every file is what it was."""
+    there.  Without them every file is what it was.
+
+    params['blend'] (an integer number of pixels, 0 .. min(margin, (tile - 2 margin) // 2, 255)) blends the seams between
+    overlapping tiles (frontend.segment_frames(blend=): within that distance of a seam line the tiles' logits are mixed with
+    integer tent weights before the argmax and the softmax).  It goes with `tta` and `save_probabilities`, and every sink
+    sees the blended mask as above.  segment.json records ``blend`` when the key is present.  A bad value, or the key
+    together with params['brick'], raises before anything is opened; SERVER_segment, SERVER_segment_volume and the training
+    jobs refuse it.  Without the key (or with null / 0) every file is what it was."""
     _refuse_volume_postprocess(params, 'SERVER_segment_frames')
     _refuse_volume_tta(params, options, 'SERVER_segment_frames')
     tta, probabilities = _parse_tta(params, options, 'SERVER_segment_frames')
+    blend = _parse_blend(params, 'SERVER_segment_frames')
     postprocess = _parse_postprocess(params)                    # before anything is opened
     want_neighbors = bool(options.get('neighbors'))
     want_link = bool(options.get('link'))
@@ -831,7 +866,7 @@ def SERVER_segment_frames(params, options):
                          frames_per_batch=int(params.get('frames_per_batch', 4)),
                          on_masks=sink if want_centroids and not want_measure else None,
                          on_batch=measure_sink if want_measure else None, normalise=normalise, clean=clean,
-                         postprocess=postprocess, tta=tta, probabilities=probabilities,
+                         postprocess=postprocess, tta=tta, probabilities=probabilities, blend=blend,
                          on_probs=prob_sink if prob_stack is not None else None)
     if probabilities is not None and not want_centroids:
         out, prob_stack = out
@@ -848,6 +883,8 @@ def SERVER_segment_frames(params, options):
         info['tta'] = tta
     if 'save_probabilities' in options:
         info['probabilities'] = probabilities
+    if 'blend' in params:
+        info['blend'] = blend
     if C_in is not None:
         info['channels'] = C_in
         if want_measure:
@@ -1052,10 +1089,15 @@ def SERVER_evaluate(params, options):
     the way to see whether the 4 or 8 network passes pay on a data set; evaluate.json records ``tta`` when the key is
     present.  Frames only: with params['brick'] it is refused, and so is options['save_probabilities'], before anything is
     opened.  With params['brick'], params['volume_tta'] (as SERVER_segment_volume takes it) scores the merged masks of the
-    8 or 16 views and evaluate.json records ``volume_tta``; options['save_volume_probabilities'] is refused."""
+    8 or 16 views and evaluate.json records ``volume_tta``; options['save_volume_probabilities'] is refused.
+
+    params['blend'] (as SERVER_segment_frames takes it) scores the masks with the seams between tiles blended;
+    evaluate.json records ``blend`` when the key is present.  Frames only: with params['brick'] it is refused before
+    anything is opened."""
     if options.get('save_probabilities'):
         raise ValueError("options['save_probabilities'] belongs to SERVER_segment_frames: SERVER_evaluate writes scores")
     tta, _ = _parse_tta(params, {}, 'SERVER_evaluate')          # before anything is opened
+    blend = _parse_blend(params, 'SERVER_evaluate')
     postprocess = _parse_postprocess(params)
     cleanup = _parse_volume_postprocess(params)
     if options.get('save_volume_probabilities'):
@@ -1100,7 +1142,7 @@ def SERVER_evaluate(params, options):
 
     t0 = time.time()
     segment_frames(net, frames, tile=tile, margin=int(params.get('margin', 32)), frames_per_batch=B, on_masks=sink,
-                   normalise=normalise, clean=clean, postprocess=postprocess, tta=tta)
+                   normalise=normalise, clean=clean, postprocess=postprocess, tta=tta, blend=blend)
     counts_h, ignored_h = counts.cpu().numpy(), ignored.cpu().numpy()
     dt = time.time() - t0
     np.save(os.path.join(out_dir, 'confusion.npy'), counts_h)
@@ -1110,6 +1152,8 @@ def SERVER_evaluate(params, options):
             'mpixels_per_s': float(F * H * W / max(dt, 1e-9) / 1e6), 'device': device}
     if 'tta' in params:
         info['tta'] = tta
+    if 'blend' in params:
+        info['blend'] = blend
     if C_in is not None:
         info['channels'] = C_in
     if pipe_record is not None:
@@ -1491,6 +1535,7 @@ def SERVER_train(params, options):
     """
     _refuse_volume_postprocess(params, 'SERVER_train')
     _refuse_volume_tta(params, options, 'SERVER_train')
+    _refuse_blend(params, 'SERVER_train')
     if params.get('tile') is not None:
         return _train_frame_tiles(params, options)
     import torch
@@ -1753,6 +1798,7 @@ def SERVER_train_volume(params, options):
     """
     _refuse_volume_postprocess(params, 'SERVER_train_volume')
     _refuse_volume_tta(params, options, 'SERVER_train_volume')
+    _refuse_blend(params, 'SERVER_train_volume')
     import torch
     from . import utils
     from .networks.unet import UNet3DTrain
@@ -1842,6 +1888,7 @@ def SERVER_train_gan(params, options):
     crop, images, seconds, export_dir."""
     _refuse_volume_postprocess(params, 'SERVER_train_gan')
     _refuse_volume_tta(params, options, 'SERVER_train_gan')
+    _refuse_blend(params, 'SERVER_train_gan')
     import torch
     from .networks import gan
 
