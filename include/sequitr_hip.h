@@ -369,6 +369,13 @@ int sq_conv2d_packed_nhwc_fwd_f32(const float *x, const float *w, const float *w
 int sq_conv3x3_pool_packed_fwd_f32(const float *x, const float *w, const float *wp, const float *bias, float *y, float *pooled,
                                    int N, int H, int W, int Cin, int Cout, int act, void *stream);
 
+/* Does sq_conv2d_nhwc_fwd_f32 (pooled = 0) / sq_conv3x3_pool_fwd_f32 (pooled = 1) at wscale == 1 run the 32 -> 32 kernel with the
+ * filter held in registers (conv_r32_kernel) at this shape?  1 where K == 3, Cin == Cout == 32, act == SQ_ACT_RELU, H and W
+ * multiples of 16, every tensor below 2 GiB, and the plan is the 32-channel block with 32 staged channels (sq_conv_plan: at
+ * least 512 pixel tiles); switch SQ_CONV_R32 (0: never; read per call).  Same bits as the generic kernel, whose grid it walks
+ * (sq_conv_walk_plan describes both).  Host only, no HIP call. */
+int sq_conv_r32_takes_f32(int N, int H, int W, int Cin, int Cout, int K, int act, int pooled);
+
 /* last conv_layer of up0 + conv_layer_1x1 + prediction (unet.py:252-253,321): 3x3 conv Cin -> 16
  * + bias + act, then the 1x1 head (16 -> head_c <= 4, HWIO head_w (1,1,16,head_c)) and the argmax
  * mask in the epilogue; the 16-channel activation never reaches HBM.  mask may be NULL. */

@@ -186,6 +186,7 @@ SIGNATURES = {
     "sq_conv_packed_filter_elems_f32": (c_int64, [c_int] * 3),
     "sq_conv_pack_filter_f32": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
     "sq_conv_packed_takes_f32": (c_int, [c_int] * 6),
+    "sq_conv_r32_takes_f32": (c_int, [c_int] * 8),
     "sq_conv2d_packed_nhwc_fwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float, c_int, c_void_p]),
     "sq_conv3x3_pool_packed_fwd_f32": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
     "sq_conv3x3_first_block_fwd_f32": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),

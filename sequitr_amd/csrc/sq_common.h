@@ -26,6 +26,8 @@ int sq_plan_mosaic_splitk(int Nimg, int h, int w, int Cin, int Cout, int R, int 
 int sq_plan_f32_bn(int64_t ntiles, int Cout);
 bool sq_plan_f32_stage32(int bn, int KS, int KC, int Cin, bool concat);
 bool sq_plan_l0_takes(int mode, int cout, int act, int H, int W, bool concat, int head_c, bool pooled);
+// calls the 32 -> 32 filter-in-registers kernel (sq_conv_f32_r32.hip) takes from the generic <32,3,32,0> form
+bool sq_plan_r32_takes(int N, int H, int W, int Cin, int Cout, int K, int act, bool wscale1, bool concat, bool head, bool pooled);
 // persistent grids of the f32 inference kernels (sq_conv_f32_l0.hip, sq_conv_f32_v2.hip, sq_convt_f32_v2.hip): block b takes
 // item b, b + G, b + 2G, ...  The resident blocks per CU of every form and the grid G, shared by launch_l0 / launch_v2 /
 // launch_ct and sq_conv_walk_plan

@@ -26,3 +26,7 @@ struct SqConvEpi {
 // mode: 0 plain, 1 FIRST (x = the single-channel image), 2 UP (x = the skip tensor); cout: 16, or 32 for the plain form
 int sq_conv_l0_launch(int mode, const float *x, const float *w, const float *bias, float *y, int N, int H, int W,
                       int cout, int act, const SqConvEpi &epi, hipStream_t st);
+// the 32 -> 32 channel kernel of sq_conv_f32_r32.hip (plain, or + 2x2 max-pool when epi.pooled): returns SQ_L0_NOT_MINE when
+// sq_plan_r32_takes declines the call (the caller then launches the generic kernel), otherwise the launch status
+int sq_conv_r32_launch(const float *x, const float *w, const float *bias, float *y, int N, int H, int W, int Cin, int Cout,
+                       int K, float wscale, int act, const SqConvEpi &epi, hipStream_t st);

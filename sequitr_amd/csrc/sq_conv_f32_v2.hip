@@ -740,6 +740,10 @@ int sq_conv_mfma_v2(const float *x, const float *w, const float *bias, float *y,
         const int r = sq_conv_l0_launch(0, x, w, bias, y, N, H, W, Cout, act, epi, st);
         if (r != SQ_L0_NOT_MINE) return r;
     }
+    if (Cin == 32 && Cout == 32 && K == 3) {    // the filter-in-registers kernel (sq_conv_f32_r32.hip) where the plan is <32,3,32,0>
+        const int r = sq_conv_r32_launch(x, w, bias, y, N, H, W, Cin, Cout, K, wscale, act, epi, st);
+        if (r != SQ_L0_NOT_MINE) return r;
+    }
     if (Cin % 16 == 0)
         return K == 3 ? dispatch_bn<3, 16>(x, w, bias, y, N, H, W, Cin, Cout, wscale, act, epi, st)
                       : dispatch_bn<1, 16>(x, w, bias, y, N, H, W, Cin, Cout, wscale, act, epi, st);
@@ -785,6 +789,10 @@ extern "C" int sq_conv3x3_pool_fwd_f32(const float *x, const float *w, const flo
     epi.pooled = pooled;
     if (Cin == 16 && Cout == 16) {
         const int r = sq_conv_l0_launch(0, x, w, bias, y, N, H, W, 16, act, epi, reinterpret_cast<hipStream_t>(stream));
+        if (r != SQ_L0_NOT_MINE) return r;
+    }
+    if (Cin == 32 && Cout == 32) {
+        const int r = sq_conv_r32_launch(x, w, bias, y, N, H, W, Cin, Cout, 3, 1.0f, act, epi, reinterpret_cast<hipStream_t>(stream));
         if (r != SQ_L0_NOT_MINE) return r;
     }
     return dispatch_bn<3, 16>(x, w, bias, y, N, H, W, Cin, Cout, 1.0f, act, epi, reinterpret_cast<hipStream_t>(stream));

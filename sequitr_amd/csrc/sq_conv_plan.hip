@@ -68,6 +68,24 @@ bool sq_plan_l0_takes(int mode, int cout, int act, int H, int W, bool concat, in
     return true;
 }
 
+bool sq_plan_r32_takes(int N, int H, int W, int Cin, int Cout, int K, int act, bool wscale1, bool concat, bool head, bool pooled) {
+    // the 32 -> 32 ReLU layers on whole 16 x 16 tiles, where the plan is the generic kernel's 32-channel block with 32 staged
+    // channels (<32,3,32,0>: ntiles >= 512); the kernel walks that form's grid.  Both epilogues (plain, pooled) are on
+    (void)pooled;
+    if (K != 3 || Cin != 32 || Cout != 32 || !wscale1 || act != SQ_ACT_RELU || concat || head) return false;
+    if (N <= 0 || H <= 0 || W <= 0 || H % 16 != 0 || W % 16 != 0) return false;
+    const char *e = getenv("SQ_CONV_R32");                      // SQ_CONV_R32=0: A/B switch back to the generic kernel; read per
+    if (e && e[0] == '0') return false;                         // call: the parity tests flip it in-process
+    if ((size_t)N * H * W * 32 * 4 >= ((size_t)1 << 31)) return false;
+    const int bn = sq_plan_f32_bn(ntiles_of(N, H, W), Cout);
+    return bn == 32 && sq_plan_f32_stage32(bn, K, 16, Cin, concat);
+}
+
+// host-only query of the rule above for the plain (pooled = 0) and pooled entry points at wscale == 1
+extern "C" int sq_conv_r32_takes_f32(int N, int H, int W, int Cin, int Cout, int K, int act, int pooled) {
+    return sq_plan_r32_takes(N, H, W, Cin, Cout, K, act, true, false, false, pooled != 0) ? 1 : 0;
+}
+
 int sq_plan_l0_grid(int ntiles, int occ) {
     const int want = 256 * occ;
     return ntiles < want ? ntiles : want;

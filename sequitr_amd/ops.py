@@ -263,6 +263,14 @@ def conv_packed_takes(x_shape, w_shape):
     return bool(_lib.load().sq_conv_packed_takes_f32(N, H, W, Cin, w_shape[3], w_shape[0])) and w_shape[2] == Cin
 
 
+def conv_r32_takes(x_shape, w_shape, act="relu", pooled=False):
+    """does conv2d (conv3x3_pool: pooled=True) at wscale == 1 run the 32 -> 32 kernel with the filter held in registers at
+    this shape?  (sq_conv_r32_takes_f32, host only)"""
+    N, H, W, Cin = x_shape
+    return bool(_lib.load().sq_conv_r32_takes_f32(N, H, W, Cin, w_shape[3], w_shape[0], ACT[act], 1 if pooled else 0)) \
+        and w_shape[2] == Cin
+
+
 def _packed_filter(w, K, Cin, Cout, wscale, transform):
     """bf16 pack of the conv Cin -> Cout; transform: `w` is the FORWARD filter (K,K,Cout,Cin) of which this conv
     is the dgrad (taps rotated, channel roles swapped inside the pack kernel -- no separate transform pass)."""

@@ -12,6 +12,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "sequitr_amd", "csrc", "sq_conv_f32_v2.hip")
 WSRC = os.path.join(ROOT, "sequitr_amd", "csrc", "sq_conv_wgrad_f32.hip")
+RSRC = os.path.join(ROOT, "sequitr_amd", "csrc", "sq_conv_f32_r32.hip")
 WGRAD_VARIANTS = {
     "wg_base": [],
     "wg_noload": [("raw_buffer_load_b128(xrsrc, inb ? (unsigned)(xbase + xrel[sl]) : OOB, 0, 0)",
@@ -42,6 +43,7 @@ for _k in (24, 48, 96):
 
 def build():
     _build(SRC, "sq_conv_f32_v2.o", VARIANTS)
+    _build(RSRC, "sq_conv_f32_r32.o", R32_VARIANTS)
     _build(WSRC, "sq_conv_wgrad_f32.o", WGRAD_VARIANTS)
 
 
@@ -93,16 +95,38 @@ VARIANTS["timeline"] = [
 ]
 
 
-def timeline():
+# the same stamps in conv_r32_kernel (sq_conv_f32_r32.hip): python tools/conv_ablation.py timeline r32
+_RSTAMP = ("if (a.dbg && vb < 32 && lane == 0 && it < 64) a.dbg[(((size_t)vb * 4 + wv) * 64 + it) * 6 + %d] = "
+           "(long long)__builtin_readcyclecounter();\n")
+R32_VARIANTS = {"timeline_r32": [
+    ('#include "sq_common.h"\n', '#include "sq_common.h"\n#include <stdlib.h>\n'),
+    ("    int gx, gy, gn;  ", "    long long *dbg;\n    int gx, gy, gn;  "),
+    ("    R32Args a = {};\n", "    R32Args a = {};\n    if (const char *e_ = getenv(\"SQ_DBG_PTR\")) a.dbg = (long long *)strtoull(e_, 0, 16);\n"),
+    ("        nxt = advance(cur);\n", "        nxt = advance(cur);\n        " + _RSTAMP % 0),
+    ("        pa0 = acc[0];\n", "        " + _RSTAMP % 1 + "        pa0 = acc[0];\n"),
+    ("        __builtin_amdgcn_s_waitcnt(0x0F70);                         // the prefetch has landed",
+     "        __builtin_amdgcn_s_waitcnt(0x0F70);\n        " + _RSTAMP % 2 + "        // the prefetch has landed"),
+    # the stores ride in the next MFMA phase: "epilogue" (T4 - T3) is empty by construction
+    ("            commit_halo();\n            __syncthreads();\n        }\n        cur = nxt;\n",
+     "            commit_halo();\n            __builtin_amdgcn_s_waitcnt(0);\n        }\n        " + _RSTAMP % 3 + "        " + _RSTAMP % 4 +
+     "        if (has_next) __syncthreads();\n        " + _RSTAMP % 5 + "        cur = nxt;\n"),
+]}
+
+
+def timeline(which="v2"):
     sys.path.insert(0, ROOT)
     import numpy as np
     import torch
     from sequitr_amd import _lib
-    _lib.LIB_PATH = os.path.join(ROOT, "tools", "_exp", "timeline", "libsequitr_hip.so")
+    _lib.LIB_PATH = os.path.join(ROOT, "tools", "_exp", "timeline" if which == "v2" else "timeline_r32", "libsequitr_hip.so")
     dbg = torch.zeros((32 * 4 * 64 * 6,), dtype=torch.int64, device="cuda:0")
     os.environ["SQ_DBG_PTR"] = "%x" % dbg.data_ptr()
     from sequitr_amd import ops
-    for (n, h, ci, co) in [(32, 128, 64, 64), (32, 64, 128, 128), (32, 32, 256, 256)]:       # the <64,3,16> layers
+    if which == "v2":
+        os.environ["SQ_CONV_R32"] = "0"                          # the 32 -> 32 item is the generic <32,3,32,0> kernel's
+    # the <64,3,16> layers and the <32,3,32,0> layer of level 1; r32: that layer on conv_r32_kernel
+    shapes = [(32, 128, 64, 64), (32, 64, 128, 128), (32, 32, 256, 256), (32, 256, 32, 32)]
+    for (n, h, ci, co) in shapes if which == "v2" else shapes[3:]:
         x = torch.randn(n, h, h, ci, device="cuda:0")
         w = torch.randn(3, 3, ci, co, device="cuda:0") * 0.05
         b = torch.zeros(co, device="cuda:0")
@@ -173,7 +197,7 @@ if __name__ == "__main__":
     if sys.argv[1] == "build":
         build()
     elif sys.argv[1] == "timeline":
-        timeline()
+        timeline(*sys.argv[2:3])
     elif sys.argv[1] == "run":
         names = sys.argv[2:] or (["prod"] + list(VARIANTS) + list(WGRAD_VARIANTS))
         for v in names:   # one process per variant: the library is loaded once

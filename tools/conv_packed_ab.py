@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
-"""A/B of the packed 64-channel-block f32 conv (conv_mfma_f32_packed_kernel) against the unpacked kernel (SQ_CONV_PACKED=0, read
-per call) on the same tensors, for the ten <64,3,16> launches of the inference workload (32 tiles of 512 x 512, filters
-16-32-64-128-256).  HIP events round `--calls` launches of one arm; the arms alternate measurement by measurement, so clock and
+"""A/B of an f32 inference conv kernel behind an environment switch that is read per call against the kernel the switch falls
+back to, on the same tensors.  Default: the packed 64-channel-block conv (conv_mfma_f32_packed_kernel) against the unpacked kernel
+(SQ_CONV_PACKED=0) for the ten <64,3,16> launches of the inference workload (32 tiles of 512 x 512, filters 16-32-64-128-256).
+`--switch SQ_CONV_R32 --shapes name:entry:N:H:Cin:Cout,...` times another switch on another shape list (entry: conv2d or pool);
+the arm with the switch on is called "packed" in the output whatever the switch, the arm with it at 0 "unpacked".  HIP events round `--calls` launches of one arm; the arms alternate measurement by measurement, so clock and
 neighbour drift hits both alike.  Per arm: median and (max - min) / median of the per-call time.  A layer counts as faster only
 when the packed median is below the unpacked one by more than the larger of the two spreads.
   python tools/conv_packed_ab.py [--out profiles/conv_packed_ab.json] [--reps 15] [--calls 30] [--lib other/libsequitr_hip.so]
+  python tools/conv_packed_ab.py --switch SQ_CONV_R32 --shapes up1/conv1:conv2d:32:256:32:32,down1/conv2:pool:32:256:32:32 \
+         --out profiles/conv_r32_ab.json
 --lib times another build of the library (an experiment build of sq_conv_f32_packed.hip, say -DSQ_PK_RING=6)."""
 import argparse
 import json
@@ -32,21 +36,30 @@ def main():
     ap.add_argument("--calls", type=int, default=30, help="launches per event pair (10 leave the 150 us layers a 3-5 %% spread)")
     ap.add_argument("--warm", type=int, default=100, help="warm-up launches per layer (the clocks settle)")
     ap.add_argument("--lib", default=None, help="another build of libsequitr_hip.so to time")
+    ap.add_argument("--switch", default="SQ_CONV_PACKED", help="the environment switch of the kernel under test (0: the other kernel)")
+    ap.add_argument("--shapes", default=None, help="name:entry:N:H:Cin:Cout,... instead of the ten 64-channel-block layers")
     a = ap.parse_args()
+    layers = LAYERS
+    if a.shapes:
+        layers = [(f[0], f[1]) + tuple(int(v) for v in f[2:]) for f in (s.split(":") for s in a.shapes.split(","))]
+        assert all(len(l) == 6 and l[1] in ("conv2d", "pool") for l in layers), "--shapes: name:entry:N:H:Cin:Cout"
     from sequitr_amd import _lib
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
     from sequitr_amd import ops
-    os.environ.pop("SQ_CONV_PACKED", None)
+    os.environ.pop(a.switch, None)
     dev = "cuda:0"
     rows = []
-    for name, entry, n, h, ci, co in LAYERS:
+    for name, entry, n, h, ci, co in layers:
         g = torch.Generator(device="cpu").manual_seed(ci * 1000 + co + h)
         x = torch.randn((n, h, h, ci), generator=g).to(dev)
         w = (torch.randn((3, 3, ci, co), generator=g) / float(np.sqrt(9 * ci))).to(dev)
         b = (torch.randn((co,), generator=g) * 0.1).to(dev)
         pk = ops.pack_filter(w)
-        taken = ops.conv_packed_takes(tuple(x.shape), tuple(w.shape))
+        if a.switch == "SQ_CONV_R32":
+            taken = ops.conv_r32_takes(tuple(x.shape), tuple(w.shape), pooled=entry == "pool")
+        else:
+            taken = ops.conv_packed_takes(tuple(x.shape), tuple(w.shape))
 
         def call():
             if entry == "pool":
@@ -55,9 +68,9 @@ def main():
 
         def arm(packed):
             if packed:
-                os.environ.pop("SQ_CONV_PACKED", None)
+                os.environ.pop(a.switch, None)
             else:
-                os.environ["SQ_CONV_PACKED"] = "0"
+                os.environ[a.switch] = "0"
 
         arm(True)
         yp = call()
@@ -96,8 +109,10 @@ def main():
             "FASTER" if gain > noise else "not beyond spread", "" if same else "  OUTPUTS DIFFER"), flush=True)
     tot_p = sum(r["packed"]["median_us"] for r in rows)
     tot_u = sum(r["unpacked"]["median_us"] for r in rows)
-    out = {"what": "packed vs SQ_CONV_PACKED=0 on the same tensors, HIP events round %d calls, arms alternating, %d measurements "
-                   "per arm after %d warm-up launches; spread = (max - min) / median" % (a.calls, a.reps, a.warm),
+    out = {"what": "%s unset ('packed') vs %s=0 ('unpacked') on the same tensors, HIP events round %d calls, arms alternating, %d "
+                   "measurements per arm after %d warm-up launches; spread = (max - min) / median" % (
+                       a.switch, a.switch, a.calls, a.reps, a.warm),
+           "switch": a.switch,
            "device": torch.cuda.get_device_name(0), "library": os.path.relpath(_lib.LIB_PATH, ROOT), "layers": rows,
            "sum_of_medians_us": {"packed": round(tot_p, 1), "unpacked": round(tot_u, 1)}}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
