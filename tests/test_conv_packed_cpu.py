@@ -81,6 +81,99 @@ def test_takes_follows_the_plan_and_the_switch(monkeypatch):
     assert lib.sq_conv_packed_takes_f32(2, 256, 256, 32, 64, 3) == 1
 
 
+@pytest.mark.parametrize("c", pc.PACKED_WALKS, ids=pc.packed_case_id)
+def test_walk_cases_reach_the_regimes_they_declare(c, monkeypatch):
+    """every case of the walk sweep (tests/test_gpu_conv_packed.py): the tags it declares are the ones the walk plan and the
+    shape give, the 64-channel-block plan and the packed kernel take it, and the walk is the unpacked kernel's"""
+    monkeypatch.delenv("SQ_CONV_PACKED", raising=False)
+    lib = _lib.load()
+    assert set(c.tags) == pc.packed_tags(c)
+    on64, p = pc.on_64_blocks(c.form, c.N, c.H, c.W, c.Cin, c.Cout, c.act)
+    assert on64, p
+    assert lib.sq_conv_packed_takes_f32(c.N, c.H, c.W, c.Cin, c.Cout, 3) == 1
+    assert c.form in (wc.PLAIN, wc.POOL) and (c.form == wc.PLAIN or (c.H % 2 == 0 and c.W % 2 == 0))
+    assert c.N * c.H * c.W * max(c.Cin, c.Cout) * 4 <= 140e6            # no tensor much over 130 MB
+    tiles_x, tiles_y = wc.tiles_xy(c)
+    counts = [wc.block_count(p, b) for b in range(p["G"])]
+    assert (min(counts), max(counts), sum(counts)) == (p["tmin"], p["tmax"], p["items"]) and p["items"] == c.N * tiles_x * tiles_y
+    assert p["G"] == (p["gn"] * tiles_y + p["gy"]) * tiles_x + p["gx"]
+    for b in range(p["G"]):
+        wc.carries_of_block(p, tiles_x, tiles_y, b)                     # asserts every step lands on tile b + k G
+    monkeypatch.setenv("SQ_CONV_PACKED", "0")                           # the switch changes the kernel, never the walk
+    assert lib.sq_conv_packed_takes_f32(c.N, c.H, c.W, c.Cin, c.Cout, 3) == 0
+    assert pc.packed_walk(c) == p
+
+
+def test_walk_table_reaches_every_needed_regime():
+    """a regime that loses its last case fails here"""
+    carried = {}
+    for c in pc.PACKED_WALKS:
+        for t in c.tags:
+            carried.setdefault(t, []).append(pc.packed_case_id(c))
+    assert set(carried) == pc.PACKED_NEEDED, (pc.PACKED_NEEDED - set(carried), set(carried) - pc.PACKED_NEEDED)
+    assert len({pc.packed_case_id(c) for c in pc.PACKED_WALKS}) == len(pc.PACKED_WALKS)
+    nf = pc.NONFINITE_CASE
+    assert nf.act == "relu" and nf.bias == "rand" and pc.packed_walk(nf)["tmax"] >= 2 and nf.H % 2 == 0 and nf.W % 2 == 0
+    assert pc.on_64_blocks(wc.PLAIN, nf.N, nf.H, nf.W, nf.Cin, nf.Cout, "relu")[0]      # it also runs plain
+
+
+def test_the_oracle_stores_a_non_finite_pre_activation_under_relu_as_the_kernels_do():
+    """oracle/sq_oracle.c applies ReLU as v > 0.0f ? v : 0.0f: a NaN or -inf pre-activation gives +0, +inf stays +inf, as
+    fmaxf(v, 0) on the kernels' fast paths.  The non-finite GPU tests still use it only where the whole neighbourhood is finite;
+    pc.neighbourhoods marks exactly the outputs a planted value can reach."""
+    from oracle import c_oracle as co
+    x = np.zeros((1, 6, 6, 16), np.float32)
+    x[0, 1, 1, 0], x[0, 4, 4, 15], x[0, 1, 4, 3] = np.nan, np.inf, -np.inf
+    w = np.ones((3, 3, 16, 4), np.float32)
+    w[..., 1] = -1.0
+    y = co.conv2d(x, w, np.full(4, 0.5, np.float32), act="relu")
+    finite, has_nan = (m.numpy() for m in pc.neighbourhoods(x))
+    assert has_nan.sum() == 9 and (~finite).sum() == 27
+    assert not np.isnan(y).any() and not np.signbit(y).any()
+    assert (y[has_nan].view(np.uint32) == 0).all()                     # NaN -> +0
+    assert np.isposinf(y[0, 3:6, 3:6, 0]).all() and (y[0, 3:6, 3:6, 1].view(np.uint32) == 0).all()     # +inf stays, -inf -> +0
+    assert (y[0, 0:3, 3:6, 0].view(np.uint32) == 0).all() and np.isposinf(y[0, 0:3, 3:6, 1]).all()
+    assert (y[finite] == 0.5).all()
+    assert np.isnan(co.conv2d(x, w, None, act=None)[has_nan]).all()     # the NaN is there before the activation
+
+
+def test_a_mismatch_names_its_block_and_its_place_in_the_walk():
+    """the report of the GPU sweeps (pc.mismatch), on arrays made to differ in one known element"""
+    c = pc.PACKED_WALKS[0]
+    p, (tiles_x, tiles_y) = pc.packed_walk(c), wc.tiles_xy(c)
+    assert (p["G"], p["tmin"], p["tmax"]) == (87, 2, 3)
+    t = 5 + 2 * p["G"]                                                  # the third tile of block 5
+    n, tyi, txi = t // (tiles_x * tiles_y), (t // tiles_x) % tiles_y, t % tiles_x
+    b, pos, cnt = wc.tile_position(p, tiles_x, tiles_y, n, tyi, txi)
+    assert (b, pos, cnt) == (5, 2, 3)
+    ref = np.zeros((c.N, c.H, c.W, c.Cout), np.float32)
+    assert pc.mismatch(ref.copy(), ref, p, c.H, c.W) is None
+    got = ref.copy()
+    y, x, ch = 16 * tyi + 3, 16 * txi + 15, 200
+    got[n, y, x, ch] = 1.0
+    msg = pc.mismatch(got, ref, p, c.H, c.W)
+    assert "y: 1 of %d elements differ" % ref.size in msg, msg
+    assert "(n %d, y %d, x %d, channel %d)" % (n, y, x, ch) in msg, msg
+    assert "tile (n %d, ty %d, tx %d), item %d of %d of block %d (of 87 blocks), channel block 3" % (n, tyi, txi, pos, cnt, b) in msg, msg
+    assert "[((2, 3), 1)]" in msg, msg
+    got[n, y, x, ch] = -0.0                                             # equal as floats, not in bits: still a mismatch
+    assert "1 of %d elements differ" % ref.size in pc.mismatch(got, ref, p, c.H, c.W)
+    # a pooled pixel (y, x) lies in the tile of (2 y, 2 x); the 32 -> 32 kernel's channel blocks are 32 wide
+    got = np.zeros((c.N, c.H // 2, c.W // 2, 32), np.float32)
+    ref = got.copy()
+    got[n, 8 * tyi + 7, 8 * txi, 31] = np.nan
+    msg = pc.mismatch(got, ref, p, c.H, c.W, name="pooled", bn=32)
+    assert "tile (n %d, ty %d, tx %d), item 2 of 3 of block 5 (of 87 blocks), channel block 0" % (n, tyi, txi) in msg, msg
+    # the last block of the uneven walk: two tiles
+    t = 86 + p["G"]
+    n, tyi, txi = t // (tiles_x * tiles_y), (t // tiles_x) % tiles_y, t % tiles_x
+    assert wc.tile_position(p, tiles_x, tiles_y, n, tyi, txi) == (86, 1, 2)
+    ref = np.zeros((c.N, c.H, c.W, c.Cout), np.float32)
+    got = ref.copy()
+    got[n, 16 * tyi, 16 * txi, 0] = 2.0
+    assert "item 1 of 2 of block 86 (of 87 blocks), channel block 0" in pc.mismatch(got, ref, p, c.H, c.W)
+
+
 @pytest.mark.parametrize("Cin", [16, 48])
 @pytest.mark.parametrize("Cout", [64, 192])
 def test_pack_order_is_a_permutation(Cin, Cout):

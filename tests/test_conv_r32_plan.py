@@ -57,6 +57,52 @@ def test_plans_are_the_generic_kernels_with_the_switch_on_and_off(c, monkeypatch
     assert w["items"] == c.N * (c.H // 16) * (c.W // 16) and w["items"] >= 512
 
 
+@pytest.mark.parametrize("c", rc.R32_WALKS, ids=rc.walk_case_id)
+def test_walk_cases_reach_the_regimes_they_declare(c, monkeypatch):
+    """every case of the walk sweep (tests/test_gpu_conv_r32.py): the tags it declares are the ones the walk plan and the shape
+    give, the kernel takes it, and plan and walk are the generic kernel's with the switch on and off"""
+    assert set(c.tags) == rc.r32_tags(c)
+    assert rc.takes(c.N, c.H, c.W, pooled=c.pooled) == 1
+    assert c.N * c.H * c.W * 32 * 4 <= 140e6                           # no tensor much over 130 MB
+    on = (rc.walk(c.N, c.H, c.W, c.pooled), rc.plan(c.N, c.H, c.W, c.pooled))
+    monkeypatch.setenv("SQ_CONV_R32", "0")
+    assert rc.takes(c.N, c.H, c.W, pooled=c.pooled) == 0
+    off = (rc.walk(c.N, c.H, c.W, c.pooled), rc.plan(c.N, c.H, c.W, c.pooled))
+    assert on == off
+    w, p = on
+    assert w["kernel"] == wc.V2 and w["cblocks"] == 1 and p == dict(bn=32, kc=32, gy=1, s=1, l0=0)
+    tiles_x, tiles_y = c.W // 16, c.H // 16
+    assert w["items"] == c.N * tiles_x * tiles_y and w["items"] >= 512
+    counts = [wc.block_count(w, b) for b in range(w["G"])]
+    assert (min(counts), max(counts), sum(counts)) == (w["tmin"], w["tmax"], w["items"])
+    assert w["G"] == (w["gn"] * tiles_y + w["gy"]) * tiles_x + w["gx"]
+    for b in range(w["G"]):
+        wc.carries_of_block(w, tiles_x, tiles_y, b)                    # asserts every step lands on tile b + k G
+    if "tmin=1<tmax/%s" % ("pooled" if c.pooled else "plain") in c.tags:
+        assert sorted(set(counts)) == [1, 2]
+    if tiles_x == 2:                                                   # an odd stride: the column carries at every other step
+        assert w["gx"] == 1
+
+
+def test_walk_table_reaches_every_needed_regime():
+    """a regime that loses its last case fails here; walks of 1, 2, 3 and 4 or more tiles all occur"""
+    carried = {}
+    for c in rc.R32_WALKS:
+        for t in c.tags:
+            carried.setdefault(t, []).append(rc.walk_case_id(c))
+    assert set(carried) == rc.R32_NEEDED, (rc.R32_NEEDED - set(carried), set(carried) - rc.R32_NEEDED)
+    assert len({rc.walk_case_id(c) for c in rc.R32_WALKS}) == len(rc.R32_WALKS)
+    for pooled in (False, True):
+        lengths = set()
+        for c in rc.R32_WALKS:
+            if c.pooled == pooled:
+                w = rc.walk(c.N, c.H, c.W, pooled)
+                lengths |= {wc.block_count(w, b) for b in range(w["G"])}
+        assert {1, 2, 3} <= lengths and max(lengths) >= 4, lengths
+    N, H, W = rc.NONFINITE_SHAPE
+    assert {c.bias for c in rc.R32_WALKS if (c.N, c.H, c.W) == (N, H, W)} == {"rand"} and rc.walk(N, H, W, False)["tmax"] >= 2
+
+
 def test_the_tables_reach_their_regimes():
     """(2, 256, 256): one tile per block; (5, 256, 272): 454 blocks of 2 or 3 tiles, a non-square tile grid, and walks with a step
     that carries nothing, one that carries the column into the row and one that carries the row into the image"""

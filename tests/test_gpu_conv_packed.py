@@ -3,13 +3,17 @@ fragment pack, halo double-buffered, one barrier per item) against the unpacked 
 SQ_CONV_PACKED=0, which the existing sweeps pin to the oracle and to fp64.  Every comparison is torch.equal: the packed form keeps
 every output's fmaf chain.  Each case first asserts, through sq_conv_walk_plan, that the 64-channel-block plan takes its shape
 (ntiles x Cout / 64 >= 512) and that the packed kernel would take the call -- a smaller shape falls to narrower blocks and proves
-nothing.  The device pack itself is compared bit for bit with the numpy statement of its order (tests/conv_packed_cases.py)."""
+nothing.  The device pack itself is compared bit for bit with the numpy statement of its order (tests/conv_packed_cases.py).
+The walk sweep (pc.PACKED_WALKS) compares the packed kernel itself with the C oracle, on outputs between sentinel bands: the two
+kernels share the walk and the epilogue text, so a fault common to both shows only there."""
 import os
+import zlib
 
 import numpy as np
 import pytest
 import torch
 
+from oracle import c_oracle as co
 from sequitr_amd import _lib, ops
 from sequitr_amd.networks.unet import UNet2D, init_unet_weights
 from tests import conv_packed_cases as pc
@@ -102,6 +106,123 @@ def test_pool_epilogue(N, H, W, Cin, Cout, act):
         ry, rp = ops.conv3x3_pool(x, w, b, act=act, pack=pk)
     assert torch.equal(y, ry) and torch.equal(pooled, rp)
     assert torch.equal(rp, torch.nn.functional.max_pool2d(ry.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1))
+
+
+# ---- the walk sweep: every case of pc.PACKED_WALKS against the C oracle, on guarded outputs ------------------------------------
+def _launch(x, w, wp, b, y, p, act):
+    """one call of the packed entry points (the pooled one where `p` is given) into the guarded outputs; asserts their bands"""
+    N, H, W, Cin = x.shape
+    Cout = w.shape[3]
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    bp = b.data_ptr() if b is not None else None
+    if p is not None:
+        _lib.check(lib.sq_conv3x3_pool_packed_fwd_f32(x.data_ptr(), w.data_ptr(), wp.data_ptr(), bp, y.t.data_ptr(), p.t.data_ptr(),
+                                                      N, H, W, Cin, Cout, ops.ACT[act], st), "sq_conv3x3_pool_packed_fwd_f32")
+    else:
+        _lib.check(lib.sq_conv2d_packed_nhwc_fwd_f32(x.data_ptr(), w.data_ptr(), wp.data_ptr(), bp, y.t.data_ptr(), N, H, W, Cin,
+                                                     Cout, 3, 1.0, ops.ACT[act], st), "sq_conv2d_packed_nhwc_fwd_f32")
+    torch.cuda.synchronize()
+    assert y.bands_intact(), "a store outside y"
+    assert p is None or p.bands_intact(), "a store outside pooled"
+
+
+def _run_guarded(x, w, wp, b, act, pooled, runs=1):
+    """(y, pooled or None): `runs` calls in a row into the same guarded outputs, every one with the first one's bits"""
+    N, H, W, _ = x.shape
+    Cout = w.shape[3]
+    y = pc.Guarded(N, H, W, Cout)
+    p = pc.Guarded(N, H // 2, W // 2, Cout) if pooled else None
+    _launch(x, w, wp, b, y, p, act)
+    assert y.all_stored() and (p is None or p.all_stored()), "an output element never stored"
+    if runs > 1:
+        first = (y.t.clone(), p.t.clone() if pooled else None)
+        for i in range(1, runs):
+            _launch(x, w, wp, b, y, p, act)
+            assert torch.equal(y.t, first[0]) and (not pooled or torch.equal(p.t, first[1])), "run %d differs from the first" % i
+    return y.t, (p.t if pooled else None)
+
+
+def _seed(c):
+    return zlib.crc32(pc.packed_case_id(c).encode())
+
+
+_shared = {}
+
+
+def _walk_case(c):
+    """inputs on the device and the oracle's output of a case, computed once and left unchanged"""
+    if c not in _shared:
+        x, w, b = _inputs(c.N, c.H, c.W, c.Cin, c.Cout, _seed(c))
+        b = b if c.bias else None
+        ref = co.conv2d(x.cpu().numpy(), w.cpu().numpy(), None if b is None else b.cpu().numpy(), act=c.act)
+        _shared[c] = (x, w, b, ref)
+    return _shared[c]
+
+
+def _max_pool(y):
+    return torch.nn.functional.max_pool2d(y.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("c", pc.PACKED_WALKS, ids=pc.packed_case_id)
+def test_walks_equal_the_c_oracle(c, monkeypatch):
+    """Bit for bit against oracle/sq_oracle.c and against the unpacked kernel, at the walks the table declares (checked on the
+    CPU by tests/test_conv_packed_cpu.py): odd chunk counts, channel blocks beyond the first on walks of several tiles, walks of
+    four and five tiles, every carry of the stride, ragged last tiles of one and fifteen pixels, single rows and columns of tiles,
+    the pooled epilogue on ragged shapes.  The outputs lie between sentinel bands; the call runs twice into the same buffers."""
+    monkeypatch.delenv("SQ_CONV_PACKED", raising=False)
+    p = _takes(c.form, c.N, c.H, c.W, c.Cin, c.Cout, c.act)
+    pooled = c.form == wc.POOL
+    x, w, b, ref = _walk_case(c)
+    pk = ops.pack_filter(w)
+    y, pl = _run_guarded(x, w, pk.wp, b, c.act, pooled, runs=2)
+    msg = pc.mismatch(y.cpu().numpy(), ref, p, c.H, c.W)
+    assert msg is None, "packed kernel against the oracle [%s]\n%s" % (pc.packed_case_id(c), msg)
+    with unpacked():
+        assert not ops.conv_packed_takes((c.N, c.H, c.W, c.Cin), (3, 3, c.Cin, c.Cout))
+        ry, rp = _run_guarded(x, w, pk.wp, b, c.act, pooled)
+    assert torch.equal(y, ry)
+    if pooled:
+        assert torch.equal(pl, _max_pool(y))
+        assert torch.equal(pl, rp)
+
+
+@pytest.mark.parametrize("pooled", [False, True], ids=["plain", "pool"])
+def test_non_finite_activations(pooled, monkeypatch):
+    """NaN, +inf and -inf in x (pc.nonfinite_plants: a tile's first and last pixel, halo pixels of the ragged border tiles, image
+    corners, the first and the last channel) at 2 x 250 x 278, 32 -> 128, ReLU with a bias, three tiles per block.  The packed and
+    the unpacked kernel agree: NaN at the same outputs, the same bits everywhere else.  Both store a NaN pre-activation as +0 under
+    ReLU -- fmaxf(v, 0) on whole tiles, v > 0 ? v : 0 on partial ones -- so no NaN is left, and every output whose neighbourhood
+    holds a NaN is +0.  Wherever the whole 3x3 x Cin neighbourhood is finite the output equals the oracle bit for bit.
+    The oracle itself applies ReLU as v > 0.0f ? v : 0.0f: a NaN or -inf pre-activation gives +0, +inf stays +inf
+    (tests/test_conv_packed_cpu.py pins that); its outputs beside non-finite inputs are not relied on here."""
+    monkeypatch.delenv("SQ_CONV_PACKED", raising=False)
+    c = pc.NONFINITE_CASE
+    p = _takes(wc.POOL if pooled else wc.PLAIN, c.N, c.H, c.W, c.Cin, c.Cout, "relu")
+    assert p["tmax"] >= 2
+    x, w, b = _inputs(c.N, c.H, c.W, c.Cin, c.Cout, _seed(c) + 1)
+    xh = x.cpu()
+    for (n, yy, xx, ch, v) in pc.nonfinite_plants(c.N, c.H, c.W, c.Cin):
+        xh[n, yy, xx, ch] = v
+    x = xh.cuda()
+    finite, has_nan = pc.neighbourhoods(xh)
+    assert 0 < int(has_nan.sum()) < int((~finite).sum()) < 200
+    pk = ops.pack_filter(w)
+    y, pl = _run_guarded(x, w, pk.wp, b, "relu", pooled, runs=2)
+    with unpacked():
+        ry, rp = _run_guarded(x, w, pk.wp, b, "relu", pooled)
+    nan = torch.isnan(y)
+    assert torch.equal(nan, torch.isnan(ry))
+    assert torch.equal(y.view(torch.int32)[~nan], ry.view(torch.int32)[~nan])
+    assert not bool(nan.any())
+    yh = y.cpu()
+    assert bool((yh[has_nan].view(torch.int32) == 0).all()), "a NaN pre-activation not stored as +0"
+    assert bool(torch.isinf(yh[~finite]).any())                       # the infinities did reach outputs
+    ref = co.conv2d(xh.numpy(), w.cpu().numpy(), b.cpu().numpy(), act="relu")
+    got = np.where(finite.numpy()[..., None], yh.numpy(), ref)
+    msg = pc.mismatch(got, ref, p, c.H, c.W)
+    assert msg is None, "outputs with a finite neighbourhood against the oracle\n%s" % msg
+    if pooled:
+        assert torch.equal(pl, _max_pool(y)) and torch.equal(pl, rp)
 
 
 @pytest.mark.parametrize("Cin", [16, 48])

@@ -2,7 +2,8 @@
 tensors -- the same call with SQ_CONV_R32=0 (read per call), which the existing sweeps pin to the C oracle.  Every comparison is
 torch.equal: the kernel keeps every output's fmaf chain.  Each case first asserts through sq_conv_r32_takes_f32 that the kernel
 takes the call, so that a silent fall-back cannot make the comparison vacuous.  Outputs are written between sentinel-filled guard
-bands one image row wide, and the bands are checked afterwards: a wrong store bound must not be repaired by a neighbour."""
+bands one image row wide, and the bands are checked afterwards: a wrong store bound must not be repaired by a neighbour.
+The walk sweep (rc.R32_WALKS) compares the kernel itself with the C oracle at every walk length and on degenerate tile grids."""
 import os
 import zlib
 
@@ -14,11 +15,11 @@ from oracle import c_oracle as co
 from sequitr_amd import _lib, ops
 from sequitr_amd.networks.unet import GraphedPredict, UNet2D, init_unet_weights
 from tests import conv_r32_cases as rc
+from tests.conv_packed_cases import SENTINEL, Guarded, mismatch, neighbourhoods, nonfinite_plants
 
 pytestmark = pytest.mark.gpu
 
 C = 32
-SENTINEL = -12345.678
 
 
 class generic(object):
@@ -54,28 +55,16 @@ def _inputs(N, H, W, bias, weights, key):
     return x, w, (b if bias else None)
 
 
-class Guarded(object):
-    """an (N, H, W, C) tensor inside sentinel bands of one image row (W * C floats) each"""
-
-    def __init__(self, N, H, W):
-        self.band = W * C
-        self.buf = torch.full((N * H * W * C + 2 * self.band,), SENTINEL, dtype=torch.float32, device="cuda")
-        self.t = self.buf[self.band:self.band + N * H * W * C].view(N, H, W, C)
-
-    def bands_intact(self):
-        s = torch.tensor(SENTINEL, dtype=torch.float32, device="cuda")
-        return bool((self.buf[:self.band] == s).all()) and bool((self.buf[-self.band:] == s).all())
-
-
-def _run(x, w, b, pooled, act="relu", wscale=1.0):
-    """(y, pooled or None) through the C entry points on guarded outputs; asserts the bands afterwards"""
+def _run(x, w, b, pooled, act="relu", wscale=1.0, into=None):
+    """(y, pooled or None) through the C entry points on guarded outputs; asserts the bands afterwards.  into: the (y, pooled)
+    Guarded buffers of an earlier call, written again"""
     N, H, W, _ = x.shape
     lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
-    y = Guarded(N, H, W)
+    y = into[0] if into else Guarded(N, H, W)
     bp = b.data_ptr() if b is not None else None
     if pooled:
         assert wscale == 1.0
-        p = Guarded(N, H // 2, W // 2)
+        p = into[1] if into else Guarded(N, H // 2, W // 2)
         _lib.check(lib.sq_conv3x3_pool_fwd_f32(x.data_ptr(), w.data_ptr(), bp, y.t.data_ptr(), p.t.data_ptr(), N, H, W, C, C,
                                                ops.ACT[act], st), "sq_conv3x3_pool_fwd_f32")
     else:
@@ -158,6 +147,98 @@ def test_fallbacks_run_the_generic_kernel(H, act, wscale):
         with generic():
             ry, rp = _run(x, w, b, True, act=act)
         assert torch.equal(y, ry) and torch.equal(p, rp)
+
+
+# ---- the walk sweep: every case of rc.R32_WALKS against the C oracle -----------------------------------------------------------
+def _walk_inputs(N, H, W, bias, key):
+    x, w, b = _inputs(N, H, W, bias, "normal", key)
+    x[:, ::7, ::5, ::3] = -0.0                                   # negative zeros in the activations
+    return x, w, b
+
+
+_walks = {}
+
+
+def _walk_case(c):
+    """inputs on the host and on the device and the oracle's output of a case, computed once and left unchanged"""
+    if c not in _walks:
+        x, w, b = _walk_inputs(c.N, c.H, c.W, c.bias, rc.walk_case_id(c))
+        ref = co.conv2d(x.numpy(), w.numpy(), None if b is None else b.numpy(), act="relu")
+        _walks[c] = ((x.cuda(), w.cuda(), None if b is None else b.cuda()), ref)
+    return _walks[c]
+
+
+def _run_twice(x, w, b, pooled):
+    """(y, pooled or None) of two calls in a row into the same guarded outputs, the second with the first one's bits"""
+    N, H, W, _ = x.shape
+    bufs = (Guarded(N, H, W), Guarded(N, H // 2, W // 2) if pooled else None)
+    y, p = _run(x, w, b, pooled, into=bufs)
+    first = (y.clone(), p.clone() if pooled else None)
+    y, p = _run(x, w, b, pooled, into=bufs)
+    assert torch.equal(y, first[0]) and (not pooled or torch.equal(p, first[1])), "the second run differs from the first"
+    return y, p
+
+
+def _max_pool(y):
+    return torch.nn.functional.max_pool2d(y.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("c", rc.R32_WALKS, ids=rc.walk_case_id)
+def test_walks_equal_the_c_oracle(c):
+    """Bit for bit against oracle/sq_oracle.c and against the generic kernel, at the walks the table declares (checked on the CPU
+    by tests/test_conv_r32_plan.py): blocks of one tile beside blocks of two, walks of three, four and five tiles -- the stores of
+    a tile ride in the next tile's MFMA phase, only the last has an epilogue of its own -- every carry of the stride, tile grids
+    one and two tiles wide and one tile high.  The call runs twice into the same guarded buffers."""
+    (x, w, b), ref = _walk_case(c)
+    assert rc.takes(c.N, c.H, c.W, pooled=c.pooled) == 1
+    p = rc.walk(c.N, c.H, c.W, c.pooled)
+    y, pl = _run_twice(x, w, b, c.pooled)
+    msg = mismatch(y.cpu().numpy(), ref, p, c.H, c.W, bn=C)
+    assert msg is None, "conv_r32_kernel against the oracle [%s]\n%s" % (rc.walk_case_id(c), msg)
+    with generic():
+        assert rc.takes(c.N, c.H, c.W, pooled=c.pooled) == 0
+        ry, rp = _run(x, w, b, c.pooled)
+    assert torch.equal(y, ry)
+    if c.pooled:
+        assert torch.equal(pl, _max_pool(y))
+        assert torch.equal(pl, rp)
+
+
+@pytest.mark.parametrize("pooled", [False, True], ids=["plain", "pool"])
+def test_non_finite_activations(pooled):
+    """NaN, +inf and -inf in x (nonfinite_plants: a tile's first and last pixel, halo pixels of border tiles, image corners, the
+    first and the last channel) at 3 x 304 x 144 with a bias: 257 blocks, all but one of two tiles, so deferred stores and a last
+    tile's epilogue both see them.  The kernel and the generic one agree: NaN at the same outputs, the same bits everywhere else.
+    Both store a NaN pre-activation as +0 (fmaxf(v, 0)), so no NaN is left and every output whose neighbourhood holds a NaN is +0.
+    Wherever the whole 3x3 x 32 neighbourhood is finite the output equals the oracle bit for bit.
+    The oracle itself applies ReLU as v > 0.0f ? v : 0.0f: a NaN or -inf pre-activation gives +0, +inf stays +inf
+    (tests/test_conv_packed_cpu.py pins that); its outputs beside non-finite inputs are not relied on here."""
+    N, H, W = rc.NONFINITE_SHAPE
+    assert rc.takes(N, H, W, pooled=pooled) == 1
+    p = rc.walk(N, H, W, pooled)
+    assert p["tmax"] >= 2
+    xh, wh, bh = _walk_inputs(N, H, W, "rand", ("non-finite", N, H, W))
+    for (n, yy, xx, ch, v) in nonfinite_plants(N, H, W, C):
+        xh[n, yy, xx, ch] = v
+    finite, has_nan = neighbourhoods(xh)
+    assert 0 < int(has_nan.sum()) < int((~finite).sum()) < 200
+    x, w, b = xh.cuda(), wh.cuda(), bh.cuda()
+    y, pl = _run_twice(x, w, b, pooled)
+    with generic():
+        ry, rp = _run(x, w, b, pooled)
+    nan = torch.isnan(y)
+    assert torch.equal(nan, torch.isnan(ry))
+    assert torch.equal(y.view(torch.int32)[~nan], ry.view(torch.int32)[~nan])
+    assert not bool(nan.any())
+    yh = y.cpu()
+    assert bool((yh[has_nan].view(torch.int32) == 0).all()), "a NaN pre-activation not stored as +0"
+    assert bool(torch.isinf(yh[~finite]).any())                   # the infinities did reach outputs
+    ref = co.conv2d(xh.numpy(), wh.numpy(), bh.numpy(), act="relu")
+    got = np.where(finite.numpy()[..., None], yh.numpy(), ref)
+    msg = mismatch(got, ref, p, H, W, bn=C)
+    assert msg is None, "outputs with a finite neighbourhood against the oracle\n%s" % msg
+    if pooled:
+        assert torch.equal(pl, _max_pool(y)) and torch.equal(pl, rp)
 
 
 def _logits_and_mask(net, x):
