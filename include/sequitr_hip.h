@@ -1632,7 +1632,7 @@ int sq_mask_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int H, int
  * could not be captured in a graph), and seeds from the Euclidean distance transform or its h-maxima.  Known limit: objects
  * whose eroded cores stay connected (three mutually overlapping disks) are not split.
  *
- * Kernels (sq_mask_split.hip).  A fixed chain of launches on `stream`, no host readback, no block waits on another, no
+ * Kernels (sq_split.hip, one program with "Volume clean-up: splitting": a frame is a volume with D = 1).  A fixed chain of launches on `stream`, no host readback, no block waits on another, no
  * flag is polled: the call can be captured in a graph.
  *   seeds    : one sq_mask_morph_u8 erosion launch, all classes, into a 1 B / pixel plane of the workspace.
  *   labels   : sq_ccl.h's row scan / merge / compress on the seed plane; a label is the root's linear index + 1 (the batch
@@ -1784,7 +1784,7 @@ int sq_volume_clear_border_u8(const uint8_t *mask, uint8_t *out, int N, int D, i
  * Not built: growth until nothing changes (it would need a readback inside the stream), EDT or h-maxima seeds,
  * spacing-aware (anisotropic) growth, the 18-neighbour structure.
  *
- * Kernels (sq_volume_split.hip).  A fixed chain of launches on `stream`, no host readback, no memset or memcpy calls, no
+ * Kernels (sq_split.hip, the planar split's program with depth).  A fixed chain of launches on `stream`, no host readback, no memset or memcpy calls, no
  * block waits on another, no flag is polled: the call can be captured in a graph.
  *   seeds    : plane structures: one sq_mask_morph_u8 erosion launch on the (N D, H, W) view into the workspace's byte
  *              plane.  cross and cube: ceil(r / SQ_MORPH3D_MAX_ITER) launches of sq_volume_morph_u8 (erosions compose

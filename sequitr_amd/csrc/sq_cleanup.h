@@ -1,4 +1,4 @@
-// What the clean-up entries check first (sq_maskops.hip, sq_volumeops.hip, sq_component_ops.hip), with a frame counted as
+// What the clean-up entries check first (sq_maskops.hip, sq_volumeops.hip, sq_component_ops.hip, sq_split.hip), with a frame counted as
 // a volume of one plane.  The two morphology kernels share no device code: the column-validity word and the start value
 // of a 4-pixel group as functions left their registers, LDS and occupancy alone but made the planar launch 0.3-0.5 %
 // slower, and the dilating-step rule and the merge of a plane's bits changed its register allocation.
@@ -7,10 +7,12 @@
 
 namespace {
 
-inline bool ranges_overlap(const void *a, const void *b, int64_t bytes) {
+inline bool ranges_overlap(const void *a, int64_t abytes, const void *b, int64_t bbytes) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
+    return x < y + (uintptr_t)bbytes && y < x + (uintptr_t)abytes;
 }
+
+inline bool ranges_overlap(const void *a, const void *b, int64_t bytes) { return ranges_overlap(a, bytes, b, bytes); }
 
 inline int64_t volume_elements(int N, int D, int H, int W) {   // -1: an extent < 1, or 2^31 or more elements
     if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return -1;

@@ -8,7 +8,7 @@
 //                 outwards from z while A(k) <= the best distance so far -- <=, not sq_edt3d_sq_f64's <: an equidistant
 //                 seed with a smaller label further out must still be seen.  The products and the sum are explicit
 //                 round-to-nearest operations (__dmul_rn / __dadd_rn), which the compiler may not contract into an fma.
-// sq_zone_graph3d: one wave per (n, d, h) row; runs of equal zone / equal (a, b) per direction make ONE atomic each.
+// sq_zone_graph3d: sq_zones.h's contact graph with depth, the program sq_zone_graph runs on frames.
 // A minimum of fixed expressions and sums of integers: the same bits on every run.
 #include <cmath>
 #include <cstdlib>
@@ -168,92 +168,6 @@ int zones3d_depth(const int *P, const int *L, int *zones, double *d2, int N, int
     return sq_check_launch("sq_label_zones3d_i32");
 }
 
-// ---- graph ----------------------------------------------------------------------------------------------------------
-// insert-and-add into the open-addressing table: the key is claimed with a 64-bit compare-and-swap; a slot carries two
-// 32-bit counts, [lateral, axial], and `which` names the one this run adds to
-__device__ __forceinline__ void table_add3d(u64 *__restrict__ keys, unsigned *__restrict__ counts, unsigned slots, u64 key,
-                                            unsigned len, int which, int *__restrict__ dropped) {
-    unsigned s = (unsigned)mix64(key) & (slots - 1u);
-    for (unsigned i = 0; i < slots; ++i) {
-        u64 k = __atomic_load_n(&keys[s], __ATOMIC_RELAXED);
-        if (k == 0ULL) {
-            k = atomicCAS(&keys[s], 0ULL, key);
-            if (k == 0ULL) k = key;
-        }
-        if (k == key) {
-            atomicAdd(&counts[(size_t)s * 2 + which], len);
-            return;
-        }
-        s = (s + 1u) & (slots - 1u);
-    }
-    atomicAdd(dropped, 1);                                      // every slot holds another pair
-}
-
-__device__ __forceinline__ int zone_value(int z, int max_label) { return (z < 1 || z > max_label) ? 0 : z; }
-
-__global__ __launch_bounds__(256) void zone_graph3d_kernel(const int *__restrict__ zones, long long *__restrict__ stats,
-                                                           u64 *__restrict__ keys, unsigned *__restrict__ counts,
-                                                           unsigned slots, int *__restrict__ dropped, int rows, int D, int H,
-                                                           int W, int max_label) {
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;                                      // whole waves leave
-    const int h = r % H, d = (r / H) % D, n = r / (H * D);      // H * D <= rows < 2^31
-    const int *row = zones + (size_t)r * W;
-    const size_t plane = (size_t)H * W;
-    const bool face_row = h == 0 || h == H - 1 || d == 0 || d == D - 1;
-    long long *st = stats + (size_t)n * ((size_t)max_label + 1) * 2;
-    const u64 head = (u64)n << (2 * LABEL_BITS);
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int col = c0 + lane;
-        const bool in = col < W;
-        const int z = in ? zone_value(row[col], max_label) : 0;
-        const int zh = (in && h + 1 < H) ? zone_value(row[col + W], max_label) : 0;       // the lower neighbour
-        const int zd = (in && d + 1 < D) ? zone_value(row[col + plane], max_label) : 0;   // the deeper neighbour
-        int zw = __shfl_down(z, 1);                                                        // the right neighbour
-        if (lane == 63) zw = col + 1 < W ? zone_value(row[col + 1], max_label) : 0;
-        // voxels and face voxels: one 64-bit add per run of equal zone
-        u64 mask = 0;
-        const u64 E = __ballot(in && (face_row || col == 0 || col == W - 1));
-        int len = run_length((u64)z, lane, &mask);
-        if (len) {
-            atomicAdd((u64 *)&st[(size_t)z * 2], (u64)len);
-            const int e = __popcll(E & mask);
-            if (e) atomicAdd((u64 *)&st[(size_t)z * 2 + 1], (u64)e);
-        }
-        // voxel pairs along w and h (lateral) and along d (axial) whose zones differ, both > 0
-        const u64 kw = pair_key(head, z, zw), kh = pair_key(head, z, zh), kd = pair_key(head, z, zd);
-        len = run_length(kw, lane, &mask);
-        if (len) table_add3d(keys, counts, slots, kw, (unsigned)len, 0, dropped);
-        len = run_length(kh, lane, &mask);
-        if (len) table_add3d(keys, counts, slots, kh, (unsigned)len, 0, dropped);
-        len = run_length(kd, lane, &mask);
-        if (len) table_add3d(keys, counts, slots, kd, (unsigned)len, 1, dropped);
-    }
-}
-
-__global__ __launch_bounds__(256) void zone_graph3d_compact_kernel(const u64 *__restrict__ keys,
-                                                                   const unsigned *__restrict__ counts, unsigned slots,
-                                                                   int *__restrict__ pairs, int max_pairs,
-                                                                   int *__restrict__ count, int *__restrict__ dropped) {
-    for (unsigned s = blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += gridDim.x * blockDim.x) {
-        const u64 k = keys[s];
-        if (k == 0ULL) continue;
-        const int idx = atomicAdd(count, 1);
-        if (idx < 0 || idx >= max_pairs) {                      // only once max_pairs rows are written: count ends at max_pairs
-            atomicSub(count, 1);
-            atomicAdd(dropped, 1);
-            continue;
-        }
-        int *row = pairs + (size_t)idx * 5;
-        row[0] = (int)(k >> (2 * LABEL_BITS));
-        row[1] = (int)((k >> LABEL_BITS) & LABEL_MASK);
-        row[2] = (int)(k & LABEL_MASK);
-        row[3] = (int)counts[(size_t)s * 2];
-        row[4] = (int)counts[(size_t)s * 2 + 1];
-    }
-}
-
 }  // namespace
 
 extern "C" int64_t sq_label_zones3d_workspace(int N, int D, int H, int W) {
@@ -302,10 +216,7 @@ extern "C" int sq_label_zones3d_i32(const int32_t *labels, int32_t *zones, doubl
               : zones3d_depth<false>(P, L, zones, nullptr, N, D, H, W, dz, max_distance, st);
 }
 
-extern "C" int64_t sq_zone_graph3d_workspace(int max_pairs) {
-    if (max_pairs < 1 || max_pairs > (1 << 28)) return -1;
-    return graph_slots(max_pairs) * 16;
-}
+extern "C" int64_t sq_zone_graph3d_workspace(int max_pairs) { return graph_bytes(max_pairs, 2); }
 
 extern "C" int sq_zone_graph3d(const int32_t *zones, int N, int D, int H, int W, int max_label, int64_t *stats,
                                int32_t *pairs, int max_pairs, int32_t *count, int32_t *dropped, void *workspace,
@@ -324,22 +235,6 @@ extern "C" int sq_zone_graph3d(const int32_t *zones, int N, int D, int H, int W,
                    !overlaps(workspace, wsb, pairs, (int64_t)max_pairs * 20) && !overlaps(workspace, wsb, count, 4) &&
                    !overlaps(workspace, wsb, dropped, 4),
                "sq_zone_graph3d: the workspace must not overlap zones or an output");
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned slots = (unsigned)graph_slots(max_pairs);
-    u64 *keys = reinterpret_cast<u64 *>(workspace);
-    unsigned *counts = reinterpret_cast<unsigned *>(keys + slots);
-    const int64_t table_words = (int64_t)slots * 4, stat_words = stb / 4;
-    hipLaunchKernelGGL(clear_words_kernel, dim3(nb_grid(table_words > stat_words ? table_words : stat_words)), dim3(256), 0, st,
-                       reinterpret_cast<unsigned *>(workspace), table_words, reinterpret_cast<unsigned *>(stats), stat_words,
-                       count, dropped);
-    int rc = sq_check_launch("sq_zone_graph3d");
-    if (rc) return rc;
-    const int rows = N * D * H;
-    hipLaunchKernelGGL(zone_graph3d_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, zones, reinterpret_cast<long long *>(stats),
-                       keys, counts, slots, dropped, rows, D, H, W, max_label);
-    rc = sq_check_launch("sq_zone_graph3d");
-    if (rc) return rc;
-    hipLaunchKernelGGL(zone_graph3d_compact_kernel, dim3(nb_grid(slots)), dim3(256), 0, st, keys, counts, slots, pairs,
-                       max_pairs, count, dropped);
-    return sq_check_launch("sq_zone_graph3d");
+    return zone_graph_run<true>("sq_zone_graph3d", zones, N, D, H, W, max_label, stats, stb / 4, pairs, max_pairs, count, dropped,
+                                workspace, (hipStream_t)stream);
 }

@@ -1,6 +1,6 @@
 // What the planar and the volumetric neighbourhood calls share (sq_neighbors.hip, sq_neighbors3d.hip): the two planar
-// passes of the feature transform, the clearing kernel, and the run / hash helpers of the contact graphs.  Everything
-// sits in an unnamed namespace: each translation unit gets its own copy, as with the other shared headers.
+// passes of the feature transform, the clearing kernel, and the contact graph (its run / hash helpers serve sq_link.hip
+// too).  Everything sits in an unnamed namespace: each translation unit gets its own copy, as with the other headers.
 //   rows    : per pixel the distance g along its row to the nearest seed and the smaller label of the at most two
 //             seeds at that distance; one wave per row over 64-pixel segments, the seed ballot, the nearest set bit
 //             to the left / right (clz / ffs) with a carry between segments, the label fetched from that lane
@@ -187,6 +187,136 @@ __device__ __forceinline__ int run_length(u64 key, int lane, u64 *mask_out) {
     const u64 upto_end = end == 64 ? ~0ULL : ((1ULL << end) - 1ULL);
     *mask_out = upto_end & (~0ULL << lane);
     return end - lane;
+}
+
+// ---- graph ----------------------------------------------------------------------------------------------------------
+// sq_zone_graph and sq_zone_graph3d: a frame is a volume with D = 1.  DEPTH (a volume's call) adds the deeper neighbour
+// and a second count per pair: a slot of the table carries COUNTS = 1 (frames) or 2 ([lateral, axial]) 32-bit counts,
+// and a row of `pairs` is [n, a, b] and the counts.
+
+// insert-and-add into the open-addressing table: the key is claimed with a 64-bit compare-and-swap, the count -- the
+// `which`-th of the slot's `stride` -- is a 32-bit add
+__device__ __forceinline__ void table_add(u64 *__restrict__ keys, unsigned *__restrict__ counts, unsigned slots, u64 key,
+                                          unsigned len, int stride, int which, int *__restrict__ dropped) {
+    unsigned s = (unsigned)mix64(key) & (slots - 1u);
+    for (unsigned i = 0; i < slots; ++i) {
+        u64 k = __atomic_load_n(&keys[s], __ATOMIC_RELAXED);
+        if (k == 0ULL) {
+            k = atomicCAS(&keys[s], 0ULL, key);
+            if (k == 0ULL) k = key;
+        }
+        if (k == key) {
+            atomicAdd(&counts[(size_t)s * stride + which], len);
+            return;
+        }
+        s = (s + 1u) & (slots - 1u);
+    }
+    atomicAdd(dropped, 1);                                      // every slot holds another pair
+}
+
+__device__ __forceinline__ int zone_value(int z, int max_label) { return (z < 1 || z > max_label) ? 0 : z; }
+
+// one wave per (n, d, h) row; runs of equal zone / equal (a, b) per direction make ONE atomic each.  D comes last: a
+// frame's launch never reads it, and with rows, H, W and max_label side by side a wave fetches them in one scalar load.
+template <bool DEPTH>
+__global__ __launch_bounds__(256) void zone_graph_kernel(const int *__restrict__ zones, long long *__restrict__ stats,
+                                                         u64 *__restrict__ keys, unsigned *__restrict__ counts,
+                                                         unsigned slots, int *__restrict__ dropped, int rows, int H, int W,
+                                                         int max_label, int D) {
+    constexpr int COUNTS = DEPTH ? 2 : 1;
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;                                      // whole waves leave
+    const int h = r % H, d = DEPTH ? (r / H) % D : 0, n = DEPTH ? r / (H * D) : r / H;     // H * D <= rows < 2^31
+    const int *row = zones + (size_t)r * W;
+    const size_t plane = (size_t)H * W;
+    const bool face_row = h == 0 || h == H - 1 || (DEPTH && (d == 0 || d == D - 1));
+    long long *st = stats + (size_t)n * ((size_t)max_label + 1) * 2;
+    const u64 head = (u64)n << (2 * LABEL_BITS);
+    for (int c0 = 0; c0 < W; c0 += 64) {
+        const int col = c0 + lane;
+        const bool in = col < W;
+        // the loads first, the range checks after: checked inside the conditionals, each load waits for the one before
+        int z = in ? row[col] : 0;
+        int zh = (in && h + 1 < H) ? row[col + W] : 0;                                     // the lower neighbour
+        int zd = (DEPTH && in && d + 1 < D) ? row[col + plane] : 0;                        // the deeper neighbour
+        z = zone_value(z, max_label), zh = zone_value(zh, max_label), zd = zone_value(zd, max_label);
+        int zw = __shfl_down(z, 1);                                                        // the right neighbour
+        if (lane == 63) zw = col + 1 < W ? zone_value(row[col + 1], max_label) : 0;
+        // cells and cells on the frame's border / the volume's faces: one 64-bit add per run of equal zone
+        u64 mask = 0;
+        const u64 E = __ballot(in && (face_row || col == 0 || col == W - 1));
+        int len = run_length((u64)z, lane, &mask);
+        if (len) {
+            atomicAdd((u64 *)&st[(size_t)z * 2], (u64)len);
+            const int e = __popcll(E & mask);
+            if (e) atomicAdd((u64 *)&st[(size_t)z * 2 + 1], (u64)e);
+        }
+        // pairs of cells along w and h (lateral) and along d (axial) whose zones differ, both > 0
+        const u64 kw = pair_key(head, z, zw), kh = pair_key(head, z, zh);
+        len = run_length(kw, lane, &mask);
+        if (len) table_add(keys, counts, slots, kw, (unsigned)len, COUNTS, 0, dropped);
+        len = run_length(kh, lane, &mask);
+        if (len) table_add(keys, counts, slots, kh, (unsigned)len, COUNTS, 0, dropped);
+        if (DEPTH) {
+            const u64 kd = pair_key(head, z, zd);
+            len = run_length(kd, lane, &mask);
+            if (len) table_add(keys, counts, slots, kd, (unsigned)len, COUNTS, 1, dropped);
+        }
+    }
+}
+
+template <int COUNTS>
+__global__ __launch_bounds__(256) void zone_graph_compact_kernel(const u64 *__restrict__ keys,
+                                                                 const unsigned *__restrict__ counts, unsigned slots,
+                                                                 int *__restrict__ pairs, int max_pairs,
+                                                                 int *__restrict__ count, int *__restrict__ dropped) {
+    for (unsigned s = blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += gridDim.x * blockDim.x) {
+        const u64 k = keys[s];
+        if (k == 0ULL) continue;
+        const int idx = atomicAdd(count, 1);
+        if (idx < 0 || idx >= max_pairs) {                      // only once max_pairs rows are written: count ends at max_pairs
+            atomicSub(count, 1);
+            atomicAdd(dropped, 1);
+            continue;
+        }
+        int *row = pairs + (size_t)idx * (3 + COUNTS);
+        row[0] = (int)(k >> (2 * LABEL_BITS));
+        row[1] = (int)((k >> LABEL_BITS) & LABEL_MASK);
+        row[2] = (int)(k & LABEL_MASK);
+#pragma unroll
+        for (int c = 0; c < COUNTS; ++c) row[3 + c] = (int)counts[(size_t)s * COUNTS + c];
+    }
+}
+
+// bytes of the table for `max_pairs` pairs: 8 of key and 4 per count a slot
+inline int64_t graph_bytes(int max_pairs, int counts) {
+    if (max_pairs < 1 || max_pairs > (1 << 28)) return -1;
+    return (graph_slots(max_pairs) * (8 + 4 * counts) + 15) / 16 * 16;
+}
+
+// clear -> graph -> compact, after the entry's own checks; `stat_words`: the 32-bit words of `stats`
+template <bool DEPTH>
+int zone_graph_run(const char *who, const int *zones, int N, int D, int H, int W, int max_label, int64_t *stats,
+                   int64_t stat_words, int *pairs, int max_pairs, int *count, int *dropped, void *workspace, hipStream_t st) {
+    constexpr int COUNTS = DEPTH ? 2 : 1;
+    const unsigned slots = (unsigned)graph_slots(max_pairs);
+    u64 *keys = reinterpret_cast<u64 *>(workspace);
+    unsigned *counts = reinterpret_cast<unsigned *>(keys + slots);
+    const int64_t table_words = (int64_t)slots * (2 + COUNTS);
+    hipLaunchKernelGGL(clear_words_kernel, dim3(nb_grid(table_words > stat_words ? table_words : stat_words)), dim3(256), 0, st,
+                       reinterpret_cast<unsigned *>(workspace), table_words, reinterpret_cast<unsigned *>(stats), stat_words,
+                       count, dropped);
+    int rc = sq_check_launch(who);
+    if (rc) return rc;
+    const int rows = N * D * H;
+    hipLaunchKernelGGL(zone_graph_kernel<DEPTH>, dim3((rows + 3) / 4), dim3(256), 0, st, zones,
+                       reinterpret_cast<long long *>(stats), keys, counts, slots, dropped, rows, H, W, max_label, D);
+    rc = sq_check_launch(who);
+    if (rc) return rc;
+    hipLaunchKernelGGL(zone_graph_compact_kernel<COUNTS>, dim3(nb_grid(slots)), dim3(256), 0, st, keys, counts, slots, pairs,
+                       max_pairs, count, dropped);
+    return sq_check_launch(who);
 }
 
 }  // namespace

@@ -144,21 +144,28 @@ def split(mask, erosions, structure='cross', reach=None, classes=None, out=None,
     with `structure`; they grow back through their class for `reach` = 1 .. SPLIT_MAX_REACH synchronous steps (None:
     2 * erosions), the smallest label winning where several arrive together, and a labelled pixel with a same-class
     neighbour of a smaller label becomes background.  Everything else is unchanged; bytes >= classes pass through."""
-    if structure not in STRUCTURES:
-        raise ValueError("structure must be one of %s, got %r" % (sorted(STRUCTURES), structure))
+    return _split(mask, erosions, structure, reach, classes, out, workspace, 3, STRUCTURES, MORPH_MAX_ITER, SPLIT_MAX_REACH,
+                  lambda r, st: 2 * r, "sq_mask_split_workspace", "sq_mask_split_u8")
+
+
+def _split(mask, erosions, structure, reach, classes, out, workspace, rank, structures, max_erosions, max_reach,
+           default_reach, workspace_fn, split_fn):
+    """split and volumeops.split3d: the rank of the mask, `structures` names -> codes, the two caps,
+    default_reach(erosions, structure) for reach=None, and the names of the library's two functions"""
+    if structure not in structures:
+        raise ValueError("structure must be one of %s, got %r" % (sorted(structures), structure))
     erosions = int(erosions)
-    if not 1 <= erosions <= MORPH_MAX_ITER:
-        raise ValueError("erosions must be 1 .. %d, got %d" % (MORPH_MAX_ITER, erosions))
-    reach = 2 * erosions if reach is None else int(reach)
-    if not 1 <= reach <= SPLIT_MAX_REACH:
-        raise ValueError("reach must be 1 .. %d, got %d" % (SPLIT_MAX_REACH, reach))
-    classes = _check_mask(mask, classes)
+    if not 1 <= erosions <= max_erosions:
+        raise ValueError("erosions must be 1 .. %d, got %d" % (max_erosions, erosions))
+    reach = default_reach(erosions, structure) if reach is None else int(reach)
+    if not 1 <= reach <= max_reach:
+        raise ValueError("reach must be 1 .. %d, got %d" % (max_reach, reach))
+    classes = _check_mask(mask, classes, rank)
     out = _check_out(out, mask)
     lib = _lib.load()
-    ws = _workspace(lib.sq_mask_split_workspace, mask, workspace)
-    N, H, W = _dims(mask)
-    _lib.check(lib.sq_mask_split_u8(mask.data_ptr(), out.data_ptr(), N, H, W, classes, erosions, STRUCTURES[structure], reach,
-                                    ws.data_ptr(), _stream(mask)), "sq_mask_split_u8")
+    ws = _workspace(getattr(lib, workspace_fn), mask, workspace)
+    _lib.check(getattr(lib, split_fn)(mask.data_ptr(), out.data_ptr(), *(_dims(mask) + (
+        classes, erosions, structures[structure], reach, ws.data_ptr(), _stream(mask)))), split_fn)
     return out
 
 
@@ -241,6 +248,16 @@ def _is_int(v, lo, hi=None):
     return not isinstance(v, bool) and isinstance(v, int) and v >= lo and (hi is None or v <= hi)
 
 
+def _check_split_step(where, full, structures, max_erosions, max_reach):
+    """the 'split' step of a MaskCleanup list and the 'split3d' step of a VolumeCleanup list"""
+    if not _is_int(full['erosions'], 1, max_erosions):
+        raise ValueError("%s: erosions must be an integer 1 .. %d, got %r" % (where, max_erosions, full['erosions']))
+    if not isinstance(full['structure'], str) or full['structure'] not in structures:
+        raise ValueError("%s: structure must be one of %s, got %r" % (where, sorted(structures), full['structure']))
+    if full['reach'] is not None and not _is_int(full['reach'], 1, max_reach):
+        raise ValueError("%s: reach must be an integer 1 .. %d or null, got %r" % (where, max_reach, full['reach']))
+
+
 class MaskCleanup(_Cleanup):
     """A validated list of clean-up steps, e.g. [{"op": "open", "iterations": 2, "structure": "cross"},
     {"op": "fill_holes", "max_area": 400}, {"op": "split", "erosions": 8}, {"op": "clear_border"}].  Unknown ops, unknown keys and bad values raise a
@@ -252,12 +269,10 @@ class MaskCleanup(_Cleanup):
             raise ValueError("%s: iterations must be an integer 1 .. %d, got %r" % (where, MORPH_MAX_ITER, full['iterations']))
         if op == 'fill_holes' and full['max_area'] is not None and not _is_int(full['max_area'], 1):
             raise ValueError("%s: max_area must be a positive integer or null, got %r" % (where, full['max_area']))
-        if op == 'split' and not _is_int(full['erosions'], 1, MORPH_MAX_ITER):
-            raise ValueError("%s: erosions must be an integer 1 .. %d, got %r" % (where, MORPH_MAX_ITER, full['erosions']))
-        if 'structure' in full and full['structure'] not in STRUCTURES:
+        if op == 'split':
+            _check_split_step(where, full, STRUCTURES, MORPH_MAX_ITER, SPLIT_MAX_REACH)
+        elif 'structure' in full and full['structure'] not in STRUCTURES:
             raise ValueError("%s: structure must be one of %s, got %r" % (where, sorted(STRUCTURES), full['structure']))
-        if op == 'split' and full['reach'] is not None and not _is_int(full['reach'], 1, SPLIT_MAX_REACH):
-            raise ValueError("%s: reach must be an integer 1 .. %d or null, got %r" % (where, SPLIT_MAX_REACH, full['reach']))
 
     def _step_workspace(self, lib, s, dims):
         fn = {'fill_holes': lib.sq_mask_fill_holes_workspace, 'clear_border': lib.sq_mask_clear_border_workspace,

@@ -130,21 +130,9 @@ def split3d(mask, erosions, structure='cross', reach=None, classes=None, out=Non
     for 'cube', 2 * erosions otherwise), the smallest label winning where several arrive together, and a labelled voxel
     with a same-class neighbour of a smaller label becomes background.  Everything else is unchanged; bytes >= classes
     pass through."""
-    if structure not in SPLIT3D_STRUCTURES:
-        raise ValueError("structure must be one of %s, got %r" % (sorted(SPLIT3D_STRUCTURES), structure))
-    erosions = int(erosions)
-    if not 1 <= erosions <= SPLIT3D_MAX_EROSIONS:
-        raise ValueError("erosions must be 1 .. %d, got %d" % (SPLIT3D_MAX_EROSIONS, erosions))
-    reach = default_reach3d(erosions, structure) if reach is None else int(reach)
-    if not 1 <= reach <= SPLIT3D_MAX_REACH:
-        raise ValueError("reach must be 1 .. %d, got %d" % (SPLIT3D_MAX_REACH, reach))
-    classes = maskops._check_mask(mask, classes, 4)
-    out = maskops._check_out(out, mask)
-    lib = _lib.load()
-    ws = maskops._workspace(lib.sq_volume_split_workspace, mask, workspace)
-    _lib.check(lib.sq_volume_split_u8(mask.data_ptr(), out.data_ptr(), *(maskops._dims(mask) + (
-        classes, erosions, SPLIT3D_STRUCTURES[structure], reach, ws.data_ptr(), maskops._stream(mask)))), "sq_volume_split_u8")
-    return out
+    return maskops._split(mask, erosions, structure, reach, classes, out, workspace, 4, SPLIT3D_STRUCTURES,
+                          SPLIT3D_MAX_EROSIONS, SPLIT3D_MAX_REACH, default_reach3d, "sq_volume_split_workspace",
+                          "sq_volume_split_u8")
 
 
 class VolumeCleanup(maskops._Cleanup):
@@ -171,12 +159,7 @@ class VolumeCleanup(maskops._Cleanup):
             if not isinstance(full['planar'], bool):
                 raise ValueError("%s: planar must be true or false, got %r" % (where, full['planar']))
         elif op == 'split3d':
-            if not maskops._is_int(full['erosions'], 1, SPLIT3D_MAX_EROSIONS):
-                raise ValueError("%s: erosions must be an integer 1 .. %d, got %r" % (where, SPLIT3D_MAX_EROSIONS, full['erosions']))
-            if not isinstance(full['structure'], str) or full['structure'] not in SPLIT3D_STRUCTURES:
-                raise ValueError("%s: structure must be one of %s, got %r" % (where, sorted(SPLIT3D_STRUCTURES), full['structure']))
-            if full['reach'] is not None and not maskops._is_int(full['reach'], 1, SPLIT3D_MAX_REACH):
-                raise ValueError("%s: reach must be an integer 1 .. %d or null, got %r" % (where, SPLIT3D_MAX_REACH, full['reach']))
+            maskops._check_split_step(where, full, SPLIT3D_STRUCTURES, SPLIT3D_MAX_EROSIONS, SPLIT3D_MAX_REACH)
         elif not isinstance(full['faces'], str) or full['faces'] not in FACES:
             raise ValueError("%s: faces must be one of %s, got %r" % (where, sorted(FACES), full['faces']))
 

@@ -99,7 +99,7 @@ ROWS = [
     ('linking.relabel/V=1', 'relabel1x3', 'chunk_grid/relabel', 66000, 3),
     ('linking.relabel/V=4', 'relabel4', 'chunk_grid/relabel', 41000, 2),
 ]
-# No cap row: zone_graph_kernel and zone_graph3d_kernel take a wave per row and their grid is not capped, the capped launches
+# No cap row: zone_graph_kernel (with and without depth) takes a wave per row and its grid is not capped, the capped launches
 # of these entries walk the pair table (TABLE_ROWS).  The graphs are run on the zones of two big inputs all the same, as the
 # issue asks: (entry, input).
 BIG_INPUT_ROWS = [('neighbors.zone_graph', 'labels2'), ('neighbors.zone_graph3d', 'labelvol2')]

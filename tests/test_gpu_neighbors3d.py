@@ -15,6 +15,7 @@ from tests import neighbors3d_cases as n3
 from tests import neighbors_cases as nc
 from tests import objects_cases as oc
 from tests.test_gpu_neighbors import Guarded, dev
+from tests.test_gpu_neighbors import graph_raw as planar_graph_raw
 
 pytestmark = pytest.mark.gpu
 SQ_EINVAL = -1
@@ -119,6 +120,25 @@ def test_graph_equals_the_restatement(case):
     assert s.dtype == np.int64 and p.dtype == np.int64 and p.shape[1] == 5
     assert np.array_equal(s, want_s) and np.array_equal(p, want_p)
     assert np.array_equal(z_d.cpu().numpy(), z)
+
+
+def test_a_frame_is_a_volume_of_one_slice():
+    """sq_zone_graph and sq_zone_graph3d are one program: at D = 1 the volume call gives the frame call's rows, no axial
+    contact, and a border column equal to the area column -- every voxel of a one-slice volume lies on a face"""
+    name, z, ml = nc.random_zones(6, 2, 37, 130, 20)            # about 20 zones over three 64-lane segments a row
+    z = z.copy()
+    z[0, 5:9, 40:60] = 0                                        # no zone: borders nothing
+    z[1, 20, 100:] = ml + 3                                     # out of range either way: counts as 0
+    z[1, 30:, 64] = -2
+    assert z.shape == (2, 37, 130) and 15 <= len(np.unique(z[(z >= 1) & (z <= ml)])) <= ml
+    want_s, want_p = nc.graph_ref(z, ml)
+    assert len(want_p) > 20
+    s2, p2, count2, dropped2 = planar_graph_raw(dev(z), ml, 4 * len(want_p) + 3)
+    s3, p3, count3, dropped3 = graph_raw(dev(z[:, None]), ml, 4 * len(want_p) + 3)
+    assert dropped2 == 0 and dropped3 == 0 and count2 == count3 == len(want_p)
+    assert np.array_equal(s2, want_s) and np.array_equal(p2, want_p)
+    assert np.array_equal(p3[:, :4], p2) and not p3[:, 4].any()
+    assert np.array_equal(s3[:, :, 0], s2[:, :, 0]) and np.array_equal(s3[:, :, 1], s3[:, :, 0])
 
 
 def test_too_little_room_is_reported_and_the_wrapper_comes_back_with_more():

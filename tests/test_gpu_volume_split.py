@@ -5,7 +5,9 @@ import numpy as np
 import pytest
 import torch
 
-from sequitr_amd import volumeops
+from sequitr_amd import maskops, volumeops
+from tests import mask_cleanup_cases as mc
+from tests import mask_split_cases as ms
 from tests import volume_cleanup_cases as vc
 from tests import volume_split_cases as sc
 
@@ -111,6 +113,33 @@ def test_erosion_chains(monkeypatch, case):
     assert sc.count_objects(want, C) == 2
     # a dense random volume of several bricks through the same chain; where no core survives it comes back unchanged
     check(monkeypatch, vc.random_volume(r, 1, 2 * TILE[0] + 1, TILE[1] + 3, TILE[2] + 2, 3, 0.97), 3, r, st, 5)
+
+
+@pytest.mark.parametrize("st,plane_st", [("cross", "plane_cross"), ("square", "plane_square")])
+def test_a_frame_is_a_volume_of_one_slice(monkeypatch, st, plane_st):
+    """sq_mask_split_u8 and sq_volume_split_u8 are one program after the seeds: at D = 1 the plane structures give the
+    planar split, under every regrowth form of both switches.  The mask spans 2 x 3 planar tiles and 5 x 5 bricks; the
+    reaches are K - 1, K, K + 1 of both geometries and one with a remainder launch.  (The 3-D structures are no part of
+    this: at D = 1 their erosion removes everything, by scipy's definition.)"""
+    m = np.concatenate([ms.seam_pairs(maskops.SPLIT_TILE, 4)[:, :70, :150], mc.random_mask(9, 1, 70, 150, 3, 0.9)])
+    d2, d3 = dev(m), dev(m[:, None])
+    for reach in (1, 2, 3, 7, 8, 9, 19):
+        want = ms.split_ref(m, 4, st, reach, 3)
+        for planar_form in (None, "1", "0"):
+            if planar_form is None:
+                monkeypatch.delenv("SQ_SPLIT_LDS", raising=False)
+            else:
+                monkeypatch.setenv("SQ_SPLIT_LDS", planar_form)
+            frame = maskops.split(d2, 4, st, reach, classes=3).cpu().numpy()
+            assert np.array_equal(frame, want), (st, reach, planar_form)
+
+        def run(what):
+            volume = volumeops.split3d(d3, 4, plane_st, reach, classes=3)[:, 0].cpu().numpy()
+            assert np.array_equal(volume, want), (plane_st, reach, what)
+
+        both_forms(monkeypatch, run)
+    monkeypatch.delenv("SQ_SPLIT_LDS", raising=False)
+    assert (want != m).any()
 
 
 def test_guards_views_and_overlap(monkeypatch):

@@ -61,12 +61,14 @@ def test_the_capped_launches_are_the_ones_the_table_names():
     """which helper sizes which launch: a launch moved to another helper must move its rows"""
     src = lambda f: open(os.path.join(ROOT, 'sequitr_amd/csrc', f)).read()   # noqa: E731
     assert 'tgrid(cc_grid(total)), fgrid(cc_grid(N * face_count(D, H, W, lateral)))' in src('sq_component_ops.hip')
-    assert 'tgrid(cc_grid(total))' in src('sq_mask_split.hip') and 'tgrid(cc_grid(total))' in src('sq_volume_split.hip')
+    assert 'tgrid(cc_grid(total))' in src('sq_split.hip')       # both splits: one driver
     assert src('sq_neighbors.hip').count('dim3(nb_grid(px))') == 2
     n3d = src('sq_neighbors3d.hip')
     assert 'dim3(nb_grid(vox))' in n3d and 'dim3(nb_grid((int64_t)N * D * H * W))' in n3d
-    for f in ('sq_neighbors.hip', 'sq_neighbors3d.hip', 'sq_link.hip'):
+    for f in ('sq_zones.h', 'sq_link.hip'):                     # sq_zones.h: both zone graphs, one driver
         assert 'dim3(nb_grid(slots))' in src(f) and 'nb_grid(table_words >' in src(f)
+    for f, run in (('sq_neighbors.hip', 'zone_graph_run<false>('), ('sq_neighbors3d.hip', 'zone_graph_run<true>(')):
+        assert run in src(f)
     assert 'dim3(fe_grid((int64_t)F * H * W))' in src('sq_frontend.hip')
 
 

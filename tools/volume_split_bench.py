@@ -277,8 +277,8 @@ def fold_trace(trace_dir, line):
     if len(files) != 1:
         raise SystemExit('expected one kernel_trace.csv under %s, found %d' % (trace_dir, len(files)))
     rows = sorted(csv.DictReader(open(files[0])), key=lambda r: int(r['Start_Timestamp']))
-    groups = (('erosion', 'morph_kernel'), ('labelling', 'cc_'), ('lds', 'vsplit_grow_lds_kernel'),
-              ('step', 'vsplit_grow_step_kernel'), ('cut', 'vsplit_cut_kernel'))
+    groups = (('erosion', 'morph_kernel'), ('labelling', 'cc_'), ('lds', 'split_grow_lds_kernel'),
+              ('step', 'split_grow_step_kernel'), ('cut', 'split_cut_kernel'))
     calls, last = [], None
     for r in rows:
         name = r['Kernel_Name']
